@@ -71,7 +71,17 @@ def parse_args():
                   help='sites of the timed batch checked against the oracle after the timed region')
   ap.add_argument('--cpu-sample', type=int, default=0,
                   help='candidates in the CPU-baseline sample (0 = auto)')
-  return ap.parse_args()
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='resident mode: after the timed steps write what the last timed step computed as DIR/<name>.npy '
+                       '(float32 / float64, at most 64 MB in all), per workload: the probabilities of every candidate '
+                       'and a fixed sample of the pile-up tensors they were classified from.  The inputs are seeded, '
+                       'so two builds run with the same arguments can be compared file for file')
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be at least 1 and --warmup at least 0')
+  if args.dump_outputs is not None and args.mode != 'resident':
+    ap.error('--dump-outputs covers the resident mode')
+  return args
 
 
 def algorithmic_bytes_per_item(batch, out_channels):
@@ -172,6 +182,30 @@ def reduce_elapsed(elapsed, n_items, world, device):
   return float(t.item()), float(total.item())
 
 
+DUMP_PILEUPS = 16              # pile-up tensors per workload in --dump-outputs (ont50: 16 x 100x199x9 x 4 B = 11.5 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_outputs(workload, probs, images):
+  """--dump-outputs: what the last timed step handed its caller, copied to the host before anything else runs on the
+  buffers -- every candidate's probabilities and DUMP_PILEUPS of the pile-up tensors, picked by a fixed seed."""
+  n = images.shape[0]
+  pick = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_PILEUPS, n), replace=False))
+  return {workload + '_probs': probs.cpu().numpy().astype(np.float32),
+          workload + '_pileup_index': pick.astype(np.float64),
+          workload + '_pileups': images[torch.from_numpy(pick).to(images.device)].cpu().numpy().astype(np.float32)}
+
+
+def write_outputs(directory, arrays):
+  total = sum(a.nbytes for a in arrays.values())
+  if total > DUMP_LIMIT_BYTES:
+    raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def run_rank(args, rank, local_rank, world):
   if world != args.gpus and world > 1:
     raise SystemExit('--gpus must equal WORLD_SIZE')
@@ -192,7 +226,11 @@ def run_rank(args, rank, local_rank, world):
   if args.workload != 'illumina30':
     if world > 1 or args.mode != 'resident':
       raise SystemExit('--workload %s runs in resident mode on one GPU' % args.workload)
-    return longread_bench(args, dev, local_rank)
+    dump = {} if args.dump_outputs is not None else None
+    longread_bench(args, dev, local_rank, dump=dump)
+    if dump is not None:
+      write_outputs(args.dump_outputs, dump)
+    return
 
   C = args.channels
   opts = synth.illumina_options(C)
@@ -257,6 +295,13 @@ def run_rank(args, rank, local_rank, world):
   lib = _lib.lib()
   # ---- timed region: exactly K steps, barrier + synchronize on both sides ----
   elapsed, probs = timed_steps(step, sync_all, args.warmup, args.steps)
+  dump = None
+  if args.dump_outputs is not None and rank == 0:
+    dump = snapshot_outputs('illumina30', probs, images)
+    if gathered is not None:         # the caller of a multi-GPU step receives every rank's probabilities + ids
+      all_p, all_i = gathered['all']
+      dump['illumina30_probs'] = all_p.cpu().numpy().astype(np.float32)
+      dump['illumina30_candidate_ids'] = all_i.cpu().numpy().astype(np.float64)
   # ---- instrumented pass: the SAME K steps again with a HIP event pair around
   # every kernel launch, on the launch stream.  Event profiling forces eager
   # launches (the timed region replays the forward as one hipGraph), so it is
@@ -392,11 +437,13 @@ def run_rank(args, rank, local_rank, world):
       for w in ('hifi35', 'ont50'):
         sub = argparse.Namespace(**vars(args))
         sub.workload = w
-        full = longread_bench(sub, dev, local_rank, emit=False)
+        full = longread_bench(sub, dev, local_rank, emit=False, dump=dump)
         out['workloads'][w] = {k: full[k] for k in ('metric', 'value', 'value_dense', 'unit', 'ms_per_step',
                                                     'ms_per_step_dense', 'config', 'roofline', 'roofline_encoder',
                                                     'other_kernels_ms_per_step', 'calibration', 'blank_row_skipping',
                                                     'parity', 'precise', 'fast') if k in full}
+    if dump is not None:
+      write_outputs(args.dump_outputs, dump)
     print(json.dumps(out))
   if world > 1:
     dist.destroy_process_group()
@@ -802,7 +849,7 @@ def make_longread_workload(kind, n, seed=None):
   return synth.make_longread_workload(kind, n, seed=seed)
 
 
-def longread_bench(args, dev, local_rank, emit=True):
+def longread_bench(args, dev, local_rank, emit=True, dump=None):
   """`--workload hifi35 | ont50`: the long-read shapes of SURVEY.md 8(d) / BASELINE configs[3], [4] through
   the same two entry points, one JSON line each (never the contract's `value`).
 
@@ -851,6 +898,8 @@ def longread_bench(args, dev, local_rank, emit=True):
     torch.cuda.synchronize(dev)
 
   elapsed, probs = timed_steps(step, sync_all, args.warmup, args.steps)
+  if dump is not None:
+    dump.update(snapshot_outputs(args.workload, probs, images))
   lib.dv_set_profiling(1)
   for _ in range(args.steps):
     step()

@@ -33,3 +33,16 @@ class OracleEncoder:
 
 def make(options):
   return OracleEncoder(options)
+
+
+class OracleDeviceEncoder:
+  """Stands in for make_examples_native._Encoder in the CPU suite: same call, pixels from the oracle."""
+
+  def __init__(self, pic):
+    self._pic = pic
+
+  def encode(self, batch, out_channels, min_bytes=0):
+    images, rows = O.encode_packed(self._pic, batch, out_channels, n_threads=4)
+    if images.size < min_bytes:
+      images = np.concatenate([images, np.zeros(min_bytes - images.size, np.uint8)])
+    return images, rows

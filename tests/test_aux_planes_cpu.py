@@ -290,7 +290,7 @@ def test_methylation_from_a_bam_reaches_the_pixels(tmp_path):
   from deepvariant_amd import make_examples_native as men
   from oracle import oracle as O
   from tests import fuzz_inputs as FZ
-  from tests.test_reference_examples_cpu import OracleDeviceEncoder
+  from tests.oracle_adapter import OracleDeviceEncoder
   rng = np.random.default_rng(12)
   L = 600
   ref_seq = ''.join('ACGT'[int(i)] for i in rng.integers(0, 4, size=L))

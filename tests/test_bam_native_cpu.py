@@ -2,7 +2,7 @@
 restatement of nucleus' SamReader semantics, on a synthetic BGZF BAM written here (every
 flag combination the read requirements look at, every CIGAR op, HP tags of all integer
 types behind Z / B / f tags, records straddling BGZF blocks), and on the reference's own
-test BAMs when they are present in the container."""
+test BAMs (bundled under tests/golden/; the PacBio one where the reference tree is present)."""
 import os
 import struct
 import zlib
@@ -114,30 +114,47 @@ def test_errors_are_reported(tmp_path):
 
 
 REF_INPUT = '/root/reference/deepvariant/testdata/input'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason='reference testdata not in this container')
+def _bundled(tmp_path, npz, files):
+  """Writes the reference test files kept byte for byte in tests/golden/<npz> ({file name: array name}) to tmp_path."""
+  with np.load(os.path.join(GOLDEN, npz)) as z:
+    for name, key in files.items():
+      (tmp_path / name).write_bytes(z[key].tobytes())
+
+
+def _reference_bam(tmp_path, bam):
+  """deepvariant/testdata/input/<bam> with its .bai: NA12878's slice from its bundled copy
+  (tests/golden/na12878_100kb.npz), the PacBio BAM (not bundled) from the reference tree where it is present."""
+  if bam == 'NA12878_S1.chr20.10_10p1mb.bam':
+    _bundled(tmp_path, 'na12878_100kb.npz', {bam: 'bam', bam + '.bai': 'bai'})
+    return str(tmp_path / bam)
+  if not os.path.isdir(REF_INPUT):
+    pytest.skip('reference testdata not in this container')
+  return os.path.join(REF_INPUT, bam)
+
+
 @pytest.mark.parametrize('bam,contig,start,end,mapq', [
     ('NA12878_S1.chr20.10_10p1mb.bam', 'chr20', 9_999_000, 10_012_000, 5),
     ('test_pacbio.chr20_100kbp_at_9mb.bam', 'chr20', 8_900_000, 9_200_000, 1)])
-def test_native_equals_python_reader_on_reference_bams(bam, contig, start, end, mapq):
-  path = os.path.join(REF_INPUT, bam)
+def test_native_equals_python_reader_on_reference_bams(bam, contig, start, end, mapq, tmp_path):
+  path = _reference_bam(tmp_path, bam)
   nat = packing.ReadTable.from_bam(path, contig, start, end, min_mapping_quality=mapq)
   _assert_same(nat, _python_table(path, contig, start, end, min_mapping_quality=mapq))
   assert nat.n_reads in (6014, 281)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INPUT), reason='reference testdata not in this container')
 @pytest.mark.parametrize('bam,regions,mapq', [
     ('NA12878_S1.chr20.10_10p1mb.bam',
      [(9_999_000, 10_012_000), (10_050_000, 10_051_000), (0, 1 << 40), (10_099_900, 10_200_000),
       (5, 10)], 5),
     ('test_pacbio.chr20_100kbp_at_9mb.bam',
      [(8_900_000, 9_200_000), (9_050_000, 9_050_100), (9_099_000, 9_099_500)], 1)])
-def test_bai_indexed_read_equals_full_scan(bam, regions, mapq, monkeypatch):
+def test_bai_indexed_read_equals_full_scan(bam, regions, mapq, monkeypatch, tmp_path):
   """With <bam>.bai next to the file only the BGZF members the index points at are read
   (reg2bins + linear index, SAMv1 5.2); the result must be the full scan's, read for read."""
-  path = os.path.join(REF_INPUT, bam)
+  path = _reference_bam(tmp_path, bam)
   assert os.path.exists(path + '.bai')
   for start, end in regions:
     monkeypatch.delenv('DV_BAM_NO_INDEX', raising=False)
@@ -194,16 +211,14 @@ def test_bgzf_isize_is_capped(tmp_path):
     packing.ReadTable.from_bam(path, 'chrA', 0, 1000)
 
 
-NUCLEUS_TESTDATA = '/root/reference/third_party/nucleus/testdata'
-
-
-@pytest.mark.skipif(not os.path.isdir(NUCLEUS_TESTDATA), reason='reference testdata not in this container')
-def test_known_answers_of_the_reference_sam_reader_tests():
+def test_known_answers_of_the_reference_sam_reader_tests(tmp_path):
   """Counts and coordinates the REFERENCE's own tests hold for its test.bam
   (third_party/nucleus/io/sam_reader_test.cc:311-418: SimpleQueriesWork,
   ThatRangeIsExactlyCorrect, QueriedRespectsReadRequirements) -- an anchor for the native
-  reader that does not go through this repo's Python reader."""
-  path = os.path.join(NUCLEUS_TESTDATA, 'test.bam')
+  reader that does not go through this repo's Python reader.  test.bam (+ .bai) is bundled
+  byte for byte in tests/golden/nucleus_sam.npz."""
+  _bundled(tmp_path, 'nucleus_sam.npz', {'test.bam': 'test_bam', 'test.bam.bai': 'test_bam_bai'})
+  path = str(tmp_path / 'test.bam')
   everything = dict(keep_duplicates=True, keep_supplementary=True, keep_secondary=True, keep_failed_qc=True,
                     keep_improperly_placed=True)
   # default ReadRequirements: 105 of the 106 records (the unmapped one goes); min_mapping_quality 38: 104

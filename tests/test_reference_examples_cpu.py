@@ -22,19 +22,7 @@ if not O.reference_available():
 from deepvariant_amd import dv_types as T                   # noqa: E402
 from deepvariant_amd import make_examples_native as men     # noqa: E402
 from deepvariant_amd import protowire as pw                 # noqa: E402
-
-
-class OracleDeviceEncoder:
-  """Stands in for make_examples_native._Encoder in the CPU suite: same call, pixels from the oracle."""
-
-  def __init__(self, pic):
-    self._pic = pic
-
-  def encode(self, batch, out_channels, min_bytes=0):
-    images, rows = O.encode_packed(self._pic, batch, out_channels, n_threads=4)
-    if images.size < min_bytes:
-      images = np.concatenate([images, np.zeros(min_bytes - images.size, np.uint8)])
-    return images, rows
+from tests.oracle_adapter import OracleDeviceEncoder        # noqa: E402
 
 
 def product_examples(options, ref, candidates, reads_per_sample, sample_order, role, coverage):
