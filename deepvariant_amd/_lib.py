@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
+    'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
 ]
 
 
@@ -236,6 +237,24 @@ class DvAlleleEvent(C.Structure):
               ('length_type', C.c_uint32)]
 
 
+class DvGvcfSite(C.Structure):
+  # include/dvhip.h dv_gvcf_site: one entry of the reference-confidence table
+  _fields_ = [('likelihoods', C.c_double * 3), ('gq', C.c_int32), ('has_valid_gl', C.c_int32)]
+
+
+class DvGvcfOptions(C.Structure):
+  _fields_ = [('p_error', C.c_double), ('max_gq', C.c_int32), ('gq_resolution', C.c_int32),
+              ('max_cache_coverage', C.c_int32), ('include_med_dp', C.c_int32),
+              ('left_padding', C.c_int32), ('right_padding', C.c_int32),
+              ('table', C.c_void_p), ('n_table', C.c_int64)]
+
+
+class DvGvcfBlock(C.Structure):
+  _fields_ = [('start', C.c_int64), ('end', C.c_int64), ('likelihoods', C.c_double * 3),
+              ('gq', C.c_int32), ('min_dp', C.c_int32), ('med_dp', C.c_int32),
+              ('ref_base', C.c_uint8), ('has_valid_gl', C.c_uint8), ('reserved', C.c_uint8 * 2)]
+
+
 class DvModelDesc(C.Structure):
   _fields_ = [('height', C.c_int32), ('width', C.c_int32),
               ('channels', C.c_int32), ('num_classes', C.c_int32),
@@ -362,6 +381,11 @@ def lib():
     l.dv_allele_counts_arrays.argtypes = [C.c_void_p] + [C.c_void_p] * 4
     l.dv_allele_counts_free.argtypes = [C.c_void_p]
     l.dv_allele_counts_free.restype = None
+    l.dv_count_alleles_gvcf_batch.argtypes = [C.c_int32] + [C.c_void_p] * 7
+    l.dv_gvcf_blocks_arrays.restype = C.c_int64
+    l.dv_gvcf_blocks_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_gvcf_blocks_free.argtypes = [C.c_void_p]
+    l.dv_gvcf_blocks_free.restype = None
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

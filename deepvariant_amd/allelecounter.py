@@ -10,6 +10,9 @@ The reference adds reads one by one on the CPU; here `add` only queues them and 
 call that needs results packs the queue (packing.ReadTable) and counts the whole region in
 ONE kernel launch (deepvariant_amd/csrc/allele_counter.hip).  There is no CPU path.
 normalize_cigar restates AlleleCounter::NormalizeCigar (:777-845) for --normalize_reads.
+gvcf_blocks / run_batch(gvcf=...) add the reference's VariantCaller.make_gvcfs(summary_counts())
+(deepvariant/variant_caller.py), computed on the device from the same counts
+(deepvariant_amd/csrc/gvcf.hip); variant_calling.VariantCaller.make_gvcfs is its host restatement.
 """
 from __future__ import annotations
 
@@ -25,6 +28,9 @@ from deepvariant_amd import packing
 REFERENCE, SUBSTITUTION, INSERTION, DELETION, SOFT_CLIP = 1, 2, 3, 4, 5   # AlleleType
 _EVENT_DTYPE = np.dtype([('position', '<i4'), ('read', '<u4'), ('read_offset', '<u4'),
                          ('length_type', '<u4')])        # dv_allele_event: length | type << 28 | low quality << 31
+GVCF_BLOCK_DTYPE = np.dtype([('start', '<i8'), ('end', '<i8'), ('likelihoods', '<f8', (3,)), ('gq', '<i4'),
+                             ('min_dp', '<i4'), ('med_dp', '<i4'), ('ref_base', 'u1'), ('has_valid_gl', 'u1'),
+                             ('reserved', 'u1', (2,))])   # dv_gvcf_block
 
 
 class Allele:
@@ -88,6 +94,7 @@ class AlleleCounter:
     self._events = None
     self._event_ctx = None
     self._n_counted = 0
+    self._gvcf = None            # (GvcfOptions.key(), dv_gvcf_block records) of the last gVCF pass
 
   # ---- the reference's interface
   def interval_length(self) -> int:
@@ -100,14 +107,14 @@ class AlleleCounter:
     if self._table is not None:
       raise ValueError('reads were handed over as a packed table; add() cannot be mixed in')
     self._reads.append(read)
-    self._counts = self._alleles = self._events = None
+    self._counts = self._alleles = self._events = self._gvcf = None
 
   def add_table(self, table: packing.ReadTable):
     """All reads of the region at once, already packed (packing.ReadTable.from_bam / from_reads)."""
     if self._reads:
       raise ValueError('add() was used; add_table() cannot be mixed in')
     self._table = table
-    self._counts = self._alleles = self._events = None
+    self._counts = self._alleles = self._events = self._gvcf = None
 
   def _ensure(self):
     if self._events is None:
@@ -236,10 +243,16 @@ class AlleleCounter:
     self._take(handle, ctx)
 
   @staticmethod
-  def run_batch(counters: Sequence['AlleleCounter']) -> None:
+  def run_batch(counters: Sequence['AlleleCounter'], gvcf=None) -> None:
     """Counts for several counters (a batch of calling regions, each with its reads added) in ONE
     dv_count_alleles_batch call: one upload, kernels back to back, two synchronisations for the
-    whole batch.  Afterwards every counter answers as if it had counted alone."""
+    whole batch.  Afterwards every counter answers as if it had counted alone.  With `gvcf`
+    (variant_calling.GvcfOptions) the gVCF blocks of every counter are computed in the same device
+    pass (dv_count_alleles_gvcf_batch) and `gvcf_blocks(gvcf)` answers without another launch."""
+    if gvcf is not None:
+      AlleleCounter._run_gvcf_batch(
+          [c for c in counters if c._gvcf is None or c._gvcf[0] != gvcf.key()], gvcf)   # pylint: disable=protected-access
+      return
     todo = [c for c in counters if c._events is None]      # pylint: disable=protected-access
     if not todo:
       return
@@ -261,6 +274,67 @@ class AlleleCounter:
       for h in list(handles)[taken:]:                      # a failure part-way: the rest is not leaked
         if h:
           _lib.lib().dv_allele_counts_free(C.c_void_p(h))
+
+  @staticmethod
+  def _run_gvcf_batch(todo: Sequence['AlleleCounter'], gvcf) -> None:
+    if not todo:
+      return
+    requests = [c._request() for c in todo]                # pylint: disable=protected-access
+    n = len(todo)
+    keys = []
+    for r in requests:
+      names = r[3][0].keys
+      # read_alleles is keyed by read key: reads that share one (supplementary alignments) are one key
+      keys.append(np.ascontiguousarray(np.unique(np.array(names), return_inverse=True)[1].astype(np.int32))
+                  if len(set(names)) != len(names) else None)
+    table = gvcf.table()
+    opt = _lib.DvGvcfOptions(gvcf.p_error, gvcf.max_gq, gvcf.gq_resolution, gvcf.max_cache_coverage,
+                             int(gvcf.include_med_dp), gvcf.left_padding, gvcf.right_padding,
+                             table.ctypes.data, len(table))
+    batches = (C.c_void_p * n)(*[C.addressof(r[0]) for r in requests])
+    options = (C.c_void_p * n)(*[C.addressof(r[1]) for r in requests])
+    key_ptrs = (C.c_void_p * n)(*[k.ctypes.data if k is not None else None for k in keys])
+    handles = (C.c_void_p * n)()
+    blocks = (C.c_void_p * n)()
+    lib = _lib.lib()
+    _lib.check(lib.dv_count_alleles_gvcf_batch(n, batches, options, key_ptrs, C.byref(opt), handles, blocks, None))
+    taken = 0
+    try:
+      for c, r, h, b in zip(todo, requests, handles, blocks):
+        taken += 1                                         # both handles are freed below, also on an error
+        try:
+          records = C.POINTER(_lib.DvGvcfBlock)()
+          nb = int(lib.dv_gvcf_blocks_arrays(C.c_void_p(b), C.byref(records)))
+          # string_at: one copy, ~100x cheaper per call than np.ctypeslib.as_array on a pointer
+          arr = (np.frombuffer(C.string_at(records, nb * GVCF_BLOCK_DTYPE.itemsize), GVCF_BLOCK_DTYPE)
+                 if nb else np.zeros(0, GVCF_BLOCK_DTYPE))
+        finally:
+          lib.dv_gvcf_blocks_free(C.c_void_p(b))
+        c._take(C.c_void_p(h), r[3])                       # pylint: disable=protected-access
+        c._gvcf = (gvcf.key(), arr)                        # pylint: disable=protected-access
+    finally:
+      for h, b in list(zip(handles, blocks))[taken:]:
+        if h:
+          lib.dv_allele_counts_free(C.c_void_p(h))
+        if b:
+          lib.dv_gvcf_blocks_free(C.c_void_p(b))
+
+  def gvcf_block_array(self, gvcf) -> np.ndarray:
+    """The device's gVCF records of this counter (GVCF_BLOCK_DTYPE; MED_DP -1 unless asked for),
+    computed now unless run_batch(gvcf=...) already did with these options."""
+    if self._gvcf is None or self._gvcf[0] != gvcf.key():
+      AlleleCounter._run_gvcf_batch([self], gvcf)
+    return self._gvcf[1]
+
+  def gvcf_blocks(self, gvcf) -> List[T.Variant]:
+    """VariantCaller.make_gvcfs(self.summary_counts(left_padding, right_padding), include_med_dp)
+    from the device: one Variant per reference block (variant_calling.gvcf_record)."""
+    from deepvariant_amd import variant_calling          # pylint: disable=g-import-not-at-top (import cycle)
+    return [variant_calling.gvcf_record(self._contig, b['start'], b['end'], chr(b['ref_base']),
+                                        b['likelihoods'].tolist(), b['gq'], b['min_dp'],
+                                        int(b['med_dp']) if gvcf.include_med_dp else None,
+                                        bool(b['has_valid_gl']), gvcf.sample_name)
+            for b in self.gvcf_block_array(gvcf)]
 
   def _build_alleles(self):
     if self._alleles is not None:

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "dv_internal.h"
+#include "gvcf.h"
 
 // Large results live in pinned host memory (the count array of a 7.7 Mb interval is 31 MB: 1.3 ms
 // over PCIe from pinned memory, 5 ms into pageable); small ones -- a 1 kb calling region's 4 KB of
@@ -434,6 +435,81 @@ int check_request(const dv_batch* b, const dv_allele_counter_options* o, dv_alle
   return DV_OK;
 }
 
+// The gVCF pass over counts that are already on the host (a region that took the one-region path:
+// a device-resident read table, no reads, or events beyond the batch's first guess): the counts go
+// back up and through the same kernels.  One synchronisation; the rare path.
+int gvcf_from_counts(const dv_allele_counts* c, const dv_allele_counter_options* o, const dv_batch* b,
+                     const int32_t* keys, const dv_gvcf_options* gv, const dv_gvcf_site* d_table, hipStream_t stream,
+                     dv_gvcf_blocks** out) {
+  static thread_local dv::DeviceBuffer d_img;
+  auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
+  const int64_t len = c->length;
+  const uint32_t n_ev = static_cast<uint32_t>(c->events.size());
+  const size_t n_keys = keys ? static_cast<size_t>(b->n_reads) : 0;
+  // image: descriptor | n_events, n_blocks | ref_count | events | ref | keys | scratch | blocks
+  size_t at = 0;
+  const size_t o_desc = at;
+  at += align16(sizeof(dv::GvcfRegion));
+  const size_t o_words = at;
+  at += 16;
+  const size_t o_cnt = at;
+  at += align16(static_cast<size_t>(len) * 4);
+  const size_t o_ev = at;
+  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
+  const size_t o_ref = at;
+  at += align16(static_cast<size_t>(len));
+  const size_t o_keys = at;
+  at += align16(n_keys * 4);
+  const size_t up_bytes = at;
+  const size_t o_scr = at;
+  at += align16(dv::gvcf_scratch_ints(len, n_ev) * 4);
+  const size_t o_blk = at;
+  const int64_t n_sites = len - gv->left_padding - gv->right_padding;
+  at += static_cast<size_t>(n_sites) * sizeof(dv_gvcf_block);
+  if (int rc = d_img.reserve_on_current_device(at)) return rc;
+  uint8_t* dev = static_cast<uint8_t*>(d_img.ptr);
+  std::vector<uint8_t> img(up_bytes, 0);
+  dv::GvcfRegion g{};
+  g.ref_count = reinterpret_cast<const int32_t*>(dev + o_cnt);
+  g.events = reinterpret_cast<const dv_allele_event*>(dev + o_ev);
+  g.n_events = reinterpret_cast<const uint32_t*>(dev + o_words);
+  g.event_cap = n_ev;
+  g.read_key = keys ? reinterpret_cast<const int32_t*>(dev + o_keys) : nullptr;
+  g.ref = dev + o_ref;
+  g.interval_start = o->interval_start;
+  g.len = static_cast<int32_t>(len);
+  g.lo = gv->left_padding;
+  g.hi = static_cast<int32_t>(len - gv->right_padding);
+  g.scratch = reinterpret_cast<int32_t*>(dev + o_scr);
+  g.blocks = reinterpret_cast<dv_gvcf_block*>(dev + o_blk);
+  g.n_blocks = reinterpret_cast<int32_t*>(dev + o_words + 4);
+  std::memcpy(img.data() + o_desc, &g, sizeof(g));
+  std::memcpy(img.data() + o_words, &n_ev, 4);
+  const int32_t* cnt = c->ref_count.ptr ? c->ref_count.ptr : c->empty_counts.data();
+  if (len) std::memcpy(img.data() + o_cnt, cnt, static_cast<size_t>(len) * 4);
+  if (n_ev) std::memcpy(img.data() + o_ev, c->events.data(), static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
+  std::memcpy(img.data() + o_ref, o->ref_bases + (o->interval_start - o->ref_start), static_cast<size_t>(len));
+  if (n_keys) std::memcpy(img.data() + o_keys, keys, n_keys * 4);
+  DV_HIP_CHECK(hipMemcpyAsync(dev, img.data(), up_bytes, hipMemcpyHostToDevice, stream));
+  DV_HIP_CHECK(hipMemsetAsync(dev + o_scr, 0, o_blk - o_scr, stream));
+  if (int rc = dv::gvcf_launch(reinterpret_cast<const dv::GvcfRegion*>(dev + o_desc), 1, len, n_ev, gv, d_table, nullptr,
+                               stream)) {
+    return rc;
+  }
+  int32_t n_blocks = 0;
+  DV_HIP_CHECK(hipMemcpyAsync(&n_blocks, dev + o_words + 4, 4, hipMemcpyDeviceToHost, stream));
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  auto res = std::make_unique<dv_gvcf_blocks>();
+  res->blocks.resize(static_cast<size_t>(n_blocks));
+  if (n_blocks) {
+    DV_HIP_CHECK(hipMemcpyAsync(res->blocks.data(), dev + o_blk, static_cast<size_t>(n_blocks) * sizeof(dv_gvcf_block),
+                                hipMemcpyDeviceToHost, stream));
+    DV_HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  *out = res.release();
+  return DV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -546,24 +622,43 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
 // back to back, and the stream is synchronised twice for the whole batch.  Results per region are
 // those of dv_count_alleles (the same kernel on the same arguments).  Regions whose tables are
 // device-resident, and the rare region whose events overflow the first guess, take the one-region path.
-int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
-                           dv_allele_counts** out, void* stream_v) {
-  if (n < 0 || (n > 0 && (!reads || !options || !out))) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles_batch: null");
+// dv_count_alleles_batch, and with `gv` set dv_count_alleles_gvcf_batch: the gVCF pass (gvcf.hip) is queued
+// behind the counting kernels and its records come back with the events.  Without `gv` nothing differs.
+static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                       const int32_t* const* read_keys, const dv_gvcf_options* gv, dv_allele_counts** out,
+                       dv_gvcf_blocks** gout, void* stream_v, const char* who) {
+  const std::string name(who);
+  if (n < 0 || (n > 0 && (!reads || !options || !out || (gv && !gout)))) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
   for (int32_t k = 0; k < n; ++k) out[k] = nullptr;
+  if (gv) {
+    for (int32_t k = 0; k < n; ++k) gout[k] = nullptr;
+  }
   auto fail_all = [&](int rc) {
     for (int32_t k = 0; k < n; ++k) {
       delete out[k];
       out[k] = nullptr;
+      if (gv) {
+        delete gout[k];
+        gout[k] = nullptr;
+      }
     }
     return rc;
   };
+  if (gv) {
+    if (int rc = dv::gvcf_check_options(gv, who)) return rc;
+  }
   for (int32_t k = 0; k < n; ++k) {
-    if (int rc = check_request(reads[k], options[k], &out[k], "dv_count_alleles_batch")) return rc;
+    if (gv) {   // before check_request: bad input is reported as such with or without a device
+      if (int rc = dv::gvcf_check_region(options[k], gv, who)) return rc;
+    }
+    if (int rc = check_request(reads[k], options[k], &out[k], who)) return rc;
     if (options[k]->track_ref_reads && options[k]->n_candidate_positions > 0 && !options[k]->candidate_positions) {
-      return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles_batch: candidate_positions is null");
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": candidate_positions is null");
     }
   }
+  auto keys_of = [&](int32_t k) -> const int32_t* { return read_keys ? read_keys[k] : nullptr; };
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const dv_gvcf_site* d_table = nullptr;
   // Everything from here on may have results in out[]: the body runs as one callable so that EVERY error exit
   // -- the DV_HIP_CHECK returns included -- passes through fail_all ("on an error no result is left allocated").
   auto body = [&]() -> int {
@@ -574,11 +669,17 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
     int64_t len = 0;
     uint32_t cap = 0;
     size_t mask_words = 0;
+    size_t key_up = 0, scr_off = 0, blk_off = 0;  // gVCF: staging offset of the read keys, scratch ints, records
+    int gv_slot = -1;                             // gVCF: index among the batched regions
   };
   std::vector<Plan> plan(static_cast<size_t>(n));
   auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   size_t up_bytes = 0, cnt_ints = 0, ev_total = 0;
   int n_batched = 0;
+  int n_gv = 0;                                  // gVCF: batched regions, their scratch and record totals
+  size_t scr_ints = 0, blk_total = 0;
+  int64_t max_len = 0;
+  uint32_t max_cap = 0;
   for (int32_t k = 0; k < n; ++k) {
     const dv_batch* b = reads[k];
     const dv_allele_counter_options* o = options[k];
@@ -606,17 +707,42 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
     p.cap = b->n_cigar + b->n_bases / 16 + 4096 + static_cast<uint32_t>(std::min<size_t>(n_candidate_refs * 64, 1u << 24));
     p.ev_off = ev_total;
     ev_total += p.cap;
+    if (gv) {
+      if (keys_of(k)) {
+        p.key_up = up_bytes;
+        up_bytes += align16(nr * 4);
+      }
+      p.gv_slot = n_gv;
+      ++n_gv;
+      p.scr_off = scr_ints;
+      scr_ints += dv::gvcf_scratch_ints(p.len, p.cap);
+      p.blk_off = blk_total;
+      blk_total += static_cast<size_t>(p.len - gv->left_padding - gv->right_padding);
+      max_len = std::max(max_len, p.len);
+      max_cap = std::max(max_cap, p.cap);
+    }
   }
+  // gVCF: the batched regions' descriptors travel at the end of the staging image
+  const size_t desc_up = up_bytes;
+  if (n_gv) up_bytes += align16(static_cast<size_t>(n_gv) * sizeof(dv::GvcfRegion));
   if (n_batched > 0) {
     // grow-only scratch per host thread: pinned staging both ways, device images
     static thread_local PinnedBytes h_up, h_down;
     static thread_local dv::DeviceBuffer d_up, d_res, d_ev;
+    static thread_local dv::DeviceBuffer d_gscr, d_gblk, d_gpack;
     const size_t ctr_bytes = align16(static_cast<size_t>(n) * 4 * sizeof(uint32_t));
-    const size_t res_bytes = ctr_bytes + cnt_ints * sizeof(int32_t);
+    // gVCF: each region's record count follows the counts (and comes back with them)
+    const size_t nblk_off = align16(ctr_bytes + cnt_ints * sizeof(int32_t));
+    const size_t res_bytes = gv ? nblk_off + static_cast<size_t>(n) * sizeof(int32_t) : ctr_bytes + cnt_ints * sizeof(int32_t);
     if (int rc = h_up.reserve(up_bytes)) return rc;
     if (int rc = d_up.reserve_on_current_device(up_bytes)) return rc;
     if (int rc = d_res.reserve_on_current_device(res_bytes)) return rc;
     if (int rc = d_ev.reserve_on_current_device(std::max<size_t>(ev_total, 1) * sizeof(dv_allele_event))) return rc;
+    if (n_gv) {
+      if (int rc = d_gscr.reserve_on_current_device(scr_ints * sizeof(int32_t))) return rc;
+      if (int rc = d_gblk.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
+      if (int rc = d_gpack.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
+    }
     for (int32_t k = 0; k < n; ++k) {
       const Plan& p = plan[k];
       if (!p.batched) continue;
@@ -640,9 +766,34 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
           if (q >= 0 && q < p.len) mask[static_cast<size_t>(q >> 5)] |= 1u << (q & 31);
         }
       }
+      if (p.gv_slot >= 0) {
+        // the descriptor points into the device images: the counts, events and reference the counter uses
+        const uint8_t* dup0 = static_cast<const uint8_t*>(d_up.ptr);
+        uint8_t* dres0 = static_cast<uint8_t*>(d_res.ptr);
+        if (keys_of(k)) std::memcpy(base + p.key_up, keys_of(k), nr * 4);
+        dv::GvcfRegion g{};
+        g.ref_count = reinterpret_cast<const int32_t*>(dres0 + ctr_bytes) + p.cnt_off;
+        g.events = static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off;
+        g.n_events = reinterpret_cast<const uint32_t*>(dres0) + static_cast<size_t>(k) * 4;
+        g.event_cap = p.cap;
+        g.read_key = keys_of(k) ? reinterpret_cast<const int32_t*>(dup0 + p.key_up) : nullptr;
+        g.ref = dup0 + p.up[7] + (o->interval_start - o->ref_start);
+        g.interval_start = o->interval_start;
+        g.len = static_cast<int32_t>(p.len);
+        g.lo = gv->left_padding;
+        g.hi = static_cast<int32_t>(p.len - gv->right_padding);
+        g.scratch = static_cast<int32_t*>(d_gscr.ptr) + p.scr_off;
+        g.blocks = static_cast<dv_gvcf_block*>(d_gblk.ptr) + p.blk_off;
+        g.n_blocks = reinterpret_cast<int32_t*>(dres0 + nblk_off) + k;
+        std::memcpy(base + desc_up + static_cast<size_t>(p.gv_slot) * sizeof(dv::GvcfRegion), &g, sizeof(g));
+      }
     }
     DV_HIP_CHECK(hipMemcpyAsync(d_up.ptr, h_up.ptr, up_bytes, hipMemcpyHostToDevice, stream));
     DV_HIP_CHECK(hipMemsetAsync(d_res.ptr, 0, res_bytes, stream));
+    if (n_gv) {
+      DV_HIP_CHECK(hipMemsetAsync(d_gscr.ptr, 0, scr_ints * sizeof(int32_t), stream));
+      if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
+    }
     uint8_t* dres = static_cast<uint8_t*>(d_res.ptr);
     const uint8_t* dup = static_cast<const uint8_t*>(d_up.ptr);
     for (int32_t k = 0; k < n; ++k) {
@@ -680,6 +831,13 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
                          dim3(256), 0, stream, a);
     }
     DV_HIP_CHECK(hipGetLastError());
+    if (n_gv) {
+      // the reference-confidence pass reads the counts where the kernels above leave them
+      if (int rc = dv::gvcf_launch(reinterpret_cast<const dv::GvcfRegion*>(dup + desc_up), n_gv, max_len, max_cap, gv,
+                                   d_table, static_cast<dv_gvcf_block*>(d_gpack.ptr), stream)) {
+        return rc;
+      }
+    }
     // counters and counts come back together; the events follow once their numbers are known
     if (int rc = h_down.reserve(res_bytes)) return rc;
     DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, res_bytes, hipMemcpyDeviceToHost, stream));
@@ -707,8 +865,22 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
       if (int rc = res->raw.reserve(ctr[0])) return fail_all(rc);
       out[k] = res.release();
       ev_bytes += static_cast<size_t>(ctr[0]) * sizeof(dv_allele_event);
+      if (gv) {
+        gout[k] = new dv_gvcf_blocks();
+        gout[k]->blocks.resize(static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]));
+      }
     }
-    // the events of every region into one pinned image, one synchronisation
+    // gVCF: every batched region's records lie packed in region order (gvcf_pack_kernel), the overflowed
+    // regions' included: they come back in one copy behind the events
+    size_t packed_blocks = 0;
+    if (gv) {
+      for (int32_t k = 0; k < n; ++k) {
+        if (plan[k].gv_slot >= 0) packed_blocks += static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]);
+      }
+    }
+    const size_t packed_at = ev_bytes;
+    ev_bytes += packed_blocks * sizeof(dv_gvcf_block);
+    // the events (and gVCF records) of every region into one pinned image, one synchronisation
     static thread_local PinnedBytes h_ev;
     if (int rc = h_ev.reserve(ev_bytes)) return fail_all(rc);
     size_t at = 0;
@@ -722,6 +894,10 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
       }
       at += bytes;
     }
+    if (packed_blocks) {
+      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + packed_at, d_gpack.ptr, packed_blocks * sizeof(dv_gvcf_block),
+                                  hipMemcpyDeviceToHost, stream));
+    }
     DV_HIP_CHECK(hipStreamSynchronize(stream));
     at = 0;
     for (int32_t k = 0; k < n; ++k) {
@@ -732,16 +908,50 @@ int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_all
       at += n_ev * sizeof(dv_allele_event);
       order_events(out[k], n_ev);
     }
+    at = packed_at;
+    for (int32_t k = 0; k < n; ++k) {
+      if (plan[k].gv_slot < 0) continue;
+      const size_t gbytes = static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]) *
+                            sizeof(dv_gvcf_block);
+      if (plan[k].batched && out[k] && gbytes) std::memcpy(gout[k]->blocks.data(), h_ev.ptr + at, gbytes);
+      at += gbytes;
+    }
   }
   for (int32_t k = 0; k < n; ++k) {
     if (out[k]) continue;
     if (int rc = dv_count_alleles(reads[k], options[k], &out[k], stream_v)) return rc;
+    if (gv) {
+      if (!d_table) {
+        if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
+      }
+      if (int rc = gvcf_from_counts(out[k], options[k], reads[k], keys_of(k), gv, d_table, stream, &gout[k])) return rc;
+    }
   }
   return DV_OK;
   };
   const int rc = body();
   return rc == DV_OK ? DV_OK : fail_all(rc);
 }
+
+int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                           dv_allele_counts** out, void* stream_v) {
+  return count_batch(n, reads, options, nullptr, nullptr, out, nullptr, stream_v, "dv_count_alleles_batch");
+}
+
+int dv_count_alleles_gvcf_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                                const int32_t* const* read_keys, const dv_gvcf_options* gvcf,
+                                dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out, void* stream) {
+  if (!gvcf) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles_gvcf_batch: gvcf options are null");
+  return count_batch(n, reads, options, read_keys, gvcf, counts_out, blocks_out, stream, "dv_count_alleles_gvcf_batch");
+}
+
+int64_t dv_gvcf_blocks_arrays(const dv_gvcf_blocks* b, const dv_gvcf_block** blocks) {
+  if (!b) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_gvcf_blocks_arrays: null");
+  if (blocks) *blocks = b->blocks.data();
+  return static_cast<int64_t>(b->blocks.size());
+}
+
+void dv_gvcf_blocks_free(dv_gvcf_blocks* b) { delete b; }
 
 int dv_allele_counts_arrays(const dv_allele_counts* c, const int32_t** ref_supporting_read_count,
                             const dv_allele_event** events, uint32_t* n_events, int32_t* n_reads_counted) {

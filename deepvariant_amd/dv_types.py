@@ -194,6 +194,7 @@ class VariantCall:
   call_set_name: str = ''
   genotype: List[int] = field(default_factory=list)
   info: Dict[str, ListValue] = field(default_factory=dict)
+  genotype_likelihood: List[float] = field(default_factory=list)   # variants.proto field 6 (gVCF records)
 
 
 @dataclass

@@ -5,16 +5,18 @@ deepvariant/make_examples_core.py's RegionProcessor that joins the hot path's st
   RegionProcessor.realign_reads          make_examples_core.py:2479-2518
   RegionProcessor.candidates_in_region   make_examples_core.py:2840-3165 (one sample; incl. the
                                          two-pass track_ref_reads counting and read phasing with
-                                         region padding; no gVCF, no normalize_reads, no
-                                         methylation-aware phasing)
+                                         region padding; gVCF blocks from the device allele counts;
+                                         no normalize_reads, no methylation-aware phasing)
   RegionProcessor.process                make_examples_core.py:2215-2380
   partition                              ranges.RangeSet.partition (1000-base calling regions)
 
 Every stage below is this package's own: realigner/ (device allele counts for window
 selection, native assembly and alignment), allelecounter.AlleleCounter (device),
 variant_calling.VariantCaller (host), direct_phasing.DirectPhasing (native, host),
-make_examples_native.ExamplesGenerator (device encoder, optionally fused with the CNN).  File
-handling, sharding, labelling, gVCF and multi-sample plumbing of the reference's make_examples are
+make_examples_native.ExamplesGenerator (device encoder, optionally fused with the CNN).  With
+RegionProcessorOptions.gvcf the regions' gVCF reference blocks come out of the same allele-count
+pass (RegionProcessor.gvcf_records; GvcfShardWriter writes them as the reference's gVCF TFRecords).
+File handling, sharding, labelling and multi-sample plumbing of the reference's make_examples are
 outside SURVEY.md section 8.
 """
 from __future__ import annotations
@@ -28,6 +30,9 @@ from deepvariant_amd import direct_phasing
 from deepvariant_amd import dv_types as T
 from deepvariant_amd import make_examples_native
 from deepvariant_amd import packing
+from deepvariant_amd import sharded_file_utils
+from deepvariant_amd import tfrecord
+from deepvariant_amd import protowire
 from deepvariant_amd import variant_calling
 from deepvariant_amd.realigner import realigner as realigner_module
 from deepvariant_amd.realigner import utils
@@ -52,10 +57,44 @@ class RegionProcessorOptions:
   phase_reads_region_padding_pct: int = 20        # dv_constants.PHASE_READS_REGION_PADDING_PCT
   phase_max_candidates: int = 5000
   min_alleles_to_phase: int = 1
+  # --gvcf (make_examples_options.py): reference-confidence blocks of every region, from the allele counts
+  gvcf: bool = False
+  gvcf_gq_binsize: int = 5
+  include_med_dp: bool = False
 
 
 END_OF_REGION = -1        # make_examples_core.py:125-129: markers in a candidate-positions file
 END_OF_PARTITION = -2
+
+
+class GvcfShardWriter:
+  """The gVCF output of one task: serialized nucleus Variant records in a TFRecord file, sharded and
+  named as the examples are ('gvcf.tfrecord@N.gz' + task -> 'gvcf.tfrecord-0000t-of-0000N.gz';
+  GZIP when the name ends in .gz, tfrecord.Writer's rule).  `with GvcfShardWriter(spec, task) as w:
+  w.write_all(records)`."""
+
+  def __init__(self, spec: str, task: int = 0):
+    n_shards, self.path = sharded_file_utils.resolve_filespecs(task, spec)
+    self.n_shards = n_shards
+    self._writer = tfrecord.Writer(self.path)
+    self.n_written = 0
+
+  def write(self, variant: T.Variant):
+    self._writer.write(protowire.encode_variant(variant))
+    self.n_written += 1
+
+  def write_all(self, variants: Iterable[T.Variant]):
+    for v in variants:
+      self.write(v)
+
+  def close(self):
+    self._writer.close()
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *args):
+    self.close()
 
 
 def partition(region: T.Range, size: int) -> Iterator[T.Range]:
@@ -205,7 +244,10 @@ class RegionProcessor:
     sample = options.sample_options[0]
     self.variant_caller = variant_calling.VariantCaller(variant_calling.VariantCallerOptions(
         po.vsc_min_count_snps, po.vsc_min_count_indels, po.vsc_min_fraction_snps, po.vsc_min_fraction_indels,
-        sample_name=sample.name, track_ref_reads=po.track_ref_reads))
+        sample_name=sample.name, track_ref_reads=po.track_ref_reads, gq_resolution=po.gvcf_gq_binsize))
+    # with po.gvcf: the gVCF records of the regions of the last process / process_table(s) call, one list
+    # per region in call order (empty for a region without reads, as in the reference)
+    self.gvcf_records: List[List[T.Variant]] = []
     self._queue: List = []
     self.n_queued_examples = 0
     self.generator = make_examples_native.ExamplesGenerator(
@@ -241,6 +283,7 @@ class RegionProcessor:
     phase_reads -- the phasing of those reads (their HP tags are REPLACED in place)."""
     po = self.processor_options
     in_region = [r for r in reads if utils.ranges_overlap(utils.read_range(r), region)]
+    self.gvcf_records = [[]] if po.gvcf else []
     if not in_region:
       return []
     effective = padded_region or region
@@ -249,7 +292,13 @@ class RegionProcessor:
     if po.track_ref_reads:
       first_pass = self._allele_counter(effective, table)
       positions = self.variant_caller.call_positions_from_allele_counter(first_pass)
-    candidates = self.variant_caller.calls_from_allele_counter(self._allele_counter(effective, table, positions))
+    counter = self._allele_counter(effective, table, positions)
+    if po.gvcf:
+      # summary_counts(left_padding, right_padding): the padding of a padded region is not reported
+      opts = self._gvcf_options(region.start - effective.start, effective.end - region.end)
+      allelecounter.AlleleCounter.run_batch([counter], gvcf=opts)
+      self.gvcf_records = [counter.gvcf_blocks(opts)]
+    candidates = self.variant_caller.calls_from_allele_counter(counter)
     if self.direct_phasing is not None:
       to_phase = [r for r in in_region if utils.ranges_overlap(utils.read_range(r), effective)]
       for read in to_phase:
@@ -262,6 +311,11 @@ class RegionProcessor:
     if padded_region is not None:                 # filter_candidates_by_region, :2579-2606
       candidates = [c for c in candidates if region.start <= c.variant.start < region.end]
     return candidates
+
+  def _gvcf_options(self, left_padding: int = 0, right_padding: int = 0) -> 'variant_calling.GvcfOptions':
+    caller_options = self.variant_caller._options          # pylint: disable=protected-access
+    return variant_calling.GvcfOptions.from_caller_options(caller_options, self.processor_options.include_med_dp,
+                                                           left_padding, right_padding)
 
   def find_candidate_positions(self, region: T.Range, reads: Sequence) -> List[int]:
     """candidate_sweep mode (make_examples_core.py:2117-2189): the positions at which the RAW reads
@@ -365,7 +419,15 @@ class RegionProcessor:
       run_batch(first_pass)
       positions = [self.variant_caller.call_positions_from_allele_counter(c) for c in first_pass]
     counters = [self._allele_counter(regions[k], t, p) for k, t, p in zip(slots, in_region, positions)]
-    run_batch(counters)
+    if self.processor_options.gvcf:
+      # the same counts, with the regions' gVCF blocks computed behind them on the device
+      opts = self._gvcf_options()
+      allelecounter.AlleleCounter.run_batch(counters, gvcf=opts)
+      self.gvcf_records = [[] for _ in regions]
+      for k, counter in zip(slots, counters):
+        self.gvcf_records[k] = counter.gvcf_blocks(opts)
+    else:
+      run_batch(counters)
     for k, counter in zip(slots, counters):
       out[k] = (self.variant_caller.calls_from_allele_counter(counter), realigned_tables[k])
     return out

@@ -215,6 +215,12 @@ def decode_variant(buf) -> T.Variant:
             call.info[key] = lv
         elif f2 == 9:
           call.call_set_name = bytes(v2).decode()
+        elif f2 == 6:                                 # genotype_likelihood: repeated double, packed or not
+          if wt2 == LEN:
+            raw = bytes(v2)
+            call.genotype_likelihood.extend(struct.unpack('<%dd' % (len(raw) // 8), raw))
+          else:
+            call.genotype_likelihood.append(struct.unpack('<d', bytes(v2))[0])
         elif f2 == 7:
           if wt2 == LEN:
             p = 0
@@ -252,6 +258,8 @@ def encode_variant(v: T.Variant) -> bytes:
           one = enc_len(3, (val.string_value or '').encode())     # Value.string_value
         values += enc_len(1, one)
       body += enc_len(2, enc_len(1, key.encode()) + enc_len(2, values))
+    if c.genotype_likelihood:
+      body += enc_len(6, struct.pack('<%dd' % len(c.genotype_likelihood), *c.genotype_likelihood))
     if c.genotype:
       body += enc_len(7, b''.join(enc_varint(g) for g in c.genotype))
     if c.call_set_name:

@@ -14,12 +14,24 @@ support channel is computed from -- the candidates of make_examples' "calling" m
 sample.  With one sample, no complex-allele creation and no methylation-aware options the
 multi-sample caller the reference runs in production (variant_calling_multisample.cc) reduces
 to exactly these rules (AlleleFilter :264-311 falls back to IsGoodAltAllele when there is no
-other sample).  Not restated: multi-sample filtering, complex alleles, gVCF / reference-site
+other sample).  Not restated: multi-sample filtering, complex alleles, reference-site
 sampling (fraction_reference_sites_to_emit), methylation statistics, CallsFromVcf.
+
+gVCF reference confidence (deepvariant/variant_caller.py VariantCaller.reference_confidence /
+make_gvcfs with nucleus genomics_math.normalize_log10_probs / log10_ptrue_to_phred):
+`site_reference_confidence` is the one restatement of the per-site model; `reference_confidence_table`
+tabulates it for the device pass (allelecounter.AlleleCounter.gvcf_blocks) and `make_gvcfs` merges
+sites into blocks on the host -- the checker, and the route for callers that hold Python counts.
+Which points of it rest on memory rather than the reference's source: DESIGN.md section 9.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+import functools
+import math
+import statistics
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 from deepvariant_amd import allelecounter as ac
 from deepvariant_amd import dv_types as T
@@ -27,16 +39,125 @@ from deepvariant_amd import dv_types as T
 K_SUPPORTING_UNCALLED_ALLELE = 'UNCALLED_ALLELE'
 K_NO_ALT_ALLELE = '.'
 _CANONICAL = frozenset('ACGT')
+# reference bases that are IUPAC codes but not A/C/G/T: their sites get no gVCF record
+_IUPAC_NON_CANONICAL = frozenset('NRYKMSWBDHV')
+GVCF_ALT_ALLELE = '<*>'                   # vcf_constants.GVCF_ALT_ALLELE
+GVCF_SITE_DTYPE = np.dtype([('likelihoods', '<f8', (3,)), ('gq', '<i4'), ('has_valid_gl', '<i4')])   # dv_gvcf_site
+
+
+def site_reference_confidence(n_ref: int, n_total: int, p_error: float,
+                              max_gq: int) -> Tuple[int, Tuple[float, float, float]]:
+  """VariantCaller._calc_reference_confidence for ploidy 2: -> (raw GQ, normalised log10 likelihoods of
+  hom-ref, het, hom-alt).  The whole per-site model is here; everything else (the table, the device
+  pass, make_gvcfs) reads it."""
+  if n_ref < 0 or n_total < n_ref:
+    raise ValueError('Invalid read counts: n_ref=%d n_total=%d' % (n_ref, n_total))
+  n_alt = n_total - n_ref
+  logp = math.log10(p_error)
+  log1p = math.log10(1 - p_error)
+  raw = (n_ref * log1p + n_alt * logp, -n_total * math.log10(2), n_ref * logp + n_alt * log1p)
+  # genomics_math.normalize_log10_probs: minus log10-sum-exp (max-shifted), clipped at 0
+  m = max(raw)
+  lse = m + math.log10(sum(math.pow(10.0, x - m) for x in raw))
+  lp = tuple(min(x - lse, 0.0) for x in raw)
+  # genomics_math.log10_ptrue_to_phred(lp[0], max_gq): the cap when 1 - 10^lp[0] is 0
+  ptrue = math.pow(10.0, lp[0])
+  phred = max_gq if ptrue == 1 else -10.0 * math.log10(1.0 - ptrue)
+  return int(min(math.floor(phred), max_gq)), lp
+
+
+@functools.lru_cache(maxsize=8)
+def reference_confidence_table(p_error: float, max_gq: int, max_cache_coverage: int) -> np.ndarray:
+  """The cache of the reference's VariantCaller over 0 <= n_ref <= n_total <= M, as the dv_gvcf_site
+  array the device reads: entry n_total * (n_total + 1) // 2 + n_ref.  Computed once per argument set;
+  callers must not modify it."""
+  m = int(max_cache_coverage)
+  table = np.zeros((m + 1) * (m + 2) // 2, GVCF_SITE_DTYPE)
+  for t in range(m + 1):
+    for r in range(t + 1):
+      gq, lp = site_reference_confidence(r, t, p_error, max_gq)
+      e = table[t * (t + 1) // 2 + r]
+      e['likelihoods'] = lp
+      e['gq'] = gq
+      e['has_valid_gl'] = int(max(lp) == lp[0])
+  return table
+
+
+def rescale_read_counts_if_necessary(n_ref: int, n_total: int, max_allowed_reads: int) -> Tuple[int, int]:
+  """_rescale_read_counts_if_necessary: deeper sites are scaled down to max_allowed_reads."""
+  if n_total > max_allowed_reads:
+    ratio = n_ref / (1.0 * n_total)
+    n_ref = int(math.ceil(ratio * max_allowed_reads))
+    n_total = max_allowed_reads
+  return n_ref, n_total
+
+
+def quantize_gq(raw_gq: int, binsize: int) -> int:
+  """_quantize_gq: 0, or the lower edge (1, 1 + binsize, ...) of raw_gq's bin."""
+  if raw_gq < 1:
+    return 0
+  return ((raw_gq - 1) // binsize) * binsize + 1
+
+
+def gvcf_record(reference_name: str, start: int, end: int, ref_base: str, likelihoods, gq: int, min_dp: int,
+                med_dp: Optional[int], has_valid_gl: bool, sample_name: str) -> T.Variant:
+  """One reference block as make_gvcfs yields it (host and device routes build it here)."""
+  call = T.VariantCall(call_set_name=sample_name, genotype=[0, 0] if has_valid_gl else [-1, -1],
+                       genotype_likelihood=[float(x) for x in likelihoods])
+  call.info['GQ'] = T.ListValue(values=[T.Value(int_value=int(gq))])
+  call.info['MIN_DP'] = T.ListValue(values=[T.Value(int_value=int(min_dp))])
+  if med_dp is not None:
+    call.info['MED_DP'] = T.ListValue(values=[T.Value(int_value=int(med_dp))])
+  return T.Variant(reference_name=reference_name, start=int(start), end=int(end), reference_bases=ref_base,
+                   alternate_bases=[GVCF_ALT_ALLELE], calls=[call])
+
+
+def _summary_fields(s):
+  """AlleleCountSummary-like object or AlleleCounter.summary_counts tuple -> its five fields."""
+  if isinstance(s, tuple):
+    return s
+  return (s.reference_name, s.position, s.ref_base, s.ref_supporting_read_count, s.total_read_count)
 
 
 class VariantCallerOptions:
   def __init__(self, min_count_snps=0, min_count_indels=0, min_fraction_snps=0.0, min_fraction_indels=0.0,
-               sample_name='', fraction_reference_sites_to_emit=0.0, track_ref_reads=False):
+               sample_name='', fraction_reference_sites_to_emit=0.0, track_ref_reads=False,
+               p_error=0.001, max_gq=50, gq_resolution=5, ploidy=2, max_cache_coverage=100):
     self.min_count_snps, self.min_count_indels = min_count_snps, min_count_indels
     self.min_fraction_snps, self.min_fraction_indels = min_fraction_snps, min_fraction_indels
     self.sample_name = sample_name
     self.fraction_reference_sites_to_emit = fraction_reference_sites_to_emit
     self.track_ref_reads = track_ref_reads
+    # gVCF (the values oracle/oracle.py passes to the reference's VariantCallerOptions; M: DESIGN.md section 9)
+    self.p_error, self.max_gq, self.gq_resolution, self.ploidy = p_error, max_gq, gq_resolution, ploidy
+    self.max_cache_coverage = max_cache_coverage
+
+
+class GvcfOptions:
+  """What the device gVCF pass needs (dv_gvcf_options) plus the call's sample name."""
+
+  def __init__(self, sample_name: str = '', p_error: float = 0.001, max_gq: int = 50, gq_resolution: int = 5,
+               max_cache_coverage: int = 100, include_med_dp: bool = False, left_padding: int = 0,
+               right_padding: int = 0):
+    if gq_resolution < 1:
+      raise ValueError('gq_resolution must be >= 1')
+    self.sample_name = sample_name
+    self.p_error, self.max_gq, self.gq_resolution = float(p_error), int(max_gq), int(gq_resolution)
+    self.max_cache_coverage, self.include_med_dp = int(max_cache_coverage), bool(include_med_dp)
+    self.left_padding, self.right_padding = int(left_padding), int(right_padding)
+
+  @classmethod
+  def from_caller_options(cls, options: VariantCallerOptions, include_med_dp: bool = False, left_padding: int = 0,
+                          right_padding: int = 0) -> 'GvcfOptions':
+    return cls(options.sample_name, options.p_error, options.max_gq, options.gq_resolution,
+               options.max_cache_coverage, include_med_dp, left_padding, right_padding)
+
+  def table(self) -> np.ndarray:
+    return reference_confidence_table(self.p_error, self.max_gq, self.max_cache_coverage)
+
+  def key(self) -> tuple:
+    return (self.sample_name, self.p_error, self.max_gq, self.gq_resolution, self.max_cache_coverage,
+            self.include_med_dp, self.left_padding, self.right_padding)
 
 
 def _deletion_size(allele) -> int:
@@ -113,8 +234,54 @@ class VariantCaller:
     if options.fraction_reference_sites_to_emit > 0:
       raise NotImplementedError('fraction_reference_sites_to_emit (reference-site sampling)')
     self._options = options
-    import numpy as np
     self._min_fraction_f32 = (float(np.float32(options.min_fraction_indels)), float(np.float32(options.min_fraction_snps)))
+
+  # ---- gVCF (variant_caller.py VariantCaller.reference_confidence / make_gvcfs)
+  def reference_confidence(self, n_ref: int, n_total: int) -> Tuple[int, Tuple[float, float, float]]:
+    """-> (raw GQ, normalised log10 likelihoods) through the cached table; deeper sites rescaled."""
+    if self._options.ploidy != 2:
+      raise NotImplementedError('reference confidence is restated for ploidy 2')
+    if n_ref < 0 or n_total < n_ref:
+      raise ValueError('Invalid read counts: n_ref=%d n_total=%d' % (n_ref, n_total))
+    n_ref, n_total = rescale_read_counts_if_necessary(n_ref, n_total, self._options.max_cache_coverage)
+    o = self._options
+    table = reference_confidence_table(float(o.p_error), int(o.max_gq), int(o.max_cache_coverage))
+    e = table[n_total * (n_total + 1) // 2 + n_ref]
+    return int(e['gq']), tuple(float(x) for x in e['likelihoods'])
+
+  def make_gvcfs(self, allele_count_summaries, include_med_dp: bool = False) -> List[T.Variant]:
+    """gVCF reference blocks of one allele counter's summary counts (AlleleCounter.summary_counts
+    tuples or AlleleCountSummary-like objects): consecutive sites with equal (quantised GQ,
+    has_valid_gl) form one record; a non-ACGT IUPAC reference base ends a block and gets none."""
+    out: List[T.Variant] = []
+    group: List = []
+    group_key = None
+
+    def flush():
+      if group:
+        first, last = group[0], group[-1]
+        depths = [g[4] for g in group]
+        out.append(gvcf_record(first[0], first[1], last[1] + 1, first[2], first[5], min(g[6] for g in group),
+                               min(depths), int(statistics.median(depths)) if include_med_dp else None,
+                               group_key[1], self._options.sample_name))
+
+    for s in allele_count_summaries:
+      name, pos, ref_base, n_ref, n_total = _summary_fields(s)
+      if ref_base in _CANONICAL:
+        raw_gq, lp = self.reference_confidence(n_ref, n_total)
+        key = (quantize_gq(raw_gq, self._options.gq_resolution), max(lp) == lp[0])
+        row = (name, pos, ref_base, n_ref, n_total, lp, raw_gq)
+      elif ref_base in _IUPAC_NON_CANONICAL:
+        key, row = None, None
+      else:
+        raise ValueError('Invalid reference base %r at %s:%d' % (ref_base, name, pos))
+      if key != group_key:
+        flush()
+        group, group_key = [], key
+      if row is not None:
+        group.append(row)
+    flush()
+    return out
 
   # ---- thresholds
   def _min_count(self, allele) -> int:

@@ -714,6 +714,65 @@ int dv_allele_counts_arrays(const dv_allele_counts* c, const int32_t** ref_suppo
                             const dv_allele_event** events, uint32_t* n_events, int32_t* n_reads_counted);
 void dv_allele_counts_free(dv_allele_counts* c);
 
+/* ---- gVCF reference-confidence blocks (device) ----------------------------------
+ * VariantCaller.make_gvcfs(allele_counter.summary_counts(left_padding, right_padding)) of the
+ * reference's deepvariant/variant_caller.py, computed next to the allele counter from the counts
+ * where they lie on the device; only the merged block records come back.  Per site of the
+ * interval (padding removed): n_ref = ref_supporting_read_count, n_total = TotalAlleleCounts
+ * (read alleles that are neither low quality nor REFERENCE, the later allele of one read key at
+ * one position standing, plus n_ref); deeper than max_cache_coverage the counts are rescaled
+ * (n_ref = ceil(n_ref / (1.0 * n_total) * M) in IEEE double, n_total = M) and the site's GQ and
+ * likelihoods are looked up in `table`; GQ is quantised by gq_resolution; runs of equal
+ * (quantised GQ, has_valid_gl) become one record.  A non-ACGT IUPAC reference base
+ * (NRYKMSWBDHV) ends a run and gives no record; any other character is DV_ERR_BAD_INPUT.
+ *
+ * The table is computed by the caller with the host restatement
+ * (deepvariant_amd/variant_calling.py reference_confidence_table): one restatement of the
+ * likelihood model, which the device only reads.  It is uploaded when it differs from the last
+ * one seen on this host thread and device. */
+typedef struct dv_gvcf_site {
+  double likelihoods[3];   /* normalised log10 genotype likelihoods (hom-ref, het, hom-alt) */
+  int32_t gq;              /* raw GQ */
+  int32_t has_valid_gl;    /* max(likelihoods) == likelihoods[0] */
+} dv_gvcf_site;
+
+typedef struct dv_gvcf_options {
+  double p_error;               /* what `table` was computed with (0.001 in the reference) */
+  int32_t max_gq;               /* likewise (50) */
+  int32_t gq_resolution;        /* gvcf_gq_binsize (5), >= 1 */
+  int32_t max_cache_coverage;   /* M: the table covers 0 <= n_ref <= n_total <= M */
+  int32_t include_med_dp;       /* compute MED_DP */
+  int32_t left_padding, right_padding;   /* sites are [interval_start + left, interval_end - right) */
+  const dv_gvcf_site* table;    /* entry n_total * (n_total + 1) / 2 + n_ref */
+  int64_t n_table;              /* (M + 1) * (M + 2) / 2 */
+} dv_gvcf_options;
+
+typedef struct dv_gvcf_block {  /* one gVCF record: Variant(start, end, ref, ['<*>']) with one call */
+  int64_t start, end;           /* absolute; end exclusive */
+  double likelihoods[3];        /* genotype_likelihood: the first site's */
+  int32_t gq;                   /* info GQ: the smallest raw GQ of the block */
+  int32_t min_dp;               /* MIN_DP: the smallest n_total */
+  int32_t med_dp;               /* MED_DP: int(statistics.median(n_total)); -1 unless include_med_dp */
+  uint8_t ref_base;             /* reference_bases: the first site's base */
+  uint8_t has_valid_gl;
+  uint8_t reserved[2];
+} dv_gvcf_block;
+
+typedef struct dv_gvcf_blocks dv_gvcf_blocks;
+
+/* dv_count_alleles_batch plus the gVCF blocks of every region, from the same counts in the same
+ * device pass (no further synchronisation).  read_keys[k] (may be NULL, as may read_keys):
+ * region k's read-key id per read (equal ids = one key of read_alleles, e.g. the supplementary
+ * alignments of a read); NULL = every read its own key.  blocks_out[k] receives region k's
+ * records (each freed with dv_gvcf_blocks_free); counts_out as for dv_count_alleles_batch.  On an
+ * error no result is left allocated. */
+int dv_count_alleles_gvcf_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                                const int32_t* const* read_keys, const dv_gvcf_options* gvcf,
+                                dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out, void* stream);
+/* -> the number of records; *blocks points at them (owned by `b`). */
+int64_t dv_gvcf_blocks_arrays(const dv_gvcf_blocks* b, const dv_gvcf_block** blocks);
+void dv_gvcf_blocks_free(dv_gvcf_blocks* b);
+
 /* CRC32C (Castagnoli) as used by TFRecord framing
  * (third_party/nucleus/io/example_writer.cc:88-104 via tensorflow::io::RecordWriter). */
 uint32_t dv_crc32c(const uint8_t* data, size_t n);
