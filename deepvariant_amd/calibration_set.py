@@ -9,10 +9,17 @@ generates the same pileups on every rank, in every run -- synthetic reads (synth
 encoder, bit-exact by construction -- so the corrections are a pure function of (weights, shape) and every process
 that loads a checkpoint computes (or reads from the cache next to it) the same numbers.
 
-  C <= 7         synthetic 30x Illumina pile-ups, the first C of make_examples' WGS channel list
+  C <= 7         synthetic Illumina pile-ups, the first C of make_examples' WGS channel list, at a mixture of
+                 coverages (ILLUMINA_DEPTHS: half of the blocks 30x-like, the rest 60x and 150x, whose pileups fill
+                 every row -- a set of 30x pileups alone left 150x candidates over the 1e-3 bar)
   C = 8, 10      synthetic PacBio HiFi 35x (6 + haplotype + 5mC), + the two alt-aligned diff channels at C = 10
   C = 9          synthetic ONT R10.4 50x (6 + haplotype) + the two alt-aligned diff channels
   other          no set: the model stays uncalibrated (plain fp16), identically on every rank
+
+A model taller than one pileup can be (--alt_aligned_pileup=rows: 300 rows of 100 + 100 + 100) gets FillPileupArray's
+row stack: the pileup drawn at a third of the height, then the alt-aligned block (the same pileup again for every third
+candidate, standing in for its indel's alt-aligned reads; zeros for the rest) and the second alt block (zeros: the
+sites are bi-allelic).
 """
 from __future__ import annotations
 
@@ -26,9 +33,11 @@ from deepvariant_amd import _lib
 from deepvariant_amd import dv_types as T
 from deepvariant_amd import synth
 
-SET_VERSION = 1          # bump when the generator changes: cached corrections are keyed on it
+SET_VERSION = 2          # bump when the generator changes: cached corrections are keyed on it
+                         # (2: Illumina blocks at a mixture of coverages)
 SET_SEED = 600613        # never one of the seeds tests or bench.py evaluate on
 DEFAULT_IMAGES = 256
+ILLUMINA_DEPTHS = (32.0, 150.0, 32.0, 60.0)   # mean coverage of Illumina block k: ILLUMINA_DEPTHS[k % 4]
 
 
 def _illumina_options(h: int, w: int, c: int) -> T.PileupImageOptions:
@@ -38,9 +47,19 @@ def _illumina_options(h: int, w: int, c: int) -> T.PileupImageOptions:
   return o
 
 
+_MAX_PILEUP_ROWS = 5 + 256    # the encoder draws at most 256 read rows under the 5-row reference band
+
+
+def _pileup_rows(h: int) -> int:
+  """Rows of one drawn pileup: h itself, or a third of it for the alt-aligned row stack; 0 = no set."""
+  if h <= _MAX_PILEUP_ROWS:
+    return h
+  return h // 3 if h % 3 == 0 and h // 3 <= _MAX_PILEUP_ROWS else 0
+
+
 def supported(shape: Tuple[int, int, int]) -> bool:
   h, w, c = shape
-  return 1 <= c <= 10 and w % 2 == 1 and h >= 8
+  return 1 <= c <= 10 and w % 2 == 1 and h >= 8 and _pileup_rows(h) > 0
 
 
 _BLOCK = 64              # images are generated in blocks of 64 candidates (seed + block number): draw(shape, n) is a
@@ -65,6 +84,13 @@ def draw(shape: Tuple[int, int, int], n: int = DEFAULT_IMAGES, device: int = 0,
 
 
 def _draw(h, w, c, n, device, seed):
+  hp = _pileup_rows(h)
+  if hp != h:                              # the alt-aligned row stack (module docstring)
+    pileups = _draw(hp, w, c, n, device, seed)
+    out = torch.zeros((n, h, w, c), dtype=torch.uint8, device=pileups.device)
+    out[:, :hp] = pileups
+    out[::3, hp:2 * hp] = pileups[::3]
+    return out
   from deepvariant_amd.pileup_image_native import _Encoder
   dev = torch.device('cuda', device)
   out = torch.empty((n, h, w, c), dtype=torch.uint8, device=dev)
@@ -79,7 +105,8 @@ def _draw(h, w, c, n, device, seed):
   for k, done in enumerate(range(0, n, _BLOCK)):
     m = min(_BLOCK, n - done)
     if c <= 7:                             # multi-allelic sites are off: one pileup per candidate
-      batch = synth.make_illumina_batch(_BLOCK, seed=seed + 7919 * k, options=opts, multi_allelic=False)
+      batch = synth.make_illumina_batch(_BLOCK, seed=seed + 7919 * k, options=opts, multi_allelic=False,
+                                        mean_depth=ILLUMINA_DEPTHS[k % len(ILLUMINA_DEPTHS)])
       img, _ = enc.encode(batch, c)
       block = torch.from_numpy(np.ascontiguousarray(img.reshape(-1, h, w, c)[:_BLOCK])).to(dev)
     elif c == 8:                           # the drawn HiFi channels alone

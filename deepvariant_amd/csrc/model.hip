@@ -3307,6 +3307,7 @@ int dv_model_load_weights(dv_model* m, const float* weights, int64_t n) {
 
 // The op list as calib.h's plan of plain NHWC tensors: fused pools unfolded (pool_in / pool_out), LDS-only
 // tensors given their real size, and the tensors the product keeps wider than fp16 marked (keep_f32).
+// Bump CALIBRATION_PLAN_VERSION (inception_v3.py) when keep_f32, the splits or the stem rounding points change.
 static dv::CalibPlan calib_plan_of(const dv_model* m) {
   dv::CalibPlan plan;
   plan.bufs.resize(m->buffers.size());

@@ -16,9 +16,18 @@ import torch
 
 from deepvariant_amd import _lib
 
+# Version of the rounding plan dv_model_calibrate measures against (csrc/model.hip calib_plan_of): which tensors are
+# kept wider than fp16 (keep_f32), the split-weight layers and the stem's rounding points.  Part of the name of a
+# cached calibration, so a file measured under another plan is never applied; bump it when the plan changes.
+CALIBRATION_PLAN_VERSION = 1
+
 
 class InceptionV3(torch.nn.Module):
   """`InceptionV3(input_shape=(H, W, C))`; forward(uint8 NHWC) -> probs [N,3]."""
+
+  # precise mode (dv_model_is_precise), set per model at construction; the class default is the fast path, which is
+  # also what a subclass that never creates a native model (a host-side stand-in) reports
+  precise = False
 
   def __init__(self, input_shape: Tuple[int, int, int], num_classes: int = 3,
                max_batch: int = 256, device: int = 0):
@@ -78,7 +87,8 @@ class InceptionV3(torch.nn.Module):
     call_variants and make_examples' fused route do after loading weights (`--calibration_examples`, 0 = off).
 
     `cache_prefix` (the checkpoint's path): the corrections are kept next to it in a file named by the content
-    hash of the weights, the shape, the set's version and size -- whoever finds the file applies it
+    hash of the weights, the shape, the set's version and size, the precise flag, the library's ABI version and the
+    rounding plan's version (CALIBRATION_PLAN_VERSION) -- whoever finds the file applies it
     (dv_model_apply_corrections) instead of measuring again; written atomically, never locked, safe to share
     between jobs because the name says everything the content depends on.  Returns the corrections, or None when
     the shape has no calibration set (the model then stays plain fp16 -- on every rank alike)."""
@@ -94,8 +104,9 @@ class InceptionV3(torch.nn.Module):
     path = None
     if cache_prefix:
       stamp = zlib.crc32(self.flat_weights.tobytes()) & 0xffffffff
-      path = '%s.dvcal-v%d-%08x-%dx%dx%d-n%d.f32' % ((cache_prefix, calibration_set.SET_VERSION, stamp) +
-                                                  tuple(self.input_shape) + (n_images,))
+      plan = 'p%d-abi%d-plan%d' % (1 if self.precise else 0, _lib.lib().dv_abi_version(), CALIBRATION_PLAN_VERSION)
+      path = '%s.dvcal-v%d-%s-%08x-%dx%dx%d-n%d.f32' % ((cache_prefix, calibration_set.SET_VERSION, plan, stamp) +
+                                                     tuple(self.input_shape) + (n_images,))
       try:
         corr = np.fromfile(path, np.float32)
         if corr.size == n_corr and np.isfinite(corr).all():

@@ -9,8 +9,9 @@ from deepvariant_amd.inception_v3 import InceptionV3
 
 
 class _Stub(InceptionV3):
-  def __init__(self, weights, shape=(100, 221, 7)):   # no dv_model_create
+  def __init__(self, weights, shape=(100, 221, 7), precise=False):   # no dv_model_create
     self.input_shape, self.flat_weights, self.device_index = shape, np.asarray(weights, np.float32), 0
+    self.precise = precise
     self.measured, self.applied = 0, []
     self._handle = None
 
@@ -61,7 +62,35 @@ def test_cache_file_protocol(tmp_path, monkeypatch):
   assert g.calibrate_for_checkpoint(256, cache_prefix=prefix) is None and g.measured == 0 and g.calibration == {'images': 0}
 
 
+def test_cache_name_keys_the_rounding_plan(tmp_path, monkeypatch):
+  """Corrections measured in fast mode (DV_PRECISE=0) are not those of a precise model of the same weights and shape
+  (calib_plan_of keeps the wide tensors in float32): each mode has its own file, and the other mode measures again.
+  The name also carries the library's ABI version and the rounding plan's version."""
+  from deepvariant_amd import _lib
+  from deepvariant_amd import inception_v3
+  monkeypatch.setattr(calibration_set, 'draw', lambda shape, n, device=0: list(range(n)))
+  prefix = str(tmp_path / 'model.ckpt')
+  w = np.full(1000, 3.0, np.float32)
+  fast = _Stub(w, (100, 147, 10), precise=False)
+  fast.calibrate_for_checkpoint(256, cache_prefix=prefix)
+  precise = _Stub(w, (100, 147, 10), precise=True)
+  precise.calibrate_for_checkpoint(256, cache_prefix=prefix)
+  assert fast.measured == 1 and precise.measured == 1 and precise.calibration['cached'] is False
+  files = sorted(os.listdir(tmp_path))
+  assert len(files) == 2, files
+  plan = '-abi%d-plan%d-' % (_lib.lib().dv_abi_version(), inception_v3.CALIBRATION_PLAN_VERSION)
+  assert any('-p0' + plan in f for f in files) and any('-p1' + plan in f for f in files), files
+  for f in files:
+    assert '.dvcal-v%d-' % calibration_set.SET_VERSION in f and f.endswith('-100x147x10-n256.f32')
+  again = _Stub(w, (100, 147, 10), precise=True)         # and each mode still finds its own file
+  again.calibrate_for_checkpoint(256, cache_prefix=prefix)
+  assert again.measured == 0 and again.calibration['cached'] is True
+
+
 def test_calibration_set_shapes():
   assert calibration_set.supported((100, 221, 7)) and calibration_set.supported((100, 199, 9))
   assert calibration_set.supported((100, 147, 10)) and calibration_set.supported((300, 221, 6))
   assert not calibration_set.supported((100, 221, 12)) and not calibration_set.supported((100, 220, 7))
+  # taller than one pileup: only the alt-aligned row stack of three pileups has a set
+  assert calibration_set.supported((261, 221, 7)) and calibration_set.supported((783, 221, 7))
+  assert not calibration_set.supported((400, 221, 7)) and not calibration_set.supported((786, 221, 7))

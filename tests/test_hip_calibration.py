@@ -178,7 +178,8 @@ def test_probabilities_are_a_pure_function_of_checkpoint_and_image():
   assert np.array_equal(halves, one)
 
 
-@pytest.mark.parametrize('shape', [(100, 199, 9), (100, 147, 10), (100, 147, 8), (100, 221, 6), (75, 75, 4)])
+@pytest.mark.parametrize('shape', [(100, 199, 9), (100, 147, 10), (100, 147, 8), (100, 221, 6), (75, 75, 4),
+                                   (300, 221, 6), (100, 221, 8)])
 def test_calibration_set_of_every_supported_shape(shape):
   from deepvariant_amd import calibration_set
   x = calibration_set.draw(shape, 48)
@@ -186,6 +187,9 @@ def test_calibration_set_of_every_supported_shape(shape):
   assert torch.equal(x, calibration_set.draw(shape, 48))
   assert int((x.reshape(48, -1).max(1).values > 0).sum()) == 48         # every image holds a pile-up
   assert calibration_set.draw((100, 221, 12), 8) is None                # no set: the model stays plain fp16
+  if shape[0] == 300:                     # --alt_aligned_pileup=rows: the pileup, then the alt-aligned block, then zeros
+    assert torch.equal(x[:, :100], calibration_set.draw((100,) + shape[1:], 48))
+    assert torch.equal(x[::3, 100:200], x[::3, :100]) and int(x[1::3, 100:].max()) == 0 and int(x[:, 200:].max()) == 0
 
 
 def test_applied_corrections_equal_the_calibration_that_measured_them(tmp_path, monkeypatch):
@@ -220,3 +224,28 @@ def test_applied_corrections_equal_the_calibration_that_measured_them(tmp_path, 
   third = _model(shape, ref.export_flat(), 300)
   assert np.array_equal(third.calibrate_for_checkpoint(128, cache_prefix=prefix), c1)
   assert third.calibration['cached'] is False
+
+
+def test_cache_of_a_fast_model_is_not_applied_to_a_precise_one(tmp_path, monkeypatch):
+  """Corrections measured under DV_PRECISE=0 are not a precise model's (calib_plan_of keeps the wide tensors of the
+  17x17 and 8x8 stages in float32): a precise model of the same checkpoint and shape does not find the fast model's file
+  and measures its own corrections, which differ."""
+  from oracle import inception_ref as R
+  shape = (100, 147, 10)
+  flat = R.make_random_model(10, seed=61).export_flat()
+  prefix = str(tmp_path / 'ckpt')
+  monkeypatch.setenv('DV_PRECISE', '0')
+  fast = _model(shape, flat, 64)
+  monkeypatch.delenv('DV_PRECISE')
+  assert not fast.precise
+  c_fast = fast.calibrate_for_checkpoint(128, cache_prefix=prefix)
+  assert fast.calibration['cached'] is False
+  precise = _model(shape, flat, 64)                                  # the product's default for this shape
+  assert precise.precise
+  c_precise = precise.calibrate_for_checkpoint(128, cache_prefix=prefix)
+  assert precise.calibration['cached'] is False
+  assert len([f for f in os.listdir(tmp_path) if '.dvcal-' in f]) == 2
+  assert c_fast.shape == c_precise.shape and not np.array_equal(c_fast, c_precise)
+  again = _model(shape, flat, 64)                                    # and a precise model finds its own file
+  assert np.array_equal(again.calibrate_for_checkpoint(128, cache_prefix=prefix), c_precise)
+  assert again.calibration['cached'] is True

@@ -32,26 +32,6 @@ def _tail_images():
   return _cache['x']
 
 
-def _product_model(shape, weights, max_batch, precise=None):
-  """The product's model preparation: weights, then the shift calibration on the checkpoint's fixed synthetic set
-  (InceptionV3.calibrate_for_checkpoint -- what call_variants / make_examples do; other pileups than any sample here).
-  `precise` None = the product's default for the shape (precise mode for more than 8 input channels), else DV_PRECISE."""
-  import os
-  from deepvariant_amd.inception_v3 import InceptionV3
-  old = os.environ.pop('DV_PRECISE', None)
-  if precise is not None:
-    os.environ['DV_PRECISE'] = '1' if precise else '0'
-  try:
-    m = InceptionV3(shape, max_batch=max_batch)
-  finally:
-    os.environ.pop('DV_PRECISE', None)
-    if old is not None:
-      os.environ['DV_PRECISE'] = old
-  m.load_flat_weights(weights)
-  m.calibrate_for_checkpoint(256)
-  return m
-
-
 def test_gpu_oracle_equals_cpu_oracle_on_256_pileups():
   from tests import cnn_tail as T
   from oracle import inception_ref as R
@@ -69,7 +49,7 @@ def test_illumina30_tail_on_held_out_weight_seeds(seed):
   x = _tail_images()
   ref = R.make_random_model(7, seed=seed)
   want = T.oracle_probs_gpu(R.make_random_model(7, seed=seed).cuda(), x)
-  model = _product_model((100, 221, 7), ref.export_flat(), 8192)
+  model = T.product_model((100, 221, 7), ref.export_flat(), 8192)
   got = T.hip_probs(model, x, 8192)
   s = T.tail_stats(got, want)
   print('seed %d: %s' % (seed, T.fmt(s)))
@@ -95,7 +75,7 @@ def test_long_read_shapes_on_2048_examples(kind, shape, seed):
   ref_gpu = R.make_random_model(shape[2], seed=seed).cuda()
   T.check_gpu_oracle(ref, ref_gpu, x, n=64, tol=5e-6)
   want = T.oracle_probs_gpu(ref_gpu, x)
-  model = _product_model(shape, ref.export_flat(), n)
+  model = T.product_model(shape, ref.export_flat(), n)
   assert model.precise
   got = T.hip_probs(model, x, n)
   s = T.tail_stats(got, want)
@@ -118,7 +98,7 @@ def test_long_read_shapes_in_fast_mode(kind, shape, seed):
   x = _longread_images(kind, n)
   ref = R.make_random_model(shape[2], seed=seed)
   want = T.oracle_probs_gpu(R.make_random_model(shape[2], seed=seed).cuda(), x)
-  model = _product_model(shape, ref.export_flat(), n, precise=False)
+  model = T.product_model(shape, ref.export_flat(), n, precise=False)
   assert not model.precise
   got = T.hip_probs(model, x, n)
   s = T.tail_stats(got, want)
@@ -138,8 +118,8 @@ def test_illumina30_in_precise_mode_is_opt_in_and_tighter():
   seed = HELD_OUT_SEEDS[0]
   ref = R.make_random_model(7, seed=seed)
   want = T.oracle_probs_gpu(R.make_random_model(7, seed=seed).cuda(), x)
-  fast = _product_model((100, 221, 7), ref.export_flat(), 4096)
-  prec = _product_model((100, 221, 7), ref.export_flat(), 4096, precise=True)
+  fast = T.product_model((100, 221, 7), ref.export_flat(), 4096)
+  prec = T.product_model((100, 221, 7), ref.export_flat(), 4096, precise=True)
   assert not fast.precise and prec.precise
   sf = T.tail_stats(T.hip_probs(fast, x, 4096), want)
   sp = T.tail_stats(T.hip_probs(prec, x, 4096), want)
