@@ -286,6 +286,60 @@ __device__ __forceinline__ void conv_epilogue(const float16_t (&acc)[NB][PT], co
   }
 }
 
+// One pooled 8-channel group at the calling thread's pixel (y, x) of an H x W map (thread = pixel slot, the map's
+// slots consecutive in the wave): src = the group's raw float32 staging, [half hi][pixel slot][4 floats] from the
+// map's first slot; inv = 1 / (cells inside the window); shift = the group's 8 shifts (shift + ReLU) or NULL.  Every
+// lane of the wave must take part (cross-lane moves).  Shared by conv_epilogue_avg and block35.hip.
+__device__ __forceinline__ void avg_pool_group(const float4* src, int y, int x, int H, int W, int lane, float inv,
+                                               const float* shift, float (&o)[8]) {
+  // Separable: every thread sums ITS column (rows y-1 .. y+1 of column x: three reads) and takes the two
+  // neighbouring columns' sums from lanes -1 / +1 (v_mov_dpp wave_shr / wave_shl: no LDS) -- consecutive slots of a
+  // map are consecutive columns of a row.  The first and last lane of a wave fetch the column their missing
+  // neighbour would have summed themselves (two active lanes: no LDS bandwidth to speak of).  Round 6: a third of
+  // the LDS reads of the nine-point form, whose 72 ds_read_b128 per thread and pooled subtile made the pooling
+  // epilogue LDS-bound (profiles/r06_experiments.txt).  Same sums in the same order as avgpool3s1_kernel.
+  auto column = [&](int xc, bool wanted, float (&v)[8]) {
+    float r[3][8];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+      const int yy = y + dy - 1;
+      const bool ok = wanted && yy >= 0 && yy < H;
+      float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), up = lo;
+      if (ok) {
+        lo = src[yy * W + xc];
+        up = src[256 + yy * W + xc];
+      }
+      r[dy][0] = lo.x; r[dy][1] = lo.y; r[dy][2] = lo.z; r[dy][3] = lo.w;
+      r[dy][4] = up.x; r[dy][5] = up.y; r[dy][6] = up.z; r[dy][7] = up.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = r[0][j] + r[1][j] + r[2][j];
+  };
+  float col[3][8];
+  column(x, true, col[1]);
+  const bool first = lane == 0, last = lane == 63;
+  const int xe = first ? x - 1 : x + 1;
+  float edge[8];
+  column(xe, (first || last) && xe >= 0 && xe < W, edge);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int vi = __builtin_bit_cast(int, col[1][j]);
+    const float from_left = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x138, 0xf, 0xf, false));   // wave_shr:1
+    const float from_right = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x130, 0xf, 0xf, false));  // wave_shl:1
+    col[0][j] = x == 0 ? 0.f : first ? edge[j] : from_left;
+    col[2][j] = x == W - 1 ? 0.f : last ? edge[j] : from_right;
+  }
+  float sh[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (shift != nullptr) {
+    const float4 s0 = *reinterpret_cast<const float4*>(shift);
+    const float4 s1 = *reinterpret_cast<const float4*>(shift + 4);
+    sh[0] = s0.x; sh[1] = s0.y; sh[2] = s0.z; sh[3] = s0.w;
+    sh[4] = s1.x; sh[5] = s1.y; sh[6] = s1.z; sh[7] = s1.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = avg_finish(col[0][j], col[1][j], col[2][j], inv, sh[j], shift != nullptr);
+}
+
 // Epilogue of conv_mfma_kernel<..., AVG>: branches without `avgpool` store as conv_epilogue does; the others
 // leave their RAW float32 outputs in LDS (the weight slabs' space holds two 32-cout subtiles x 256 pixel slots
 // x 4 bytes at a time, so a 128-cout tile is pooled in two halves), [subtile][8-cout group q][pixel slot]
@@ -361,53 +415,8 @@ __device__ __forceinline__ void conv_epilogue_avg(const float16_t (&acc)[NB][PT]
         const int group = cbase / 8 + q8;
         if (group * 8 >= b.Cout) break;
         const float4* src = reinterpret_cast<const float4*>(tile) + (nbl * 4 + q8) * 2 * 256 + map0;
-        // Separable: every thread sums ITS column (rows y-1 .. y+1 of column x: three reads) and takes the two
-        // neighbouring columns' sums from lanes -1 / +1 (v_mov_dpp wave_shr / wave_shl: no LDS) -- consecutive slots of a
-        // map are consecutive columns of a row.  The first and last lane of a wave fetch the column their missing
-        // neighbour would have summed themselves (two active lanes: no LDS bandwidth to speak of).  Round 6: a third of
-        // the LDS reads of the nine-point form, whose 72 ds_read_b128 per thread and pooled subtile made the pooling
-        // epilogue LDS-bound (profiles/r06_experiments.txt).  Same sums in the same order as avgpool3s1_kernel.
-        auto column = [&](int xc, bool wanted, float (&v)[8]) {
-          float r[3][8];
-#pragma unroll
-          for (int dy = 0; dy < 3; ++dy) {
-            const int yy = y + dy - 1;
-            const bool ok = wanted && yy >= 0 && yy < H;
-            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), up = lo;
-            if (ok) {
-              lo = src[yy * W + xc];
-              up = src[256 + yy * W + xc];
-            }
-            r[dy][0] = lo.x; r[dy][1] = lo.y; r[dy][2] = lo.z; r[dy][3] = lo.w;
-            r[dy][4] = up.x; r[dy][5] = up.y; r[dy][6] = up.z; r[dy][7] = up.w;
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = r[0][j] + r[1][j] + r[2][j];
-        };
-        float col[3][8];
-        column(x, true, col[1]);
-        const bool first = lane == 0, last = lane == 63;
-        const int xe = first ? x - 1 : x + 1;
-        float edge[8];
-        column(xe, (first || last) && xe >= 0 && xe < W, edge);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int vi = __builtin_bit_cast(int, col[1][j]);
-          const float from_left = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x138, 0xf, 0xf, false));   // wave_shr:1
-          const float from_right = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, vi, 0x130, 0xf, 0xf, false));  // wave_shl:1
-          col[0][j] = x == 0 ? 0.f : first ? edge[j] : from_left;
-          col[2][j] = x == W - 1 ? 0.f : last ? edge[j] : from_right;
-        }
-        float sh[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (b.shift != nullptr) {
-          const float4 s0 = *reinterpret_cast<const float4*>(b.shift + group * 8);
-          const float4 s1 = *reinterpret_cast<const float4*>(b.shift + group * 8 + 4);
-          sh[0] = s0.x; sh[1] = s0.y; sh[2] = s0.z; sh[3] = s0.w;
-          sh[4] = s1.x; sh[5] = s1.y; sh[6] = s1.z; sh[7] = s1.w;
-        }
         float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = avg_finish(col[0][j], col[1][j], col[2][j], inv, sh[j], b.shift != nullptr);
+        avg_pool_group(src, y, x, H, W, lane, inv, b.shift != nullptr ? b.shift + group * 8 : nullptr, o);
         const size_t at = static_cast<size_t>(obase) + static_cast<size_t>(group) * gstride;
         if (b.out32 != nullptr) {
           float4* d = reinterpret_cast<float4*>(b.out32 + at * 8);

@@ -42,6 +42,7 @@
 #include "dv_internal.h"
 #include "conv_common.h"
 #include "imgconv.h"
+#include "block35.h"
 #include "chain.h"
 #include "stem_fused.h"
 #include "calib.h"
@@ -1545,6 +1546,10 @@ struct Op {
   int chain_g = 0;               // images per tile
   int chain_tpx = 0;             // pixels per tile (192: small maps, 1-D filters; 256: 35x35 stage, 3x3 / 5x5)
   bool in_chain = false;         // a non-leading member of a chain
+  // block35.hip: an Inception-A block of the 35x35 stage as ONE launch (choose_block35), placed at its heads' leader;
+  // role in the block: 1 = b1 (the leader), 2 = 5x5 reducer, 3 = 3x3dbl reducer, 4 = pooled projection (raw 1x1),
+  // 5 = 5x5, 6 = 3x3 64->96, 7 = 3x3 96->96, 8 = the average pool; ops 2-8 follow the leader in this order
+  int b35 = 0;
 };
 
 struct LayerInfo {
@@ -2077,6 +2082,63 @@ struct dv_model {
     }
   }
 
+  // Inception-A blocks of the 35x35 stage (mixed0..2) as ONE launch each (block35.hip): the grouped 1x1 heads, their
+  // average pool, the 5x5 and the 3x3 -> 3x3 pair on tiles of one whole map, the reducers and the 3x3 intermediate
+  // in LDS only.  Recognises the pattern build() emits after grouping -- b1 (leader) + 5x5 reducer + 3x3 reducer +
+  // pooled projection, then 5x5, 3x3, 3x3, avg pool -- and declines, keeping the per-layer launches, for wide / split
+  // ops (precise mode), heads that max-pool their input (DV_NO_POOL2_IN_CONV) and maps of more than 256 pixels.
+  // DV_NO_BLOCK35 keeps the per-layer launches; DV_NO_CHAIN implies it.
+  void choose_block35() {
+    if (getenv("DV_NO_BLOCK35") != nullptr || getenv("DV_NO_CHAIN") != nullptr) return;
+    std::vector<int> readers(buffers.size(), 0);
+    for (const Op& o : ops) readers[o.in_buf]++;
+    for (size_t i = 0; i + 7 < ops.size(); ++i) {
+      const Op &b1 = ops[i], &r5 = ops[i + 1], &r3 = ops[i + 2], &pj = ops[i + 3];
+      const Op &c5 = ops[i + 4], &c3a = ops[i + 5], &c3b = ops[i + 6], &ap = ops[i + 7];
+      const int P = b1.oh * b1.ow;
+      auto plain = [&](const Op& o) {
+        return o.type == kOpConv && o.stride == 1 && !o.split && !o.in_wide && !buffers[o.out_buf].wide && !o.pool_in &&
+               !o.pool_out && !o.first_u8 && !o.stem_a && !o.stem_b && !o.band && o.cin % kChunk == 0 &&
+               o.cin == o.cin_real && o.oh == b1.oh && o.ow == b1.ow && o.ih == b1.oh && o.iw == b1.ow && o.b35 == 0;
+      };
+      auto head = [&](const Op& o, int cout) {
+        return plain(o) && o.kh == 1 && o.kw == 1 && o.in_buf == b1.in_buf && o.cout == cout;
+      };
+      auto same = [&](const Op& o, int k, int in_buf, int cin, int cout) {
+        return plain(o) && o.kh == k && o.kw == k && o.pad_h == k / 2 && o.pad_w == k / 2 && o.in_buf == in_buf &&
+               o.cin == cin && o.cout == cout && !o.raw;
+      };
+      const int O = b1.out_buf;
+      const bool ok =
+          b1.group_followers == 3 && P <= dv::kBlock35TilePx && head(b1, dv::kBlock35B1) && !b1.raw &&
+          head(r5, dv::kBlock35Red5) && !r5.raw && head(r3, dv::kBlock35Red3) && !r3.raw &&
+          head(pj, pj.cout) && pj.raw && (pj.cout == 32 || pj.cout == 64) &&
+          same(c5, 5, r5.out_buf, dv::kBlock35Red5, dv::kBlock35Out5) &&
+          same(c3a, 3, r3.out_buf, dv::kBlock35Red3, dv::kBlock35Out3) &&
+          same(c3b, 3, c3a.out_buf, dv::kBlock35Out3, dv::kBlock35Out3) &&
+          ap.type == kOpAvgPool && ap.in_buf == pj.out_buf && ap.pool_shift_relu &&
+          readers[r5.out_buf] == 1 && readers[r3.out_buf] == 1 && readers[c3a.out_buf] == 1 && readers[pj.out_buf] == 1 &&
+          c5.out_buf == O && c3b.out_buf == O && ap.out_buf == O && !buffers[O].f32 && !buffers[O].wide &&
+          b1.out_coff % 8 == 0 && c5.out_coff % 8 == 0 && c3b.out_coff % 8 == 0 && ap.out_coff % 8 == 0;
+      if (!ok) continue;
+      for (int k = 0; k < 8; ++k) {
+        Op& o = ops[i + k];
+        o.b35 = k + 1;
+        o.chain_len = 0;
+        o.in_chain = false;
+        o.v2 = false;
+        o.avg_partner = -1;
+        o.avg_tile_g = 0;
+      }
+      for (int b : {r5.out_buf, r3.out_buf, c3a.out_buf, pj.out_buf}) {   // LDS only (the projection stays float32)
+        const bool f32 = buffers[b].f32;
+        buffers[b] = {1, 1, buffers[b].c, 0};
+        buffers[b].f32 = f32;
+      }
+      i += 7;
+    }
+  }
+
   // tf_keras applications/inception_v3.py, construction order = layer order.
   void build() {
     const int in_buf = new_buffer(desc.height, desc.width, 16);
@@ -2261,6 +2323,7 @@ struct dv_model {
     choose_split();
     choose_side_pool();
     choose_avg_epilogue();
+    choose_block35();
     for (size_t i = 0; i < ops.size(); ++i) {  // packed-weight image per LAUNCH (after grouping)
       Op& op = ops[i];
       if (op.type != kOpConv) continue;
@@ -2269,7 +2332,8 @@ struct dv_model {
       const int n_tiles = (subs + op.nb - 1) / op.nb;
       for (int gi = 0; gi <= op.group_followers; ++gi) ops[i + gi].w_off = packed_halfs;
       packed_halfs += op.first_u8 ? static_cast<size_t>(kFirstMaxChunks) * 32 * kChunk
-                      : (op.chain_len > 0 || op.in_chain)
+                      : op.b35 == 1 ? static_cast<size_t>(2) * (op.cin / kChunk) * 2 * 128 * 8   // block35.hip's heads
+                      : (op.chain_len > 0 || op.in_chain || op.b35 >= 5)
                           ? static_cast<size_t>(op.n_chunks) * 2 * ((op.cout + 31) / 32 * 32) * 8
                       : op.v2     ? static_cast<size_t>(op.v2_tiles) * op.v2_steps *
                                         dv::imgconv_wslab_halfs(op.kh, op.kw, op.nb)
@@ -2619,6 +2683,51 @@ int run_ops(dv_model* m, int first, int last, int n, hipStream_t stream,
         dv::launch_stem_b(a, m->stem_b_grid, stream);
       }
       oi += 1;
+    } else if (op.type == kOpConv && op.b35 == 1) {
+      const Op &r5 = m->ops[oi + 1], &r3 = m->ops[oi + 2], &pj = m->ops[oi + 3];
+      const Op &c5 = m->ops[oi + 4], &c3a = m->ops[oi + 5], &c3b = m->ops[oi + 6], &ap = m->ops[oi + 7];
+      const BufferDesc& ib = m->buffers[op.in_buf];
+      const _Float16* wbase = static_cast<const _Float16*>(m->d_w.ptr);
+      const float* sbase = static_cast<const float*>(m->d_shift.ptr);
+      dv::Block35Args a{};
+      a.in = static_cast<const _Float16*>(m->dbuf[op.in_buf].ptr);
+      a.ig = ib.geom();
+      a.in_img_bytes = static_cast<unsigned>(ib.bytes_per_example());
+      a.N = n;
+      a.h = op.oh;
+      a.w = op.ow;
+      a.n_chunks = op.cin / kChunk;
+      a.w1 = wbase + op.w_off;
+      a.sh_red5 = sbase + r5.shift_off;
+      a.sh_red3 = sbase + r3.shift_off;
+      a.sh_b1 = sbase + op.shift_off;
+      a.sh_pool = sbase + ap.shift_off;
+      a.pool_c = pj.cout;
+      a.w5 = wbase + c5.w_off;
+      a.sh5 = sbase + c5.shift_off;
+      a.w3a = wbase + c3a.w_off;
+      a.sh3a = sbase + c3a.shift_off;
+      a.w3b = wbase + c3b.w_off;
+      a.sh3b = sbase + c3b.shift_off;
+      a.out = static_cast<_Float16*>(m->dbuf[op.out_buf].ptr);
+      a.og = ob.geom();
+      a.goff_b1 = op.out_coff / 8;
+      a.goff_5 = c5.out_coff / 8;
+      a.goff_3 = c3b.out_coff / 8;
+      a.goff_pool = ap.out_coff / 8;
+      const double px = static_cast<double>(n) * op.oh * op.ow;
+      const double tr_flops = 2.0 * px * (static_cast<double>(op.cin) * (op.cout + r5.cout + r3.cout + pj.cout) +
+                                          25.0 * c5.cin * c5.cout + 9.0 * c3a.cin * c3a.cout + 9.0 * c3b.cin * c3b.cout);
+      const std::string tr_label = "block35 " + std::to_string(op.cin) + "->" + std::to_string(op.cout) + "|" +
+                                   std::to_string(r5.cout) + "->" + std::to_string(c5.cout) + " 5x5|" +
+                                   std::to_string(r3.cout) + "->" + std::to_string(c3a.cout) + "->" +
+                                   std::to_string(c3b.cout) + " 3x3|" + std::to_string(pj.cout) + " pool @" +
+                                   std::to_string(op.oh) + "x" + std::to_string(op.ow);
+      TraceScope tr(stream, tr_label, tr_flops,
+                    2.0 * px * (static_cast<double>(op.cin) + op.cout + c5.cout + c3b.cout + pj.cout));
+      dv::ProfileScope prof(dv::kProfConv, stream);
+      dv::launch_block35(a, m->n_cus, stream);
+      oi += 7;
     } else if (op.type == kOpConv && op.chain_len > 0) {
       const Op& last = m->ops[oi + op.chain_len - 1];
       const BufferDesc& ib = m->buffers[op.in_buf];
@@ -3185,8 +3294,23 @@ int dv_model_load_weights(dv_model* m, const float* weights, int64_t n) {
         }
       return;
     }
-    if (op.chain_len > 0 || op.in_chain) {
-      // chain.hip: [channel chunk][tap][k-group][cout_pad][8]
+    if (op.b35 >= 1 && op.b35 <= 4) {
+      // block35.hip's heads: [pass][channel chunk][k-group][128 couts][8]; pass 0 = 5x5 reducer (couts 0..) + 3x3
+      // reducer (64..), pass 1 = b1 (0..) + pooled projection (64..)
+      const int pass = op.b35 == 1 || op.b35 == 4 ? 1 : 0, base = op.b35 == 1 || op.b35 == 2 ? 0 : 64;
+      const int n_chunks = l.cin / kChunk;
+      _Float16* dst = packed.data() + op.w_off;
+      for (int cc = 0; cc < n_chunks; ++cc)
+        for (int co = 0; co < op.cout; ++co)
+          for (int jj = 0; jj < kChunk; ++jj) {
+            const float v = w[static_cast<size_t>(cc * kChunk + jj) * l.cout + co];
+            dst[(((static_cast<size_t>(pass) * n_chunks + cc) * 2 + jj / 8) * 128 + base + co) * 8 + (jj % 8)] =
+                static_cast<_Float16>(v * inv[co]);
+          }
+      return;
+    }
+    if (op.chain_len > 0 || op.in_chain || op.b35 >= 5) {
+      // chain.hip, block35.hip: [channel chunk][tap][k-group][cout_pad][8]
       const int cout_pad = (op.cout + 31) / 32 * 32, taps = op.kh * op.kw;
       _Float16* dst = packed.data() + op.w_off;
       for (int cc = 0; cc < l.cin / kChunk; ++cc)
@@ -3435,7 +3559,8 @@ int dv_model_op_label(const dv_model* m, int op_index, char* buf, int capacity) 
   const char* kind = op.type == kOpConv ? "conv" : op.type == kOpMaxPool ? "maxpool" : "avgpool";
   snprintf(buf, static_cast<size_t>(capacity), "%s layer=%d k=%dx%d s=%d cin=%d cout=%d out=%dx%d raw=%d in_buf=%d out_buf=%d coff=%d lds_only=%d",
            kind, op.layer, op.kh, op.kw, op.stride, op.cin, op.cout, op.oh, op.ow, op.raw ? 1 : 0, op.in_buf, op.out_buf,
-           op.out_coff, (op.type == kOpConv && (op.stem_a || op.stem_b)) || (op_index + 1 < static_cast<int>(m->ops.size()) && m->ops[op_index + 1].in_chain && m->ops[op_index + 1].in_buf == op.out_buf) ? 1 : 0);
+           op.out_coff, (op.type == kOpConv && (op.stem_a || op.stem_b)) || (op_index + 1 < static_cast<int>(m->ops.size()) && m->ops[op_index + 1].in_chain && m->ops[op_index + 1].in_buf == op.out_buf) ||
+               (op.b35 >= 2 && op.b35 <= 4) || op.b35 == 6 ? 1 : 0);
   return DV_OK;
 }
 
