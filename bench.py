@@ -9,12 +9,18 @@ input that is already resident in HBM:
 both through the C ABI of libdvhip.so.  Every rank processes its own shard of
 candidates (weak scaling, no data-path collective besides the final gather).
 
-Prints ONE JSON line on rank 0 (see the repo task contract), including
-  roofline          conv kernels (MFMA bound): achieved TFLOP/s over the timed
-                    region, measured with HIP events around every launch
+Prints ONE JSON line on rank 0 (see the repo task contract).  A plain run sets up, warms up, times the K steps,
+writes --dump-outputs and prints the headline (`value`, `ms_per_step`, `config`, `calibration`).  `--full` adds
+everything else, each part after the timed steps:
+  roofline          conv kernels (MFMA bound): achieved TFLOP/s, measured with
+                    HIP events around every launch of an instrumented pass;
+                    `traffic` from two rocprofv3 counter passes of a child run
   roofline_encoder  encoder kernel (HBM bound): algorithmic GB/s
+  value_dense       the same K steps with blank-row skipping off
   cpu_baseline      the CPU oracle (C++ encoder restatement + fp32 torch
                     Inception) on a bounded sample, on this host's cores
+  parity            a sample of the timed batch against the oracle
+  workloads         the hifi35 / ont50 shapes, each with the same parts
 """
 import argparse
 import json
@@ -57,25 +63,33 @@ def parse_args():
   ap.add_argument('--repeat', type=int, default=1,
                   help='--mode bam: every calling region of the slice this many times (10 = the work of 1 Mb); the '
                        'decoded BAM block is reused between passes')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check everything beyond the headline: the instrumented pass (roofline), the '
+                       'counter passes (roofline.traffic), value_dense, cpu_baseline, parity and, on one GPU, the '
+                       'hifi35 / ont50 workloads; the --no-* options below leave parts of it out')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='--full: skip cpu_baseline and the parity checks')
   ap.add_argument('--calibration-images', type=int, default=256,
                   help='examples (of another synthetic seed) dv_model_calibrate sees before the timed region; 0 = off')
   ap.add_argument('--no-workloads', action='store_true',
-                  help='skip the hifi35 / ont50 lines the default 1-GPU run attaches as "workloads"')
+                  help='skip the hifi35 / ont50 lines a --full 1-GPU run attaches as "workloads" (and their '
+                       '--dump-outputs arrays)')
   ap.add_argument('--no-dense', action='store_true',
-                  help='skip the second timing with blank-row skipping off (value_dense): profiler runs use it so that '
-                       'their per-kernel statistics describe one configuration')
+                  help='--full: skip the second timing with blank-row skipping off (value_dense) and, for the long-read '
+                       'shapes, the fast-mode timing: profiler runs use it so that their per-kernel statistics describe '
+                       'one configuration')
   ap.add_argument('--dense-only', action='store_true',
                   help='blank-row skipping off for the whole run (profiler runs of the dense configuration)')
   ap.add_argument('--parity-sites', type=int, default=4096,
-                  help='sites of the timed batch checked against the oracle after the timed region')
+                  help='--full: sites of the timed batch checked against the oracle after the timed region')
   ap.add_argument('--cpu-sample', type=int, default=0,
-                  help='candidates in the CPU-baseline sample (0 = auto)')
+                  help='--full: candidates in the CPU-baseline sample (0 = auto)')
   ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                   help='resident mode: after the timed steps write what the last timed step computed as DIR/<name>.npy '
                        '(float32 / float64, at most 64 MB in all), per workload: the probabilities of every candidate '
-                       'and a fixed sample of the pile-up tensors they were classified from.  The inputs are seeded, '
-                       'so two builds run with the same arguments can be compared file for file')
+                       'and a fixed sample of the pile-up tensors they were classified from (on one GPU the hifi35 / '
+                       'ont50 steps are timed for theirs, with or without --full).  The inputs are seeded, so two builds '
+                       'run with the same arguments can be compared file for file')
   args = ap.parse_args()
   if args.steps < 1 or args.warmup < 0:
     ap.error('--steps must be at least 1 and --warmup at least 0')
@@ -302,25 +316,26 @@ def run_rank(args, rank, local_rank, world):
       all_p, all_i = gathered['all']
       dump['illumina30_probs'] = all_p.cpu().numpy().astype(np.float32)
       dump['illumina30_candidate_ids'] = all_i.cpu().numpy().astype(np.float64)
-  # ---- instrumented pass: the SAME K steps again with a HIP event pair around
-  # every kernel launch, on the launch stream.  Event profiling forces eager
-  # launches (the timed region replays the forward as one hipGraph), so it is
-  # kept out of `value`; the per-kernel durations feed `roofline` only and must
-  # agree with profiles/*kernel_stats*.
-  lib.dv_set_profiling(1)
-  for _ in range(args.steps):
-    step()
-  sync_all()
-  enc_ms = lib.dv_profile_ms(0)
-  enc_launches = lib.dv_last_profile_count()
-  conv_ms = lib.dv_profile_ms(1)
-  conv_launches = lib.dv_last_profile_count()
-  other_ms = lib.dv_profile_ms(2)
-  lib.dv_set_profiling(0)
+  if args.full:
+    # ---- instrumented pass: the SAME K steps again with a HIP event pair around
+    # every kernel launch, on the launch stream.  Event profiling forces eager
+    # launches (the timed region replays the forward as one hipGraph), so it is
+    # kept out of `value`; the per-kernel durations feed `roofline` only and must
+    # agree with profiles/*kernel_stats*.
+    lib.dv_set_profiling(1)
+    for _ in range(args.steps):
+      step()
+    sync_all()
+    enc_ms = lib.dv_profile_ms(0)
+    enc_launches = lib.dv_last_profile_count()
+    conv_ms = lib.dv_profile_ms(1)
+    conv_launches = lib.dv_last_profile_count()
+    other_ms = lib.dv_profile_ms(2)
+    lib.dv_set_profiling(0)
 
   # ---- the same K steps with blank-row skipping OFF (dv_model_set_blank_skip; identical probabilities, bit for
   # bit): `value_dense` / `roofline.dense`, so that the headline can be read with and without the data-dependent part
-  thr = model.blank_thresholds(n_items) if n_items <= model.max_batch else None
+  thr = model.blank_thresholds(n_items) if args.full and n_items <= model.max_batch else None
   dense = None
   if thr is not None and not args.no_dense:
     model.set_blank_skip(False)
@@ -345,15 +360,6 @@ def run_rank(args, rank, local_rank, world):
 
   if rank == 0:
     value = items_per_step * args.steps / elapsed
-    conv_flops_per_item = 2.0 * model.conv_macs_per_example
-    executed = executed_conv_flops(model, (H, W, C), thr, conv_flops_per_item) if thr is not None else None
-    exec_flops_per_item = executed['executed_flops_per_candidate'] if executed else conv_flops_per_item
-    conv_tflops = (exec_flops_per_item * n_items * args.steps /
-                   (conv_ms * 1e-3) / 1e12) if conv_ms > 0 else 0.0
-    bytes_per_item = algorithmic_bytes_per_item(host_batch, C)
-    enc_gbs = (bytes_per_item * n_items * args.steps / (enc_ms * 1e-3) / 1e9
-               if enc_ms > 0 else 0.0)
-    conv_traffic, enc_traffic, traffic_note = pmc_traffic(args, n_items) if world == 1 else (None, None, None)
     out = {
         'metric': 'candidate pileups/sec (encode+CNN)',
         'value': value,
@@ -377,43 +383,53 @@ def run_rank(args, rank, local_rank, world):
             'collective_world_size': (dist.get_world_size() if world > 1 else 1),
             'collective_backend': (dist.get_backend() if world > 1 else None),
         },
-        'roofline': {
-            'kernel': 'conv kernels: stem_a/stem_b (fused stem), chain_kernel (fused 1x7/7x1 chains), '
-                      'imgconv_kernel, conv_mfma_kernel<NB,PT>, conv_resident_kernel (all 94 conv layers)',
-            'bound': 'mfma',
-            'achieved': conv_tflops,
-            'peak': MFMA_F16_PEAK_TFLOPS,
-            'unit': 'TFLOP/s',
-            'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS,
-            'traffic': conv_traffic,
-            'traffic_note': traffic_note,
-            'flops_per_candidate': conv_flops_per_item,
-            'executed_flops_per_candidate': exec_flops_per_item,
-            'achieved_note': '`achieved` / `frac` count EXECUTED MFMA FLOPs: the nominal 2 x MACs of the 94 layers minus '
-                             'the output tiles blank-row skipping copied instead of computing (mirrored on the host from '
-                             "the kernels' tile rules and the per-image thresholds of the timed batch); `dense` = the same "
-                             'K steps with the skipping switched off, nominal FLOPs',
-            'avg_launch_ms': conv_ms / max(conv_launches, 1),
-            'launches': conv_launches,
-            'ms_per_step': conv_ms / args.steps,
-            'timing': 'HIP event pair per launch, instrumented pass of the same K steps',
-        },
-        'roofline_encoder': {
-            'kernel': 'encode_items_kernel',
-            'bound': 'hbm',
-            'achieved': enc_gbs,
-            'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s',
-            'frac': enc_gbs / HBM_PEAK_GBS,
-            'traffic': enc_traffic,
-            'bytes_per_candidate': bytes_per_item,
-            'avg_launch_ms': enc_ms / max(enc_launches, 1),
-            'launches': enc_launches,
-            'candidates_per_s': (n_items * args.steps / (enc_ms * 1e-3)
-                                 if enc_ms > 0 else 0.0),
-        },
-        'other_kernels_ms_per_step': other_ms / args.steps,
     }
+    if args.full:
+      conv_flops_per_item = 2.0 * model.conv_macs_per_example
+      executed = executed_conv_flops(model, (H, W, C), thr, conv_flops_per_item) if thr is not None else None
+      exec_flops_per_item = executed['executed_flops_per_candidate'] if executed else conv_flops_per_item
+      conv_tflops = (exec_flops_per_item * n_items * args.steps /
+                     (conv_ms * 1e-3) / 1e12) if conv_ms > 0 else 0.0
+      bytes_per_item = algorithmic_bytes_per_item(host_batch, C)
+      enc_gbs = (bytes_per_item * n_items * args.steps / (enc_ms * 1e-3) / 1e9
+                 if enc_ms > 0 else 0.0)
+      conv_traffic, enc_traffic, traffic_note = pmc_traffic(args, n_items) if world == 1 else (None, None, None)
+      out['roofline'] = {
+          'kernel': 'conv kernels: stem_a/stem_b (fused stem), chain_kernel (fused 1x7/7x1 chains), '
+                    'imgconv_kernel, conv_mfma_kernel<NB,PT>, conv_resident_kernel (all 94 conv layers)',
+          'bound': 'mfma',
+          'achieved': conv_tflops,
+          'peak': MFMA_F16_PEAK_TFLOPS,
+          'unit': 'TFLOP/s',
+          'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS,
+          'traffic': conv_traffic,
+          'traffic_note': traffic_note,
+          'flops_per_candidate': conv_flops_per_item,
+          'executed_flops_per_candidate': exec_flops_per_item,
+          'achieved_note': '`achieved` / `frac` count EXECUTED MFMA FLOPs: the nominal 2 x MACs of the 94 layers minus '
+                           'the output tiles blank-row skipping copied instead of computing (mirrored on the host from '
+                           "the kernels' tile rules and the per-image thresholds of the timed batch); `dense` = the same "
+                           'K steps with the skipping switched off, nominal FLOPs',
+          'avg_launch_ms': conv_ms / max(conv_launches, 1),
+          'launches': conv_launches,
+          'ms_per_step': conv_ms / args.steps,
+          'timing': 'HIP event pair per launch, instrumented pass of the same K steps',
+      }
+      out['roofline_encoder'] = {
+          'kernel': 'encode_items_kernel',
+          'bound': 'hbm',
+          'achieved': enc_gbs,
+          'peak': HBM_PEAK_GBS,
+          'unit': 'GB/s',
+          'frac': enc_gbs / HBM_PEAK_GBS,
+          'traffic': enc_traffic,
+          'bytes_per_candidate': bytes_per_item,
+          'avg_launch_ms': enc_ms / max(enc_launches, 1),
+          'launches': enc_launches,
+          'candidates_per_s': (n_items * args.steps / (enc_ms * 1e-3)
+                               if enc_ms > 0 else 0.0),
+      }
+      out['other_kernels_ms_per_step'] = other_ms / args.steps
     out['calibration'] = calibration
     if dense is not None:
       elapsed_d, conv_ms_d = dense
@@ -426,22 +442,25 @@ def run_rank(args, rank, local_rank, world):
           'stem tiles whose receptive field holds only the zero rows below the pile-up are copied from the all-blank '
           "image's response (bit-identical; include/dvhip.h dv_model_set_blank_skip); `value` is the product's default, "
           '`value_dense` the same steps with it off'))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(host_batch, opts, C, args.cpu_sample)
       out['parity'] = parity_sample(region, opts, C, model, images, probs, n=args.parity_sites)
       out['parity'].update(cnn_tail_parity(model, C, images, probs))
-    if world == 1 and not args.no_workloads:
+    if world == 1 and not args.no_workloads and (args.full or dump is not None):
       # BASELINE configs[3], configs[4]: the long-read shapes, timed after the headline with the same
-      # K / W, attached to the ONE line (the headline `value` / `config` stay ILLUMINA30)
-      out['workloads'] = {}
+      # K / W, attached to the ONE line under --full (the headline `value` / `config` stay ILLUMINA30); a plain run
+      # with --dump-outputs times their steps for the arrays only
+      if args.full:
+        out['workloads'] = {}
       for w in ('hifi35', 'ont50'):
         sub = argparse.Namespace(**vars(args))
         sub.workload = w
-        full = longread_bench(sub, dev, local_rank, emit=False, dump=dump)
-        out['workloads'][w] = {k: full[k] for k in ('metric', 'value', 'value_dense', 'unit', 'ms_per_step',
-                                                    'ms_per_step_dense', 'config', 'roofline', 'roofline_encoder',
-                                                    'other_kernels_ms_per_step', 'calibration', 'blank_row_skipping',
-                                                    'parity', 'precise', 'fast') if k in full}
+        line = longread_bench(sub, dev, local_rank, emit=False, dump=dump)
+        if args.full:
+          out['workloads'][w] = {k: line[k] for k in ('metric', 'value', 'value_dense', 'unit', 'ms_per_step',
+                                                      'ms_per_step_dense', 'config', 'roofline', 'roofline_encoder',
+                                                      'other_kernels_ms_per_step', 'calibration', 'blank_row_skipping',
+                                                      'parity', 'precise', 'fast') if k in line}
     if dump is not None:
       write_outputs(args.dump_outputs, dump)
     print(json.dumps(out))
@@ -900,18 +919,19 @@ def longread_bench(args, dev, local_rank, emit=True, dump=None):
   elapsed, probs = timed_steps(step, sync_all, args.warmup, args.steps)
   if dump is not None:
     dump.update(snapshot_outputs(args.workload, probs, images))
-  lib.dv_set_profiling(1)
-  for _ in range(args.steps):
-    step()
-  sync_all()
-  enc_ms = lib.dv_profile_ms(0)
-  enc_launches = lib.dv_last_profile_count()
-  conv_ms = lib.dv_profile_ms(1)
-  conv_launches = lib.dv_last_profile_count()
-  other_ms = lib.dv_profile_ms(2)
-  lib.dv_set_profiling(0)
+  if args.full:
+    lib.dv_set_profiling(1)
+    for _ in range(args.steps):
+      step()
+    sync_all()
+    enc_ms = lib.dv_profile_ms(0)
+    enc_launches = lib.dv_last_profile_count()
+    conv_ms = lib.dv_profile_ms(1)
+    conv_launches = lib.dv_last_profile_count()
+    other_ms = lib.dv_profile_ms(2)
+    lib.dv_set_profiling(0)
   assert torch.isfinite(probs).all()
-  thr = model.blank_thresholds(n)
+  thr = model.blank_thresholds(n) if args.full else None
   dense = None
   if thr is not None and not args.no_dense:      # the same K steps with blank-row skipping off (identical probabilities)
     model.set_blank_skip(False)
@@ -926,18 +946,9 @@ def longread_bench(args, dev, local_rank, emit=True, dump=None):
     lib.dv_set_profiling(0)
     model.set_blank_skip(True)
     dense = (elapsed_d, conv_ms_d)
-  conv_flops = 2.0 * model.conv_macs_per_example
-  executed = executed_conv_flops(model, (H, W, Ct), thr, conv_flops) if thr is not None else None
-  exec_flops = executed['executed_flops_per_candidate'] if executed else conv_flops
-  conv_tflops = exec_flops * n * args.steps / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-  # algorithmic bytes: every image's packed reads once per alignment drawn + the n example tensors
   t = batch.table
   seq_len = t.read_seq_off[1:].astype(np.int64) - t.read_seq_off[:-1]
   n_cig = t.read_cigar_off[1:].astype(np.int64) - t.read_cigar_off[:-1]
-  per_read = 2 * seq_len + 8 * n_cig + 24 + 1
-  in_bytes = float(per_read[np.asarray(batch.list_read, np.int64)].sum()) + n_images * W
-  alg_bytes = in_bytes + float(n) * img_bytes
-  enc_gbs = alg_bytes * args.steps / (enc_ms * 1e-3) / 1e9 if enc_ms > 0 else 0.0
   out = {
       'metric': 'candidate pileups/sec (encode+CNN), %s' % args.workload,
       'value': n * args.steps / elapsed, 'unit': 'candidates/s', 'n_gpus': 1, 'steps': args.steps,
@@ -954,23 +965,33 @@ def longread_bench(args, dev, local_rank, emit=True, dump=None):
           'reads_per_step': int(t.n_reads), 'cigar_ops_per_read': float(n_cig.mean()),
           'reads_listed_per_image': float(len(batch.list_read)) / n_images,
       },
-      'roofline': {
-          'kernel': 'conv kernels (all 94 conv layers; inputs with more than 8 channels take preprocess_kernel + '
-                    'the per-layer stem instead of the fused uint8 stem)',
-          'bound': 'mfma', 'achieved': conv_tflops, 'peak': MFMA_F16_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-          'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS, 'traffic': None, 'flops_per_candidate': conv_flops,
-          'executed_flops_per_candidate': exec_flops,
-          'avg_launch_ms': conv_ms / max(conv_launches, 1), 'launches': conv_launches,
-          'ms_per_step': conv_ms / args.steps,
-      },
-      'roofline_encoder': {
-          'kernel': 'encode_items_kernel', 'bound': 'hbm', 'achieved': enc_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-          'frac': enc_gbs / HBM_PEAK_GBS, 'traffic': None, 'bytes_per_candidate': alg_bytes / n,
-          'avg_launch_ms': enc_ms / max(enc_launches, 1), 'launches': enc_launches,
-          'images_per_s': n_images * args.steps / (enc_ms * 1e-3) if enc_ms > 0 else 0.0,
-      },
-      'other_kernels_ms_per_step': other_ms / args.steps,
   }
+  if args.full:
+    conv_flops = 2.0 * model.conv_macs_per_example
+    executed = executed_conv_flops(model, (H, W, Ct), thr, conv_flops) if thr is not None else None
+    exec_flops = executed['executed_flops_per_candidate'] if executed else conv_flops
+    conv_tflops = exec_flops * n * args.steps / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+    # algorithmic bytes: every image's packed reads once per alignment drawn + the n example tensors
+    per_read = 2 * seq_len + 8 * n_cig + 24 + 1
+    in_bytes = float(per_read[np.asarray(batch.list_read, np.int64)].sum()) + n_images * W
+    alg_bytes = in_bytes + float(n) * img_bytes
+    enc_gbs = alg_bytes * args.steps / (enc_ms * 1e-3) / 1e9 if enc_ms > 0 else 0.0
+    out['roofline'] = {
+        'kernel': 'conv kernels (all 94 conv layers; inputs with more than 8 channels take preprocess_kernel + '
+                  'the per-layer stem instead of the fused uint8 stem)',
+        'bound': 'mfma', 'achieved': conv_tflops, 'peak': MFMA_F16_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+        'frac': conv_tflops / MFMA_F16_PEAK_TFLOPS, 'traffic': None, 'flops_per_candidate': conv_flops,
+        'executed_flops_per_candidate': exec_flops,
+        'avg_launch_ms': conv_ms / max(conv_launches, 1), 'launches': conv_launches,
+        'ms_per_step': conv_ms / args.steps,
+    }
+    out['roofline_encoder'] = {
+        'kernel': 'encode_items_kernel', 'bound': 'hbm', 'achieved': enc_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+        'frac': enc_gbs / HBM_PEAK_GBS, 'traffic': None, 'bytes_per_candidate': alg_bytes / n,
+        'avg_launch_ms': enc_ms / max(enc_launches, 1), 'launches': enc_launches,
+        'images_per_s': n_images * args.steps / (enc_ms * 1e-3) if enc_ms > 0 else 0.0,
+    }
+    out['other_kernels_ms_per_step'] = other_ms / args.steps
   out['calibration'] = calibration
   out['precise'] = bool(model.precise)
   out['config']['classifier_mode'] = (
@@ -985,10 +1006,10 @@ def longread_bench(args, dev, local_rank, emit=True, dump=None):
     out['roofline']['dense'] = {'achieved': dense_tflops, 'frac': dense_tflops / MFMA_F16_PEAK_TFLOPS,
                                 'ms_per_step': conv_ms_d / args.steps, 'flops_per_candidate': conv_flops}
     out['blank_row_skipping'] = executed
-  if not args.no_cpu_baseline:
+  if args.full and not args.no_cpu_baseline:
     out['parity'] = longread_parity(opts, batch, n, with_alt, Ct, c_enc, model, images, probs)
     out['parity'].update(cnn_tail_parity(model, Ct, images, probs))
-  if model.precise and not args.no_dense:
+  if args.full and model.precise and not args.no_dense:
     # the same steps in fast mode (DV_PRECISE=0: fp16 activations everywhere) on a second model of the same weights
     flat_weights = model.flat_weights
     del model
@@ -1208,8 +1229,8 @@ def _pmc_pass(counter, args, timeout_s=300):
   try:
     env = dict(os.environ, TMPDIR='/tmp', DV_BENCH_NO_PMC='1')
     cmd = ['rocprofv3', '--kernel-trace', '--pmc', counter, '-d', out, '--', sys.executable,
-           os.path.abspath(__file__), '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-workloads', '--no-dense',
-           '--calibration-images', '0', '--batch', str(args.batch), '--channels', str(args.channels)]
+           os.path.abspath(__file__), '--full', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-workloads',
+           '--no-dense', '--calibration-images', '0', '--batch', str(args.batch), '--channels', str(args.channels)]
     subprocess.run(cmd, cwd='/tmp', env=env, timeout=timeout_s, check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     dbs = glob.glob(os.path.join(out, '**', '*.db'), recursive=True)

@@ -1,7 +1,8 @@
-mkdir -p gpurun_out/r2ab
+OUT=${OUT:-out}   # output folder
+mkdir -p $OUT/r2ab
 run() { # label, env...
   label=$1; shift
-  env "$@" python bench.py --steps 15 --warmup 3 --no-cpu-baseline 2> gpurun_out/r2ab/$label.err | python -c "
+  env "$@" python bench.py --full --steps 15 --warmup 3 --no-cpu-baseline 2> $OUT/r2ab/$label.err | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$label', round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['ms_per_step'],3), round(d['other_kernels_ms_per_step'],3))"
 }

@@ -5,12 +5,13 @@
 #   ablX      no pixel-operand buffer_loads in the K loop        ablW    no weight ds_reads per chunk
 #   ablXW     neither (MFMAs + loop control + slab copy only)     ablLOOP no K loop at all (prologue + epilogue)
 #   ablEPI    no output stores                                    ablLOOPEPI  prologue only
-mkdir -p gpurun_out/abl
-DV_OP_TRACE=1 timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> gpurun_out/abl/base.txt
+OUT=${OUT:-out}   # output folder
+mkdir -p $OUT/abl
+DV_OP_TRACE=1 timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/abl/base.txt
 V="ablX ablW ablXW ablLOOP ablEPI ablLOOPEPI"
 for v in $V; do
   [ -f build_variants/libdvhip_$v.so ] || continue
-  DV_LIB_PATH=$PWD/build_variants/libdvhip_$v.so DV_OP_TRACE=1 timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> gpurun_out/abl/$v.txt
+  DV_LIB_PATH=$PWD/build_variants/libdvhip_$v.so DV_OP_TRACE=1 timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/abl/$v.txt
 done
-python tools/compare_traces.py gpurun_out/abl/base.txt $(for v in $V; do [ -f gpurun_out/abl/$v.txt ] && echo gpurun_out/abl/$v.txt; done) --all > gpurun_out/abl/cmp.txt
-grep -E "^op|conv |total" gpurun_out/abl/cmp.txt | grep -v imgconv
+python tools/compare_traces.py $OUT/abl/base.txt $(for v in $V; do [ -f $OUT/abl/$v.txt ] && echo $OUT/abl/$v.txt; done) --all > $OUT/abl/cmp.txt
+grep -E "^op|conv |total" $OUT/abl/cmp.txt | grep -v imgconv

@@ -15,7 +15,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_
            "SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM SQ_INSTS_LDS SQ_INSTS_VALU" \
            "TA_TA_BUSY_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout 400 rocprofv3 --kernel-trace --pmc $set -d $O/pmc$i -- python $R/bench.py --workload $W --steps 1 --warmup 1 --no-cpu-baseline --no-workloads --no-dense --calibration-images 0 > $O/pmc$i.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $set -d $O/pmc$i -- python $R/bench.py --full --workload $W --steps 1 --warmup 1 --no-cpu-baseline --no-workloads --no-dense --calibration-images 0 > $O/pmc$i.log 2>&1
   python $R/profiles/summarize_pmc.py $(find $O/pmc$i -name '*.db' | head -1) >> $O/pmc_sq$SUF.raw 2>&1
   rm -rf $O/pmc$i
 done
