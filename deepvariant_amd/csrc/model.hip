@@ -46,6 +46,7 @@
 #include "chain.h"
 #include "stem_fused.h"
 #include "calib.h"
+#include "layer_export.h"
 
 using namespace dv::convk;
 
@@ -1426,10 +1427,11 @@ __global__ void avgpool3s1_kernel(PoolArgs p) {
 
 // GlobalAveragePooling2D + Dense(num_classes) + softmax, fp32.  Round 6: the last block's outputs arrive in
 // float32 (BufferDesc::f32) -- the values the convolutions' accumulators held, not an fp16 copy of them.
-__global__ __launch_bounds__(256) void head_kernel(const float* in, const float* w,
-                                                   const float* b, const ExtPtrs* ext, size_t probs_off,
-                                                   TensorGeom g, int K) {
-  float* probs = ext->probs + probs_off;
+// OUT (head_outputs_kernel, dv_model_infer_outputs): also stores the pooled vector ([C] per example) and the logits
+// ([K]) where they are computed -- the same arithmetic in the same order, so the probabilities are the plain head's.
+template <bool OUT>
+__device__ __forceinline__ void head_body(const float* in, const float* w, const float* b, float* probs, TensorGeom g,
+                                          int K, float* pooled, float* logits) {
   __shared__ float red[8][4];
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
@@ -1451,6 +1453,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* in, const float*
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float m = s[j] * invP;
+      if (OUT && pooled != nullptr) pooled[static_cast<size_t>(n) * C + grp * 8 + j] = m;
       for (int k = 0; k < K; ++k) part[k] += m * w[static_cast<size_t>(grp * 8 + j) * K + k];
     }
   }
@@ -1464,6 +1467,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* in, const float*
     float logit[8], mx = -1e30f;
     for (int k = 0; k < K; ++k) {
       logit[k] = red[k][0] + red[k][1] + red[k][2] + red[k][3] + b[k];
+      if (OUT && logits != nullptr) logits[static_cast<size_t>(n) * K + k] = logit[k];
       mx = fmaxf(mx, logit[k]);
     }
     float sum = 0.f;
@@ -1473,6 +1477,19 @@ __global__ __launch_bounds__(256) void head_kernel(const float* in, const float*
     }
     for (int k = 0; k < K; ++k) probs[static_cast<size_t>(n) * K + k] = logit[k] / sum;
   }
+}
+
+__global__ __launch_bounds__(256) void head_kernel(const float* in, const float* w,
+                                                   const float* b, const ExtPtrs* ext, size_t probs_off,
+                                                   TensorGeom g, int K) {
+  head_body<false>(in, w, b, ext->probs + probs_off, g, K, nullptr, nullptr);
+}
+
+// pooled / logits: [examples][C] / [examples][K] destinations for this launch's examples; either may be null
+__global__ __launch_bounds__(256) void head_outputs_kernel(const float* in, const float* w, const float* b,
+                                                           const ExtPtrs* ext, size_t probs_off, TensorGeom g, int K,
+                                                           float* pooled, float* logits) {
+  head_body<true>(in, w, b, ext->probs + probs_off, g, K, pooled, logits);
 }
 
 // ------------------------------------------------------------------ the graph
@@ -1600,6 +1617,16 @@ struct dv_model {
   };
   std::vector<GraphEntry> graphs;  // captured forwards, see dv_model_infer
   int64_t graph_captures = 0, graph_replays = 0;
+  // dv_model_infer_outputs: the concat outputs Keras InceptionV3 names (mixed0 .. mixed10, and mixed9_0 / mixed9_1 =
+  // the 3x3-split concats inside mixed9 and mixed10), in Keras' construction order, as (buffer, first channel,
+  // channels).  Each block's output is a buffer of its own at full batch width (only the stem's tensors are
+  // sub-batched), written by its own block's ops alone: after a forward of at most max_batch examples every one of
+  // them still holds that forward's values.
+  struct NamedView {
+    std::string name;
+    int buf, coff, c;
+  };
+  std::vector<NamedView> named_views;
 
   // ---- builder ------------------------------------------------------------
   int new_buffer(int h, int w, int c) {
@@ -2229,6 +2256,7 @@ struct dv_model {
       b3 = conv(b3, 96, 3, 3);
       conv(b3, 96, 3, 3, 1, true, out, 128);
       pooled_projection(x, pool_ch, out, 224);
+      named_views.push_back({"mixed" + std::to_string(named_views.size()), out, 0, buffers[out].c});
       if (fuse_pool2 && !pool_in_conv && x.buf == stem_out_buf) {  // mixed0: its 1x1 heads pool their input
         for (size_t k = stem_ops_end; k < ops.size(); ++k) {
           if (ops[k].type == kOpConv && ops[k].in_buf == x.buf) {
@@ -2248,6 +2276,7 @@ struct dv_model {
       b = conv(b, 96, 3, 3);
       conv(b, 96, 3, 3, 2, false, out, 384);
       pool(kOpMaxPool, x, out, 480);
+      named_views.push_back({"mixed3", out, 0, buffers[out].c});
       x = full(out);
     }
     wide_stage = true;   // precise mode: the tensors created from here on (17x17 and 8x8 stages) are hi + lo
@@ -2263,6 +2292,7 @@ struct dv_model {
       d = conv(d, c7, 7, 1);
       conv(d, 192, 1, 7, 1, true, out, 384);
       pooled_projection(x, 192, out, 576);
+      named_views.push_back({"mixed" + std::to_string(named_views.size()), out, 0, buffers[out].c});
       x = full(out);
     }
     {  // mixed8
@@ -2275,6 +2305,7 @@ struct dv_model {
       d = conv(d, 192, 7, 1);
       conv(d, 192, 3, 3, 2, false, out, 320);
       pool(kOpMaxPool, x, out, 512);
+      named_views.push_back({"mixed8", out, 0, buffers[out].c});
       x = full(out);
     }
     for (int i = 0; i < 2; ++i) {  // mixed9, mixed10
@@ -2283,11 +2314,13 @@ struct dv_model {
       TensorRef b = conv(x, 384, 1, 1);
       conv(b, 384, 1, 3, 1, true, out, 320);
       conv(b, 384, 3, 1, 1, true, out, 704);
+      named_views.push_back({"mixed9_" + std::to_string(i), out, 320, 2 * 384});   // Keras' concat of these two
       TensorRef d = conv(x, 448, 1, 1);
       d = conv(d, 384, 3, 3);
       conv(d, 384, 1, 3, 1, true, out, 1088);
       conv(d, 384, 3, 1, 1, true, out, 1472);
       pooled_projection(x, 192, out, 1856);
+      named_views.push_back({"mixed" + std::to_string(9 + i), out, 0, buffers[out].c});
       x = full(out);
     }
     feat_buf = x.buf;
@@ -3185,7 +3218,11 @@ int dv_model_layer_info(const dv_model* m, int layer, int32_t* kh, int32_t* kw,
   return DV_OK;
 }
 
-static int enqueue_forward(dv_model* m, int n, hipStream_t stream);
+struct HeadOutputs {   // dv_model_infer_outputs: where the head also stores the pooled vector / the logits (or null)
+  float* pooled;
+  float* logits;
+};
+static int enqueue_forward(dv_model* m, int n, hipStream_t stream, const HeadOutputs* head_out = nullptr);
 static void set_ext(dv_model* m, const uint8_t* images, float* probs, hipStream_t stream,
                     const int32_t* rows_hint = nullptr, int rows_add = 0) {
   hipLaunchKernelGGL(set_ext_kernel, dim3(1), dim3(1), 0, stream, static_cast<ExtPtrs*>(m->d_ext.ptr), images, probs,
@@ -3662,7 +3699,8 @@ int dv_model_debug_tensor(dv_model* m, int index, int n, void* host_out, int32_t
 
 // Enqueues the whole forward for `n` examples on `stream` (eager launches).  The caller's image
 // and probability pointers come from the device-side table (set_ext), not from kernel arguments.
-static int enqueue_forward(dv_model* m, int n, hipStream_t stream) {
+// `head_out`: head_outputs_kernel instead of head_kernel.
+static int enqueue_forward(dv_model* m, int n, hipStream_t stream, const HeadOutputs* head_out) {
   const size_t img_bytes = static_cast<size_t>(m->desc.height) * m->desc.width * m->desc.channels;
   const ExtPtrs* ext = static_cast<const ExtPtrs*>(m->d_ext.ptr);
   // split evenly so that no launch is left with a sliver of a batch
@@ -3699,12 +3737,24 @@ static int enqueue_forward(dv_model* m, int n, hipStream_t stream) {
     }
     {
       dv::ProfileScope prof(dv::kProfOther, stream);
-      hipLaunchKernelGGL(head_kernel, dim3(nb), dim3(256), 0, stream,
-                         static_cast<const float*>(m->dbuf[m->feat_buf].ptr),
-                         static_cast<const float*>(m->d_dense_w.ptr),
-                         static_cast<const float*>(m->d_dense_b.ptr), ext,
-                         static_cast<size_t>(done) * m->desc.num_classes,
-                         m->buffers[m->feat_buf].geom(), m->desc.num_classes);
+      if (head_out != nullptr) {
+        hipLaunchKernelGGL(head_outputs_kernel, dim3(nb), dim3(256), 0, stream,
+                           static_cast<const float*>(m->dbuf[m->feat_buf].ptr),
+                           static_cast<const float*>(m->d_dense_w.ptr),
+                           static_cast<const float*>(m->d_dense_b.ptr), ext,
+                           static_cast<size_t>(done) * m->desc.num_classes,
+                           m->buffers[m->feat_buf].geom(), m->desc.num_classes,
+                           head_out->pooled ? head_out->pooled + static_cast<size_t>(done) * m->feat_c : nullptr,
+                           head_out->logits ? head_out->logits + static_cast<size_t>(done) * m->desc.num_classes
+                                            : nullptr);
+      } else {
+        hipLaunchKernelGGL(head_kernel, dim3(nb), dim3(256), 0, stream,
+                           static_cast<const float*>(m->dbuf[m->feat_buf].ptr),
+                           static_cast<const float*>(m->d_dense_w.ptr),
+                           static_cast<const float*>(m->d_dense_b.ptr), ext,
+                           static_cast<size_t>(done) * m->desc.num_classes,
+                           m->buffers[m->feat_buf].geom(), m->desc.num_classes);
+      }
     }
   }
   return DV_OK;
@@ -3810,6 +3860,109 @@ int dv_model_blank_thresholds(dv_model* m, int n, int32_t* out) {
                            static_cast<const int*>(m->d_blank_thr.ptr) + static_cast<size_t>(k) * m->desc.max_batch,
                            static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToHost));
   }
+  return DV_OK;
+}
+
+// dv_model_infer_outputs' names: the block outputs of named_views, then the head's two vectors.
+namespace {
+struct OutputView {
+  int buf = -1;            // named_views' buffer, or -1: a head output
+  int coff = 0, c = 0;     // channel range
+  int h = 1, w = 1;
+  bool logits = false;     // head output: the logits (else the pooled vector)
+};
+}  // namespace
+
+static int resolve_output(const dv_model* m, const char* name, OutputView* v, const char* fn) {
+  const std::string s = name != nullptr ? name : "";
+  std::string known;
+  for (const dv_model::NamedView& nv : m->named_views) {
+    if (s == nv.name) {
+      const BufferDesc& b = m->buffers[nv.buf];
+      *v = OutputView{nv.buf, nv.coff, nv.c, b.h, b.w, false};
+      return DV_OK;
+    }
+    known += nv.name + ", ";
+  }
+  if (s == "prelogits") {
+    *v = OutputView{-1, 0, m->feat_c, 1, 1, false};
+    return DV_OK;
+  }
+  if (s == "logits") {
+    *v = OutputView{-1, 0, m->desc.num_classes, 1, 1, true};
+    return DV_OK;
+  }
+  return dv::fail(DV_ERR_INVALID_ARGUMENT, std::string(fn) + ": unknown output name '" + s + "' (accepted: " + known +
+                                               "prelogits, logits)");
+}
+
+int dv_model_output_info(const dv_model* m, const char* name, int32_t* h, int32_t* w, int32_t* c) {
+  if (!m) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_model_output_info: null");
+  OutputView v;
+  if (int rc = resolve_output(m, name, &v, "dv_model_output_info")) return rc;
+  if (h) *h = v.h;
+  if (w) *w = v.w;
+  if (c) *c = v.c;
+  return DV_OK;
+}
+
+// One forward of at most max_batch examples with eager launches (never captured: the plain forward's graphs stay as
+// they are), the head that also stores its two vectors, then one export launch per requested block output -- every
+// block output is still live at the end of the forward (dv_model::named_views).
+int dv_model_infer_outputs(dv_model* m, const uint8_t* images, int n, float* probs, int n_outputs,
+                           const char* const* names, float* const* outs, void* stream_v) {
+  if (!m || !images || !probs || n < 0 || n_outputs < 0 || (n_outputs > 0 && (!names || !outs))) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_model_infer_outputs: bad argument");
+  }
+  if (n > m->desc.max_batch) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_model_infer_outputs: n = " + std::to_string(n) + " is above max_batch = " +
+                                                 std::to_string(m->desc.max_batch));
+  }
+  if (!m->loaded) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_model_infer_outputs: no weights loaded");
+  std::vector<OutputView> views(n_outputs);
+  HeadOutputs head{nullptr, nullptr};
+  for (int k = 0; k < n_outputs; ++k) {
+    if (int rc = resolve_output(m, names[k], &views[k], "dv_model_infer_outputs")) return rc;
+    if (outs[k] == nullptr || reinterpret_cast<uintptr_t>(outs[k]) % 16 != 0) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, std::string("dv_model_infer_outputs: the output for '") + names[k] +
+                                                   "' is null or not 16-byte aligned");
+    }
+    for (int j = 0; j < k; ++j) {
+      if (std::strcmp(names[j], names[k]) == 0) {
+        return dv::fail(DV_ERR_INVALID_ARGUMENT, std::string("dv_model_infer_outputs: '") + names[k] + "' requested twice");
+      }
+    }
+    if (views[k].buf < 0) (views[k].logits ? head.logits : head.pooled) = outs[k];
+  }
+  if (n_outputs == 0) return dv_model_infer(m, images, n, probs, stream_v);
+  if (n == 0) return DV_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  DV_HIP_CHECK(hipSetDevice(m->device));
+  set_ext(m, images, probs, stream);
+  if (int rc = enqueue_forward(m, n, stream, &head)) return rc;
+  for (int k = 0; k < n_outputs; ++k) {
+    const OutputView& v = views[k];
+    if (v.buf < 0) continue;
+    const BufferDesc& b = m->buffers[v.buf];
+    const TensorGeom g = b.geom();
+    dv::LayerExportArgs a{};
+    a.src = m->dbuf[v.buf].ptr;
+    a.kind = b.f32 ? dv::kExportF32 : b.wide ? dv::kExportWide : dv::kExportF16;
+    a.n = n;
+    a.h = g.h;
+    a.w = g.w;
+    a.halo = g.halo;
+    a.hp = g.hp;
+    a.wp = g.wp;
+    a.src_groups = g.groups;
+    a.lo_groups = b.c / 8;
+    a.goff = v.coff / 8;
+    a.groups = v.c / 8;
+    a.dst = outs[k];
+    dv::ProfileScope prof(dv::kProfOther, stream);
+    dv::launch_layer_export(a, stream);
+  }
+  DV_HIP_CHECK(hipGetLastError());
   return DV_OK;
 }
 

@@ -9,7 +9,7 @@ genotype probabilities.  PyTorch only owns device memory and the stream.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -203,6 +203,37 @@ class InceptionV3(torch.nn.Module):
           self._handle, images.data_ptr(), n, out.data_ptr(),
           C.c_void_p(stream)))
     return out.clone()
+
+  def output_info(self, name: str) -> Tuple[int, int, int]:
+    """(h, w, c) of one example of the named output (dv_model_output_info): mixed0 .. mixed10, mixed9_0, mixed9_1,
+    prelogits, logits."""
+    h, w, c = C.c_int32(), C.c_int32(), C.c_int32()
+    _lib.check(_lib.lib().dv_model_output_info(self._handle, name.encode(), C.byref(h), C.byref(w), C.byref(c)))
+    return h.value, w.value, c.value
+
+  def forward_outputs(self, images: torch.Tensor, names: Sequence[str]) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """forward() and the named intermediate outputs of the same pass (dv_model_infer_outputs; at most max_batch
+    images): (probs [N, num_classes], {name: CUDA float32 tensor}) -- NHWC [N, h, w, c] for the mixed blocks,
+    [N, 2048] for prelogits, [N, num_classes] for logits.  The probabilities equal forward()'s bit for bit."""
+    if images.dtype != torch.uint8 or not images.is_cuda:
+      raise ValueError('images must be a CUDA uint8 tensor [N, H, W, C]')
+    if tuple(images.shape[1:]) != self.input_shape:
+      raise ValueError('input shape %s != model shape %s' % (tuple(images.shape[1:]), self.input_shape))
+    images = images.contiguous()
+    n = images.shape[0]
+    names = list(names)
+    probs = torch.empty((n, self.num_classes), dtype=torch.float32, device=images.device)
+    outs = {}
+    for name in names:
+      h, w, c = self.output_info(name)
+      shape = (n, c) if name in ('prelogits', 'logits') else (n, h, w, c)
+      outs[name] = torch.empty(shape, dtype=torch.float32, device=images.device)
+    c_names = (C.c_char_p * max(1, len(names)))(*[s.encode() for s in names])
+    c_outs = (C.c_void_p * max(1, len(names)))(*[outs[s].data_ptr() for s in names])
+    stream = torch.cuda.current_stream(images.device).cuda_stream
+    _lib.check(_lib.lib().dv_model_infer_outputs(self._handle, images.data_ptr(), n, probs.data_ptr(), len(names),
+                                                 c_names, c_outs, C.c_void_p(stream)))
+    return probs, outs
 
   def set_blank_skip(self, enabled: bool) -> None:
     """dv_model_set_blank_skip: False runs the dense stem (same probabilities, bit for bit)."""

@@ -898,6 +898,24 @@ int dv_model_blank_thresholds(dv_model* m, int n, int32_t* out);
 int dv_model_infer_rows(dv_model* m, const uint8_t* images, int n, float* probs, const int32_t* rows_used,
                         int rows_add, void* stream);
 
+/* Intermediate outputs (ABI v8 addition), for integrators of the reference's call_variants --include_debug_info /
+ * --activation_layers and for tracing a difference from another implementation to one Inception block.  Names:
+ *   mixed0 .. mixed10     Keras InceptionV3's named concat outputs, [h][w][c] per example
+ *   mixed9_0, mixed9_1    the 3x3-split concats inside mixed9 and mixed10 (channels 320 .. 1087 of those blocks)
+ *   prelogits             the global-average-pooled vector the Dense layer reads, [1][1][2048]
+ *   logits                the Dense output before softmax, [1][1][num_classes]
+ * Any other name (the unnamed conv2d_N / activation_N layers among them) is DV_ERR_INVALID_ARGUMENT, with the accepted
+ * names in dv_last_error.
+ * dv_model_output_info: the shape of one example of `name` for this model's input shape.
+ * dv_model_infer_outputs: dv_model_infer (the same probabilities, bit for bit: blank-row skipping, calibration and
+ * precise mode as there) for n <= max_batch examples, and in addition for every k < n_outputs the DEVICE array
+ * outs[k], 16-byte aligned, receives float32 [n][h][w][c] of names[k] (NHWC).  Each name at most once; n above
+ * max_batch, a null or misaligned output, an unknown or empty name: DV_ERR_INVALID_ARGUMENT.  n_outputs = 0 is
+ * dv_model_infer.  The forward runs with plain launches; the hipGraphs of dv_model_infer are not touched. */
+int dv_model_output_info(const dv_model* m, const char* name, int32_t* h, int32_t* w, int32_t* c);
+int dv_model_infer_outputs(dv_model* m, const uint8_t* images, int n, float* probs, int n_outputs,
+                           const char* const* names, float* const* outs, void* stream);
+
 /* On a non-default stream the forward is captured once per (n, stream) into a hipGraph and
  * replayed; the image / probability pointers are read from a device-side table, so they may
  * change from call to call without a new capture.  Testing hook: captures and replays so far. */
