@@ -181,7 +181,7 @@ __device__ __forceinline__ void b35_compute(const Block35Args& p, char* smem, in
     const float* src = j < SH_RED3 ? p.sh_red5 + (j - SH_RED5) : j < SH_B1 ? p.sh_red3 + (j - SH_RED3)
                      : j < SH_POOL ? p.sh_b1 + (j - SH_B1) : j < SH_5 ? p.sh_pool + (j - SH_POOL)
                      : j < SH_3A ? p.sh5 + (j - SH_5) : j < SH_3B ? p.sh3a + (j - SH_3A) : p.sh3b + (j - SH_3B);
-    // every shift array is padded past its couts (model.hip: cout + 128 floats)
+    // every shift array is padded past its couts (model_graph.cpp dv_model::conv: cout + 128 floats)
     reinterpret_cast<float*>(smem + SH_OFF)[j] = *src;
   }
   const unsigned one[2] = {1u, 1u};

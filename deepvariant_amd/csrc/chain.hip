@@ -26,7 +26,7 @@
 // 256 pixels: one or two maps in a 256-pixel tile, waves = 4 pixel quarters x all <= 96 couts,
 // 3x3 / 5x5 filters: the 3x3 -> 3x3 branch of mixed0..2 and the 5x5 layers).
 // The K order (channel chunk major, tap minor), the fp32 accumulation, the fp16 rounding of
-// every intermediate and the shift + ReLU are those of the per-layer kernels (model.hip), and
+// every intermediate and the shift + ReLU are those of the per-layer kernels (conv_mfma.hip), and
 // skipped taps only ever multiply zeros: results are bit-identical to the per-layer path
 // (tests/test_hip_chain.py).
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the convolution kernels of libdvhip.so (model.hip,
+// Device-side pieces shared by the convolution kernels of libdvhip.so (conv_mfma.hip,
 // imgconv.hip): the C8 activation geometry, the launch arguments and the epilogue
 // that turns MFMA accumulators into 16-byte pieces of the output tensor(s).
 #ifndef DV_CONV_COMMON_H_
@@ -39,7 +39,7 @@ struct ConvBranch {
                           // projections awaiting their average pool, the last block's outputs awaiting the global pool:
                           // tensors no MFMA reads are not rounded to fp16 on the way (round 6)
   TensorGeom og;
-  int lo_groups;          // > 0: the output tensor is WIDE (precise mode, model.hip): channel groups [0, lo_groups) hold
+  int lo_groups;          // > 0: the output tensor is WIDE (precise mode, model_graph.h): channel groups [0, lo_groups) hold
                           // hi = fp16(x), groups [lo_groups, 2 lo_groups) hold lo = fp16(x - hi) -- the consumer's K runs over
                           // both with the same weights, i.e. it multiplies 22-bit activations at twice the MFMA count
   int out_goff;           // first destination group of this branch
@@ -47,7 +47,7 @@ struct ConvBranch {
   int relu;
   int sub0;               // first 32-cout subtile of this branch in the launch's cout space
   // AveragePooling2D(3, 1, 'same') of this branch's RAW outputs in the launch's epilogue (ConvArgs::tile_g):
-  // out / og / out_goff / shift / relu then describe the POOLED tensor (model.hip choose_avg_epilogue)
+  // out / og / out_goff / shift / relu then describe the POOLED tensor (model_graph.cpp choose_avg_epilogue)
   int avgpool;
 };
 
@@ -96,16 +96,16 @@ struct ConvArgs {
   const int* blank_row;
   const _Float16* blank_src;
   // blank_need[n] (optional): output rows of example n that the consumer's computed tiles read; a blank block at or
-  // below it is not even copied (model.hip blank_need_kernel)
+  // below it is not even copied (model_kernels.hip blank_need_kernel)
   const int* blank_need;
-  // Split weights (model.hip, HISTORY.md 15): the packed image holds every K chunk twice, W_hi then
+  // Split weights (model_graph.cpp choose_split, HISTORY.md 15): the packed image holds every K chunk twice, W_hi then
   // W_lo = fp16(W - W_hi); n_chunks counts both, the pixel operand advances once per pair.
   // split_tiles: the leading cout tiles of the launch that carry such pairs (= n_tiles when every
   // branch is split); the tiles behind them hold plain weights in the first half of their slot
   // (sibling 1x1 heads of which only some are split, HISTORY.md 15).
   int split;
   int split_tiles;
-  // Side max-pool (model.hip choose_side_pool, HISTORY.md 4.11): a 3x3 / stride-2 'valid' convolution
+  // Side max-pool (model_graph.cpp choose_side_pool, HISTORY.md 4.11): a 3x3 / stride-2 'valid' convolution
   // loads, per 16-channel chunk, exactly the nine pieces of the 3x3 / stride-2 max-pool window of
   // each of its output pixels.  The workgroups of cout tile 0 keep their running maximum and store
   // it -- the sibling MaxPooling2D(3, 2) of the reduction block without its own launch.
@@ -119,7 +119,7 @@ struct ConvArgs {
   // the raw tensor and the avg-pool launch disappear.  grid = ceil(N / tile_g) * n_tiles.
   int tile_g, tile_p;
   float rcp_tile_p;
-  // Wide input (precise mode, model.hip BufferDesc::wide): the input tensor holds Cin / 8 groups of hi = fp16(x) and,
+  // Wide input (precise mode, model_graph.h BufferDesc::wide): the input tensor holds Cin / 8 groups of hi = fp16(x) and,
   // lo_off bytes further in every example, Cin / 8 groups of lo = fp16(x - hi).  Every K chunk is multiplied twice --
   // the same weight fragments against the hi and the lo pixel fragment (conv_slab_wide) -- so the layer sees 22-bit
   // activations for twice the MFMAs at unchanged weight traffic.  n_chunks counts the layer's own chunks.
@@ -146,7 +146,7 @@ __device__ __forceinline__ void divmod_small(int m, int d, float rcp, int& q, in
   }
 }
 
-// The arithmetic of one average-pool output channel, shared by avgpool3s1_kernel (model.hip) and the
+// The arithmetic of one average-pool output channel, shared by avgpool3s1_kernel (model_kernels.hip) and the
 // pooling epilogue below so that both round alike: three column sums (each top + middle + bottom, zeros
 // outside the map) of the float32 raw projection, left to right, times 1 / (cells inside), then shift + ReLU
 // when the pool carries them.

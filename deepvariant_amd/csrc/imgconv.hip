@@ -4,7 +4,7 @@
 // The Inception-v3 blocks of call_variants' classifier (deepvariant/keras_modeling.py:268-274,
 // SURVEY.md App. B) work on small maps (10x25, 4x12, 1x5 at the WGS pileup shape), so a tile
 // of G consecutive images (G*OH*OW <= 512 output pixels = 16 MFMA fragments) is contiguous
-// in the C8 layout and needs no halo exchange.  Compared with conv_mfma_kernel (model.hip),
+// in the C8 layout and needs no halo exchange.  Compared with conv_mfma_kernel (conv_mfma.hip),
 // which pulls every pixel fragment of every filter tap through the vector L1:
 //   * the input patch of a 16-channel chunk (G images x (OH+KH-1) x (OW+KW-1) pixels) is
 //     copied into LDS ONCE by LDS-DMA (global_load_lds_dwordx4, per-lane gather addresses,

@@ -7,7 +7,7 @@
 
 namespace dv {
 
-// How the source buffer stores its elements (model.hip BufferDesc).
+// How the source buffer stores its elements (model_graph.h BufferDesc).
 enum LayerExportKind {
   kExportF16 = 0,    // fp16 pieces of 8 channels
   kExportF32 = 1,    // float32 pieces of 8 channels (BufferDesc::f32)

@@ -1,4 +1,4 @@
-// Interface between model.hip (graph, weights) and stem.hip (the fused stem kernels).
+// Interface between model.hip (launches, weights) and stem.hip (the fused stem kernels).
 #ifndef DV_STEM_FUSED_H_
 #define DV_STEM_FUSED_H_
 
@@ -10,7 +10,7 @@
 namespace dv {
 
 // Geometry of an fp16 activation tensor in the channel-blocked, zero-haloed
-// layout [N][C/8][h + 2 halo][w + 2 halo][8] (model.hip).
+// layout [N][C/8][h + 2 halo][w + 2 halo][8] (conv_common.h).
 struct C8Geom {
   int h, w, halo, hp, wp, groups;
 };
@@ -41,7 +41,7 @@ struct StemAArgs {
   int tiles_y, tiles_x;
   int total_tiles;        // N * tiles_y * tiles_x
   unsigned in_bytes;      // N*H*W*C (< 2^31)
-  // Blank-row skipping (model.hip): blank_thr[n] = first conv2 output row of example n whose receptive
+  // Blank-row skipping (model_kernels.hip blank_rows_kernel): blank_thr[n] = first conv2 output row of example n whose receptive
   // field holds only the zero rows below the pile-up; a tile that starts at or below it equals the all-blank image's
   // response at the same position (blank_src: ONE example in `og`'s geometry, produced by this kernel) and is copied
   // instead of loaded and multiplied -- bit-identical.  NULL = off.

@@ -3,7 +3,7 @@
 Two walks of the oracle's graph (oracle/inception_ref.py) with the product's rounding points: R in float32 as
 given; E with BN-folded weights rounded to fp16 and every stored fp16 activation rounded to fp16 (the pooled
 projections in the product's commuted order: raw 1x1 conv, float32 -> average pool -> + shift -> ReLU -> round; the
-last block's outputs stay float32 for the global pool -- round 6, BufferDesc::f32 in csrc/model.hip).
+last block's outputs stay float32 for the global pool -- round 6, BufferDesc::f32 in csrc/model_graph.h).
 corr[layer][c] = mean_E(pre-activation) - mean_R(pre-activation), applied in E before the next layer.
 """
 import numpy as np

@@ -1,4 +1,4 @@
-"""The pooled projections' average pool in the heads launch's epilogue (model.hip choose_avg_epilogue,
+"""The pooled projections' average pool in the heads launch's epilogue (model_graph.cpp choose_avg_epilogue,
 conv_common.h conv_epilogue_avg) against the separate conv -> avgpool3s1_kernel path (DV_NO_AVG_EPI=1): the
 same arithmetic in the same order, so every block output and the probabilities must agree BIT FOR BIT (GPU)."""
 import os

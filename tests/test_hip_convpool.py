@@ -99,7 +99,7 @@ def _forward_env(shape, weights, x, env):
                                      ((100, 199, 9), 40), ((75, 75, 1), 9), ((120, 301, 5), 6)])
 def test_side_max_pool_of_mixed3_is_bit_identical(shape, n):
   """mixed3's MaxPooling2D(3, 2) taken on the side by the 3x3 / stride-2 convolution of the same tensor
-  (model.hip choose_side_pool: the convolution's nine tap fragments of a channel chunk ARE the pool's window)
+  (model_graph.cpp choose_side_pool: the convolution's nine tap fragments of a channel chunk ARE the pool's window)
   against the separate max-pool launch (DV_NO_SIDE_POOL=1): the maximum is exact, so the 2048 features and
   the probabilities must agree bit for bit -- for the <4,1> tile shape of small batches and the <4,2> shape
   of large ones, and for map sizes whose last pixel block is partial."""

@@ -6,7 +6,7 @@ float32; deepvariant/dv_utils.py:343-366).  The other CNN tests stop at a few hu
 a genome is millions of candidates and the maximum error grows with the sample, so this file
 checks 2048 encoder-drawn ILLUMINA30 pileups on each of three weight seeds (round-3 verdict,
 profiles/r03_error_budget.txt: 1.20e-3 / 1.15e-3 at 1024 before the split weights of
-model.hip `choose_split`), and the split-weight mechanism itself.
+model_graph.cpp `choose_split`), and the split-weight mechanism itself.
 """
 import os
 
