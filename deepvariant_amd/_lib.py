@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
+    'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
 ]
 
 
@@ -255,6 +256,22 @@ class DvGvcfBlock(C.Structure):
               ('ref_base', C.c_uint8), ('has_valid_gl', C.c_uint8), ('reserved', C.c_uint8 * 2)]
 
 
+class DvCandidateOptions(C.Structure):
+  # include/dvhip.h dv_candidate_options: the thresholds are C floats (the reference's proto `float` fields)
+  _fields_ = [('min_count_snps', C.c_int32), ('min_count_indels', C.c_int32),
+              ('min_fraction_snps', C.c_float), ('min_fraction_indels', C.c_float),
+              ('track_ref_reads', C.c_int32), ('positions_only', C.c_int32)]
+
+
+class DvCandidateSite(C.Structure):
+  _fields_ = [('offset', C.c_int32), ('ref_count', C.c_int32), ('total', C.c_int32),
+              ('first_allele', C.c_int32), ('n_alleles', C.c_int32)]
+
+
+class DvCandidateAllele(C.Structure):
+  _fields_ = [('length_type', C.c_uint32), ('count', C.c_int32), ('read', C.c_uint32), ('read_offset', C.c_uint32)]
+
+
 class DvModelDesc(C.Structure):
   _fields_ = [('height', C.c_int32), ('width', C.c_int32),
               ('channels', C.c_int32), ('num_classes', C.c_int32),
@@ -389,6 +406,11 @@ def lib():
     l.dv_gvcf_blocks_arrays.argtypes = [C.c_void_p, C.c_void_p]
     l.dv_gvcf_blocks_free.argtypes = [C.c_void_p]
     l.dv_gvcf_blocks_free.restype = None
+    l.dv_call_candidates_batch.argtypes = [C.c_int32] + [C.c_void_p] * 9
+    l.dv_candidates_arrays.restype = C.c_int64
+    l.dv_candidates_arrays.argtypes = [C.c_void_p] * 6
+    l.dv_candidates_free.argtypes = [C.c_void_p]
+    l.dv_candidates_free.restype = None
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -13,6 +13,10 @@ normalize_cigar restates AlleleCounter::NormalizeCigar (:777-845) for --normaliz
 gvcf_blocks / run_batch(gvcf=...) add the reference's VariantCaller.make_gvcfs(summary_counts())
 (deepvariant/variant_caller.py), computed on the device from the same counts
 (deepvariant_amd/csrc/gvcf.hip); variant_calling.VariantCaller.make_gvcfs is its host restatement.
+candidates / candidate_positions / run_batch(call=...) add the reference's VariantCaller::CallsFromAlleleCounter
+and CallPositionsFromAlleleCounts (variant_calling.cc:365-382, variant_calling_multisample.cc:940-1004) in the same way
+(deepvariant_amd/csrc/candidates.hip): the device groups the events into alleles and applies the thresholds, and
+only the candidate positions' alleles are built here; variant_calling.VariantCaller is the host restatement.
 """
 from __future__ import annotations
 
@@ -31,6 +35,11 @@ _EVENT_DTYPE = np.dtype([('position', '<i4'), ('read', '<u4'), ('read_offset', '
 GVCF_BLOCK_DTYPE = np.dtype([('start', '<i8'), ('end', '<i8'), ('likelihoods', '<f8', (3,)), ('gq', '<i4'),
                              ('min_dp', '<i4'), ('med_dp', '<i4'), ('ref_base', 'u1'), ('has_valid_gl', 'u1'),
                              ('reserved', 'u1', (2,))])   # dv_gvcf_block
+CANDIDATE_SITE_DTYPE = np.dtype([('offset', '<i4'), ('ref_count', '<i4'), ('total', '<i4'), ('first_allele', '<i4'),
+                                 ('n_alleles', '<i4')])    # dv_candidate_site
+CANDIDATE_ALLELE_DTYPE = np.dtype([('length_type', '<u4'), ('count', '<i4'), ('read', '<u4'),
+                                   ('read_offset', '<u4')])   # dv_candidate_allele
+EVENT_UNCALLED, EVENT_OVERWRITTEN = -1, -2                  # DV_CANDIDATE_EVENT_*
 
 
 class Allele:
@@ -52,6 +61,18 @@ class AlleleCount:
     self.ref_supporting_read_count = 0
     self.read_alleles: Dict[str, Allele] = {}
     self.track_ref_reads = False
+
+
+class CandidateSite(AlleleCount):
+  """One position the device caller selected alternate alleles at (AlleleCounter.candidates): the
+  AlleleCount fields, plus `selected` (the selected Alleles with their counts, in SumAlleleCounts
+  order) and `total` (TotalAlleleCounts).  read_alleles is complete and in the map's order, but only
+  the reads that support a selected allele (or the reference) carry a text: the others' bases are None."""
+
+  def __init__(self, reference_name: str, position: int, ref_base: str):
+    super().__init__(reference_name, position, ref_base)
+    self.selected: List[Allele] = []
+    self.total = 0
 
 
 def sum_allele_counts(allele_count: AlleleCount, include_low_quality: bool = False) -> List[Allele]:
@@ -95,6 +116,8 @@ class AlleleCounter:
     self._event_ctx = None
     self._n_counted = 0
     self._gvcf = None            # (GvcfOptions.key(), dv_gvcf_block records) of the last gVCF pass
+    self._cand = None            # (CandidateOptions.key(), sites, alleles, event words) of the last candidate pass
+    self._cand_positions = None  # (CandidateOptions.key(), offsets) of the last positions-only pass
 
   # ---- the reference's interface
   def interval_length(self) -> int:
@@ -107,14 +130,14 @@ class AlleleCounter:
     if self._table is not None:
       raise ValueError('reads were handed over as a packed table; add() cannot be mixed in')
     self._reads.append(read)
-    self._counts = self._alleles = self._events = self._gvcf = None
+    self._counts = self._alleles = self._events = self._gvcf = self._cand = self._cand_positions = None
 
   def add_table(self, table: packing.ReadTable):
     """All reads of the region at once, already packed (packing.ReadTable.from_bam / from_reads)."""
     if self._reads:
       raise ValueError('add() was used; add_table() cannot be mixed in')
     self._table = table
-    self._counts = self._alleles = self._events = self._gvcf = None
+    self._counts = self._alleles = self._events = self._gvcf = self._cand = self._cand_positions = None
 
   def _ensure(self):
     if self._events is None:
@@ -243,12 +266,20 @@ class AlleleCounter:
     self._take(handle, ctx)
 
   @staticmethod
-  def run_batch(counters: Sequence['AlleleCounter'], gvcf=None) -> None:
+  def run_batch(counters: Sequence['AlleleCounter'], gvcf=None, call=None) -> None:
     """Counts for several counters (a batch of calling regions, each with its reads added) in ONE
     dv_count_alleles_batch call: one upload, kernels back to back, two synchronisations for the
     whole batch.  Afterwards every counter answers as if it had counted alone.  With `gvcf`
     (variant_calling.GvcfOptions) the gVCF blocks of every counter are computed in the same device
-    pass (dv_count_alleles_gvcf_batch) and `gvcf_blocks(gvcf)` answers without another launch."""
+    pass (dv_count_alleles_gvcf_batch) and `gvcf_blocks(gvcf)` answers without another launch.  With
+    `call` (variant_calling.CandidateOptions) so are the candidates (dv_call_candidates_batch):
+    `candidates(call)` / `candidate_positions(call)` then answer without another launch; a
+    positions-only pass leaves the counters uncounted."""
+    if call is not None:
+      todo = [c for c in counters if not c._has_candidates(call) or                   # pylint: disable=protected-access
+              (gvcf is not None and (c._gvcf is None or c._gvcf[0] != gvcf.key()))]   # pylint: disable=protected-access
+      AlleleCounter._run_call_batch(todo, call, gvcf)
+      return
     if gvcf is not None:
       AlleleCounter._run_gvcf_batch(
           [c for c in counters if c._gvcf is None or c._gvcf[0] != gvcf.key()], gvcf)   # pylint: disable=protected-access
@@ -281,12 +312,7 @@ class AlleleCounter:
       return
     requests = [c._request() for c in todo]                # pylint: disable=protected-access
     n = len(todo)
-    keys = []
-    for r in requests:
-      names = r[3][0].keys
-      # read_alleles is keyed by read key: reads that share one (supplementary alignments) are one key
-      keys.append(np.ascontiguousarray(np.unique(np.array(names), return_inverse=True)[1].astype(np.int32))
-                  if len(set(names)) != len(names) else None)
+    keys = [AlleleCounter._read_key_ids(r[3][0].keys) for r in requests]
     table = gvcf.table()
     opt = _lib.DvGvcfOptions(gvcf.p_error, gvcf.max_gq, gvcf.gq_resolution, gvcf.max_cache_coverage,
                              int(gvcf.include_med_dp), gvcf.left_padding, gvcf.right_padding,
@@ -318,6 +344,152 @@ class AlleleCounter:
           lib.dv_allele_counts_free(C.c_void_p(h))
         if b:
           lib.dv_gvcf_blocks_free(C.c_void_p(b))
+
+  def _has_candidates(self, call) -> bool:
+    if self._cand is not None and self._cand[0] == call.key():
+      return True
+    return bool(call.positions_only) and self._cand_positions is not None and self._cand_positions[0] == call.key()
+
+  @staticmethod
+  def _read_key_ids(names) -> Optional[np.ndarray]:
+    """read_alleles is keyed by read key: reads that share one (supplementary alignments) are one key."""
+    ids: Dict[str, int] = {}
+    per_read = [ids.setdefault(name, len(ids)) for name in names]     # (np.unique on strings costs 100 us a region)
+    return None if len(ids) == len(names) else np.ascontiguousarray(per_read, np.int32)
+
+  @staticmethod
+  def _run_call_batch(todo: Sequence['AlleleCounter'], call, gvcf=None) -> None:
+    if not todo:
+      return
+    if call.positions_only and gvcf is not None:
+      raise ValueError('a positions-only candidate pass has no gVCF records')
+    requests = [c._request() for c in todo]                # pylint: disable=protected-access
+    n = len(todo)
+    keys = [AlleleCounter._read_key_ids(r[3][0].keys) for r in requests]
+    copt = _lib.DvCandidateOptions(int(call.min_count_snps), int(call.min_count_indels), float(call.min_fraction_snps),
+                                   float(call.min_fraction_indels), int(call.track_ref_reads), int(call.positions_only))
+    gopt = None
+    if gvcf is not None:
+      table = gvcf.table()
+      gopt = _lib.DvGvcfOptions(gvcf.p_error, gvcf.max_gq, gvcf.gq_resolution, gvcf.max_cache_coverage,
+                                int(gvcf.include_med_dp), gvcf.left_padding, gvcf.right_padding,
+                                table.ctypes.data, len(table))
+    batches = (C.c_void_p * n)(*[C.addressof(r[0]) for r in requests])
+    options = (C.c_void_p * n)(*[C.addressof(r[1]) for r in requests])
+    key_ptrs = (C.c_void_p * n)(*[k.ctypes.data if k is not None else None for k in keys])
+    handles, blocks, cands = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+    lib = _lib.lib()
+    _lib.check(lib.dv_call_candidates_batch(n, batches, options, key_ptrs, C.byref(copt),
+                                            C.byref(gopt) if gopt is not None else None,
+                                            None if call.positions_only else handles,
+                                            blocks if gopt is not None else None, cands, None))
+    taken = 0
+    try:
+      for c, r, h, b, d in zip(todo, requests, handles, blocks, cands):
+        taken += 1                                         # this region's handles are freed below, also on an error
+        try:
+          sites, alleles, words = C.c_void_p(), C.c_void_p(), C.c_void_p()
+          n_alleles, n_words = C.c_int32(), C.c_uint32()
+          n_sites = int(lib.dv_candidates_arrays(C.c_void_p(d), C.byref(sites), C.byref(alleles), C.byref(n_alleles),
+                                                 C.byref(words), C.byref(n_words)))
+
+          def array(pointer, count, dtype):
+            return (np.frombuffer(C.string_at(pointer, count * dtype.itemsize), dtype) if count
+                    else np.zeros(0, dtype))
+          site_arr = array(sites, n_sites, CANDIDATE_SITE_DTYPE)
+          allele_arr = array(alleles, n_alleles.value, CANDIDATE_ALLELE_DTYPE)
+          word_arr = array(words, n_words.value, np.dtype('<i4'))
+          block_arr = None
+          if gopt is not None:
+            records = C.POINTER(_lib.DvGvcfBlock)()
+            nb = int(lib.dv_gvcf_blocks_arrays(C.c_void_p(b), C.byref(records)))
+            block_arr = array(records, nb, GVCF_BLOCK_DTYPE)
+        finally:
+          lib.dv_candidates_free(C.c_void_p(d))
+          if b:
+            lib.dv_gvcf_blocks_free(C.c_void_p(b))
+        if call.positions_only:
+          c._cand_positions = (call.key(), site_arr['offset'].astype(np.int64))   # pylint: disable=protected-access
+          continue
+        c._take(C.c_void_p(h), r[3])                       # pylint: disable=protected-access
+        c._cand = (call.key(), site_arr, allele_arr, word_arr)   # pylint: disable=protected-access
+        c._cand_positions = None                           # pylint: disable=protected-access
+        if gopt is not None:
+          c._gvcf = (gvcf.key(), block_arr)                # pylint: disable=protected-access
+    finally:
+      for h, b, d in list(zip(handles, blocks, cands))[taken:]:
+        if h:
+          lib.dv_allele_counts_free(C.c_void_p(h))
+        if b:
+          lib.dv_gvcf_blocks_free(C.c_void_p(b))
+        if d:
+          lib.dv_candidates_free(C.c_void_p(d))
+
+  def candidate_positions(self, call) -> List[int]:
+    """CallPositionsFromAlleleCounts from the device: the absolute positions CallVariant will return a
+    call for, in order.  Answers from a full candidate pass with the same thresholds when there was
+    one; otherwise from a positions-only pass (run now unless run_batch(call=...) already did), which
+    brings home the positions and nothing else."""
+    if self._cand is not None and self._cand[0] == call.key():
+      offsets = self._cand[1]['offset']
+    else:
+      if self._cand_positions is None or self._cand_positions[0] != call.key():
+        AlleleCounter._run_call_batch([self], call.positions_form())
+      offsets = self._cand_positions[1]
+    return [self._start + int(o) for o in offsets]
+
+  def candidates(self, call) -> List[CandidateSite]:
+    """The positions at which the device caller selected alternate alleles (SelectAltAlleles), in
+    order, each with what CallVariant needs -- computed now unless run_batch(call=...) already did
+    with these thresholds.  Allele texts are cut for the selected alleles' representatives only;
+    every other read allele of the site is known by the word the device left for its event."""
+    if self._cand is None or self._cand[0] != call.key():
+      AlleleCounter._run_call_batch([self], call.calls_form())
+    _, sites, alleles, words = self._cand
+    if not len(sites):
+      return []
+    ev = self._events
+    table, window, w0 = self._event_ctx
+    keys, bases, seq_off = table.keys, table.bases, table.read_seq_off
+    first = np.searchsorted(ev['position'], sites['offset'], 'left').tolist()
+    last = np.searchsorted(ev['position'], sites['offset'], 'right').tolist()
+    out = []
+    for site, lo, hi in zip(sites.tolist(), first, last):
+      offset, ref_count, total, first_allele, n_alleles = site
+      c = CandidateSite(self._contig, self._start + offset, self._interval_ref[offset])
+      c.ref_supporting_read_count, c.total, c.track_ref_reads = ref_count, total, self._track_ref_reads
+      selected = []
+      for packed, count, read, read_offset in alleles[first_allele:first_allele + n_alleles].tolist():
+        length_k, type_k = packed & 0x0fffffff, (packed >> 28) & 7
+        s0 = int(seq_off[read]) + read_offset
+        if type_k == SUBSTITUTION:
+          text = chr(bases[s0])
+        else:
+          anchor = self._start + offset - w0              # the base the indel is anchored on
+          prev = chr(bases[s0 - 1]) if read_offset > 0 else window[anchor:anchor + 1].decode()
+          if type_k == DELETION:
+            text = prev + window[anchor + 1:anchor + 1 + length_k].decode()
+          else:
+            text = prev + bytes(bases[s0:s0 + length_k]).decode()
+        selected.append(Allele(text, type_k, count))
+      c.selected = sorted(selected, key=lambda a: (a.bases, a.type))     # SumAlleleCounts' map order
+      # read_alleles in the map's order: a key stands where it was first inserted, with its last value
+      read_alleles: Dict[str, Optional[Allele]] = {}
+      for (_, read, _, packed), word in zip(ev[lo:hi].tolist(), words[lo:hi].tolist()):
+        key = keys[read]
+        if word == EVENT_OVERWRITTEN:
+          read_alleles.setdefault(key, None)
+          continue
+        type_k, low = (packed >> 28) & 7, bool(packed >> 31)
+        if type_k == REFERENCE:
+          read_alleles[key] = Allele(c.ref_base, REFERENCE, 1, low)
+        elif word >= 0:
+          read_alleles[key] = Allele(selected[word].bases, type_k, 1, low)
+        else:
+          read_alleles[key] = Allele(None, type_k, 1, low)
+      c.read_alleles = read_alleles
+      out.append(c)
+    return out
 
   def gvcf_block_array(self, gvcf) -> np.ndarray:
     """The device's gVCF records of this counter (GVCF_BLOCK_DTYPE; MED_DP -1 unless asked for),

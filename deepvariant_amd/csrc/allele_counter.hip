@@ -21,6 +21,7 @@
 #include <memory>
 #include <vector>
 
+#include "candidates.h"
 #include "dv_internal.h"
 #include "gvcf.h"
 
@@ -392,6 +393,27 @@ void order_events(dv_allele_counts* res, size_t n_ev) {
   }
 }
 
+// The same order with one word per raw event carried along (the candidate pass' event words, which the
+// device writes in the kernel's event order).
+void order_events_with_words(dv_allele_counts* res, size_t n_ev, const int32_t* raw_words, std::vector<int32_t>* words) {
+  std::vector<uint32_t> idx(n_ev);
+  for (size_t i = 0; i < n_ev; ++i) idx[i] = static_cast<uint32_t>(i);
+  const dv_allele_event* raw = res->raw.ptr;
+  std::stable_sort(idx.begin(), idx.end(), [raw](uint32_t i, uint32_t j) {
+    const dv_allele_event &x = raw[i], &y = raw[j];
+    if (x.position != y.position) return static_cast<uint32_t>(x.position) < static_cast<uint32_t>(y.position);
+    if (x.read != y.read) return x.read < y.read;
+    return x.read_offset < y.read_offset;
+  });
+  res->events.resize(n_ev);
+  words->resize(n_ev);
+  for (size_t i = 0; i < n_ev; ++i) {
+    res->events[i] = raw[idx[i]];
+    (*words)[i] = raw_words[idx[i]];
+  }
+  res->raw.release();
+}
+
 // Argument and read-table checks shared by the one-region and the batch entry point.
 int check_request(const dv_batch* b, const dv_allele_counter_options* o, dv_allele_counts** out, const char* who) {
   const std::string name(who);
@@ -510,6 +532,110 @@ int gvcf_from_counts(const dv_allele_counts* c, const dv_allele_counter_options*
   return DV_OK;
 }
 
+// The candidate pass over counts that are already on the host (a region that took the one-region path),
+// as gvcf_from_counts: the counts and sorted events go back up and through the same kernels, so the
+// event words come back in the order of dv_allele_counts_arrays.  Two synchronisations; the rare path.
+int candidates_from_counts(const dv_allele_counts* c, const dv_allele_counter_options* o, const dv_batch* b,
+                           const int32_t* keys, const dv_candidate_options* co, hipStream_t stream,
+                           dv_candidates** out) {
+  static thread_local dv::DeviceBuffer d_img;
+  auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
+  auto res = std::make_unique<dv_candidates>();
+  const int64_t len = c->length;
+  if (len == 0) {
+    *out = res.release();
+    return DV_OK;
+  }
+  if (len > 0x7fffffff - 2) return dv::fail(DV_ERR_INVALID_ARGUMENT, "interval too long for the candidate pass");
+  const uint32_t n_ev = static_cast<uint32_t>(c->events.size());
+  const size_t n_reads = static_cast<size_t>(b->n_reads);
+  const size_t n_keys = keys ? n_reads : 0;
+  const bool table_on_host = b->memory == DV_MEM_HOST && n_reads > 0;
+  // image: descriptor | n_events, n_sites, n_alleles | ref_count | events | ref | keys | seq_off | bases |
+  //        scratch | sites | alleles | words
+  size_t at = 0;
+  const size_t o_desc = at;
+  at += align16(sizeof(dv::CandRegion));
+  const size_t o_words = at;
+  at += 16;
+  const size_t o_cnt = at;
+  at += align16(static_cast<size_t>(len) * 4);
+  const size_t o_ev = at;
+  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
+  const size_t o_ref = at;
+  at += align16(static_cast<size_t>(len));
+  const size_t o_keys = at;
+  at += align16(n_keys * 4);
+  const size_t o_seq = at;
+  if (table_on_host) at += align16((n_reads + 1) * 4);
+  const size_t o_bases = at;
+  if (table_on_host) at += align16(b->n_bases);
+  const size_t up_bytes = at;
+  const size_t o_scr = at;
+  at += align16(dv::cand_scratch_ints(len, n_ev) * 4);
+  const size_t o_site = at;
+  at += align16(static_cast<size_t>(len) * sizeof(dv_candidate_site));
+  const size_t o_all = at;
+  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_candidate_allele));
+  const size_t o_evw = at;
+  at += align16(static_cast<size_t>(n_ev) * 4);
+  if (int rc = d_img.reserve_on_current_device(at)) return rc;
+  uint8_t* dev = static_cast<uint8_t*>(d_img.ptr);
+  std::vector<uint8_t> img(up_bytes, 0);
+  dv::CandRegion g{};
+  g.ref_count = reinterpret_cast<const int32_t*>(dev + o_cnt);
+  g.events = reinterpret_cast<const dv_allele_event*>(dev + o_ev);
+  g.n_events = reinterpret_cast<const uint32_t*>(dev + o_words);
+  g.event_cap = n_ev;
+  g.read_key = keys ? reinterpret_cast<const int32_t*>(dev + o_keys) : nullptr;
+  g.ref = dev + o_ref;
+  g.bases = table_on_host ? dev + o_bases : b->bases;
+  g.seq_off = table_on_host ? reinterpret_cast<const uint32_t*>(dev + o_seq) : b->read_seq_off;
+  g.len = static_cast<int32_t>(len);
+  g.scratch = reinterpret_cast<int32_t*>(dev + o_scr);
+  g.sites = reinterpret_cast<dv_candidate_site*>(dev + o_site);
+  g.alleles = reinterpret_cast<dv_candidate_allele*>(dev + o_all);
+  g.words = reinterpret_cast<int32_t*>(dev + o_evw);
+  g.n_out = reinterpret_cast<int32_t*>(dev + o_words + 4);
+  std::memcpy(img.data() + o_desc, &g, sizeof(g));
+  std::memcpy(img.data() + o_words, &n_ev, 4);
+  const int32_t* cnt = c->ref_count.ptr ? c->ref_count.ptr : c->empty_counts.data();
+  std::memcpy(img.data() + o_cnt, cnt, static_cast<size_t>(len) * 4);
+  if (n_ev) std::memcpy(img.data() + o_ev, c->events.data(), static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
+  std::memcpy(img.data() + o_ref, o->ref_bases + (o->interval_start - o->ref_start), static_cast<size_t>(len));
+  if (n_keys) std::memcpy(img.data() + o_keys, keys, n_keys * 4);
+  if (table_on_host) {
+    std::memcpy(img.data() + o_seq, b->read_seq_off, (n_reads + 1) * 4);
+    std::memcpy(img.data() + o_bases, b->bases, b->n_bases);
+  }
+  DV_HIP_CHECK(hipMemcpyAsync(dev, img.data(), up_bytes, hipMemcpyHostToDevice, stream));
+  DV_HIP_CHECK(hipMemsetAsync(dev + o_scr, 0, o_site - o_scr, stream));
+  if (int rc = dv::cand_launch(reinterpret_cast<const dv::CandRegion*>(dev + o_desc), 1, n_ev, co, nullptr, nullptr,
+                               stream)) {
+    return rc;
+  }
+  int32_t n_out[2] = {0, 0};
+  DV_HIP_CHECK(hipMemcpyAsync(n_out, dev + o_words + 4, 8, hipMemcpyDeviceToHost, stream));
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  res->sites.resize(static_cast<size_t>(n_out[0]));
+  if (n_out[0]) {
+    DV_HIP_CHECK(hipMemcpyAsync(res->sites.data(), dev + o_site, res->sites.size() * sizeof(dv_candidate_site),
+                                hipMemcpyDeviceToHost, stream));
+  }
+  if (!co->positions_only) {
+    res->alleles.resize(static_cast<size_t>(n_out[1]));
+    res->words.resize(n_ev);
+    if (n_out[1]) {
+      DV_HIP_CHECK(hipMemcpyAsync(res->alleles.data(), dev + o_all, res->alleles.size() * sizeof(dv_candidate_allele),
+                                  hipMemcpyDeviceToHost, stream));
+    }
+    if (n_ev) DV_HIP_CHECK(hipMemcpyAsync(res->words.data(), dev + o_evw, static_cast<size_t>(n_ev) * 4, hipMemcpyDeviceToHost, stream));
+  }
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  *out = res.release();
+  return DV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -624,14 +750,29 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
 // device-resident, and the rare region whose events overflow the first guess, take the one-region path.
 // dv_count_alleles_batch, and with `gv` set dv_count_alleles_gvcf_batch: the gVCF pass (gvcf.hip) is queued
 // behind the counting kernels and its records come back with the events.  Without `gv` nothing differs.
+// With `co` set dv_call_candidates_batch: the candidate pass (candidates.hip) is queued behind the counting
+// kernels in the same way; with positions_only neither counts nor events come back (`out` is not used).
 static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
-                       const int32_t* const* read_keys, const dv_gvcf_options* gv, dv_allele_counts** out,
-                       dv_gvcf_blocks** gout, void* stream_v, const char* who) {
+                       const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
+                       dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout, void* stream_v,
+                       const char* who) {
   const std::string name(who);
-  if (n < 0 || (n > 0 && (!reads || !options || !out || (gv && !gout)))) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
+  const bool pos_only = co && co->positions_only;
+  // positions only: the one-region path's counts live here and go with the call
+  std::vector<dv_allele_counts*> own_out;
+  if (pos_only && n > 0) {
+    own_out.assign(static_cast<size_t>(n), nullptr);
+    out = own_out.data();
+  }
+  if (n < 0 || (n > 0 && (!reads || !options || !out || (gv && !gout) || (co && !cout)))) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
+  }
   for (int32_t k = 0; k < n; ++k) out[k] = nullptr;
   if (gv) {
     for (int32_t k = 0; k < n; ++k) gout[k] = nullptr;
+  }
+  if (co) {
+    for (int32_t k = 0; k < n; ++k) cout[k] = nullptr;
   }
   auto fail_all = [&](int rc) {
     for (int32_t k = 0; k < n; ++k) {
@@ -641,11 +782,19 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
         delete gout[k];
         gout[k] = nullptr;
       }
+      if (co) {
+        delete cout[k];
+        cout[k] = nullptr;
+      }
     }
     return rc;
   };
   if (gv) {
     if (int rc = dv::gvcf_check_options(gv, who)) return rc;
+  }
+  if (co) {
+    if (int rc = dv::cand_check_options(co, who)) return rc;
+    if (pos_only && gv) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": positions_only excludes the gVCF pass");
   }
   for (int32_t k = 0; k < n; ++k) {
     if (gv) {   // before check_request: bad input is reported as such with or without a device
@@ -655,7 +804,11 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     if (options[k]->track_ref_reads && options[k]->n_candidate_positions > 0 && !options[k]->candidate_positions) {
       return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": candidate_positions is null");
     }
+    if (co && options[k]->interval_end - options[k]->interval_start > 0x7fffffff - 2) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": interval too long for the candidate pass");
+    }
   }
+  std::vector<char> done(static_cast<size_t>(n), 0);   // regions the batched path has answered
   auto keys_of = [&](int32_t k) -> const int32_t* { return read_keys ? read_keys[k] : nullptr; };
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const dv_gvcf_site* d_table = nullptr;
@@ -671,6 +824,8 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     size_t mask_words = 0;
     size_t key_up = 0, scr_off = 0, blk_off = 0;  // gVCF: staging offset of the read keys, scratch ints, records
     int gv_slot = -1;                             // gVCF: index among the batched regions
+    int cd_slot = -1;                             // candidates: likewise, and the region's scratch ints
+    size_t cscr_off = 0;
   };
   std::vector<Plan> plan(static_cast<size_t>(n));
   auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
@@ -678,6 +833,8 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
   int n_batched = 0;
   int n_gv = 0;                                  // gVCF: batched regions, their scratch and record totals
   size_t scr_ints = 0, blk_total = 0;
+  int n_cd = 0;                                  // candidates: batched regions and their scratch total
+  size_t cscr_ints = 0;
   int64_t max_len = 0;
   uint32_t max_cap = 0;
   for (int32_t k = 0; k < n; ++k) {
@@ -707,11 +864,18 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     p.cap = b->n_cigar + b->n_bases / 16 + 4096 + static_cast<uint32_t>(std::min<size_t>(n_candidate_refs * 64, 1u << 24));
     p.ev_off = ev_total;
     ev_total += p.cap;
+    if ((gv || co) && keys_of(k)) {
+      p.key_up = up_bytes;
+      up_bytes += align16(nr * 4);
+    }
+    if (co) {
+      p.cd_slot = n_cd;
+      ++n_cd;
+      p.cscr_off = cscr_ints;
+      cscr_ints += dv::cand_scratch_ints(p.len, p.cap);
+      max_cap = std::max(max_cap, p.cap);
+    }
     if (gv) {
-      if (keys_of(k)) {
-        p.key_up = up_bytes;
-        up_bytes += align16(nr * 4);
-      }
       p.gv_slot = n_gv;
       ++n_gv;
       p.scr_off = scr_ints;
@@ -725,15 +889,21 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
   // gVCF: the batched regions' descriptors travel at the end of the staging image
   const size_t desc_up = up_bytes;
   if (n_gv) up_bytes += align16(static_cast<size_t>(n_gv) * sizeof(dv::GvcfRegion));
+  const size_t cdesc_up = up_bytes;
+  if (n_cd) up_bytes += align16(static_cast<size_t>(n_cd) * sizeof(dv::CandRegion));
   if (n_batched > 0) {
     // grow-only scratch per host thread: pinned staging both ways, device images
     static thread_local PinnedBytes h_up, h_down;
     static thread_local dv::DeviceBuffer d_up, d_res, d_ev;
     static thread_local dv::DeviceBuffer d_gscr, d_gblk, d_gpack;
+    static thread_local dv::DeviceBuffer d_cscr, d_csite, d_call, d_cword, d_cpsite, d_cpall;
     const size_t ctr_bytes = align16(static_cast<size_t>(n) * 4 * sizeof(uint32_t));
     // gVCF: each region's record count follows the counts (and comes back with them)
     const size_t nblk_off = align16(ctr_bytes + cnt_ints * sizeof(int32_t));
-    const size_t res_bytes = gv ? nblk_off + static_cast<size_t>(n) * sizeof(int32_t) : ctr_bytes + cnt_ints * sizeof(int32_t);
+    size_t res_bytes = gv ? nblk_off + static_cast<size_t>(n) * sizeof(int32_t) : ctr_bytes + cnt_ints * sizeof(int32_t);
+    // candidates: then each region's site and allele record counts
+    const size_t ncand_off = align16(res_bytes);
+    if (co) res_bytes = ncand_off + static_cast<size_t>(n) * 2 * sizeof(int32_t);
     if (int rc = h_up.reserve(up_bytes)) return rc;
     if (int rc = d_up.reserve_on_current_device(up_bytes)) return rc;
     if (int rc = d_res.reserve_on_current_device(res_bytes)) return rc;
@@ -742,6 +912,15 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
       if (int rc = d_gscr.reserve_on_current_device(scr_ints * sizeof(int32_t))) return rc;
       if (int rc = d_gblk.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
       if (int rc = d_gpack.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
+    }
+    if (n_cd) {
+      const size_t sites = std::max<size_t>(cnt_ints, 1), evs = std::max<size_t>(ev_total, 1);
+      if (int rc = d_cscr.reserve_on_current_device(std::max<size_t>(cscr_ints, 1) * sizeof(int32_t))) return rc;
+      if (int rc = d_csite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
+      if (int rc = d_cpsite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
+      if (int rc = d_call.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
+      if (int rc = d_cpall.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
+      if (int rc = d_cword.reserve_on_current_device(evs * sizeof(int32_t))) return rc;
     }
     for (int32_t k = 0; k < n; ++k) {
       const Plan& p = plan[k];
@@ -766,11 +945,29 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
           if (q >= 0 && q < p.len) mask[static_cast<size_t>(q >> 5)] |= 1u << (q & 31);
         }
       }
+      const uint8_t* dup0 = static_cast<const uint8_t*>(d_up.ptr);
+      uint8_t* dres0 = static_cast<uint8_t*>(d_res.ptr);
+      if ((gv || co) && keys_of(k)) std::memcpy(base + p.key_up, keys_of(k), nr * 4);
+      if (p.cd_slot >= 0) {
+        dv::CandRegion g{};
+        g.ref_count = reinterpret_cast<const int32_t*>(dres0 + ctr_bytes) + p.cnt_off;
+        g.events = static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off;
+        g.n_events = reinterpret_cast<const uint32_t*>(dres0) + static_cast<size_t>(k) * 4;
+        g.event_cap = p.cap;
+        g.read_key = keys_of(k) ? reinterpret_cast<const int32_t*>(dup0 + p.key_up) : nullptr;
+        g.ref = dup0 + p.up[7] + (o->interval_start - o->ref_start);
+        g.bases = dup0 + p.up[4];
+        g.seq_off = reinterpret_cast<const uint32_t*>(dup0 + p.up[1]);
+        g.len = static_cast<int32_t>(p.len);
+        g.scratch = static_cast<int32_t*>(d_cscr.ptr) + p.cscr_off;
+        g.sites = static_cast<dv_candidate_site*>(d_csite.ptr) + p.cnt_off;
+        g.alleles = static_cast<dv_candidate_allele*>(d_call.ptr) + p.ev_off;
+        g.words = static_cast<int32_t*>(d_cword.ptr) + p.ev_off;
+        g.n_out = reinterpret_cast<int32_t*>(dres0 + ncand_off) + static_cast<size_t>(k) * 2;
+        std::memcpy(base + cdesc_up + static_cast<size_t>(p.cd_slot) * sizeof(dv::CandRegion), &g, sizeof(g));
+      }
       if (p.gv_slot >= 0) {
         // the descriptor points into the device images: the counts, events and reference the counter uses
-        const uint8_t* dup0 = static_cast<const uint8_t*>(d_up.ptr);
-        uint8_t* dres0 = static_cast<uint8_t*>(d_res.ptr);
-        if (keys_of(k)) std::memcpy(base + p.key_up, keys_of(k), nr * 4);
         dv::GvcfRegion g{};
         g.ref_count = reinterpret_cast<const int32_t*>(dres0 + ctr_bytes) + p.cnt_off;
         g.events = static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off;
@@ -794,6 +991,7 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
       DV_HIP_CHECK(hipMemsetAsync(d_gscr.ptr, 0, scr_ints * sizeof(int32_t), stream));
       if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
     }
+    if (n_cd) DV_HIP_CHECK(hipMemsetAsync(d_cscr.ptr, 0, cscr_ints * sizeof(int32_t), stream));
     uint8_t* dres = static_cast<uint8_t*>(d_res.ptr);
     const uint8_t* dup = static_cast<const uint8_t*>(d_up.ptr);
     for (int32_t k = 0; k < n; ++k) {
@@ -838,10 +1036,25 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
         return rc;
       }
     }
+    if (n_cd) {
+      // the candidate caller reads the same counts and events, and the read bases the events point into
+      if (int rc = dv::cand_launch(reinterpret_cast<const dv::CandRegion*>(dup + cdesc_up), n_cd, max_cap, co,
+                                   static_cast<dv_candidate_site*>(d_cpsite.ptr),
+                                   static_cast<dv_candidate_allele*>(d_cpall.ptr), stream)) {
+        return rc;
+      }
+    }
     // counters and counts come back together; the events follow once their numbers are known
     if (int rc = h_down.reserve(res_bytes)) return rc;
-    DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, res_bytes, hipMemcpyDeviceToHost, stream));
+    if (pos_only) {                  // the counters and the record counts only
+      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, ctr_bytes, hipMemcpyDeviceToHost, stream));
+      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr + ncand_off, dres + ncand_off, res_bytes - ncand_off, hipMemcpyDeviceToHost,
+                                  stream));
+    } else {
+      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, res_bytes, hipMemcpyDeviceToHost, stream));
+    }
     DV_HIP_CHECK(hipStreamSynchronize(stream));
+    const int32_t* ncand = reinterpret_cast<const int32_t*>(h_down.ptr + ncand_off);
     const uint32_t* ctrs = reinterpret_cast<const uint32_t*>(h_down.ptr);
     const int32_t* cnts = reinterpret_cast<const int32_t*>(h_down.ptr + ctr_bytes);
     size_t ev_bytes = 0;
@@ -857,6 +1070,13 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
         p.batched = false;
         continue;
       }
+      done[k] = 1;
+      if (co) {
+        cout[k] = new dv_candidates();
+        cout[k]->sites.resize(static_cast<size_t>(ncand[2 * k]));
+        if (!pos_only) cout[k]->alleles.resize(static_cast<size_t>(ncand[2 * k + 1]));
+      }
+      if (pos_only) continue;
       auto res = std::make_unique<dv_allele_counts>();
       res->length = p.len;
       res->n_reads_counted = static_cast<int32_t>(ctr[1]);
@@ -880,19 +1100,49 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     }
     const size_t packed_at = ev_bytes;
     ev_bytes += packed_blocks * sizeof(dv_gvcf_block);
+    // candidates: the event words region by region (as the events), then the packed site and allele
+    // records of every batched region (cand_pack_kernel), the overflowed regions' included
+    const size_t words_at = ev_bytes;
+    size_t packed_sites = 0, packed_alleles = 0;
+    if (co) {
+      for (int32_t k = 0; k < n; ++k) {
+        if (plan[k].cd_slot < 0) continue;
+        packed_sites += static_cast<size_t>(ncand[2 * k]);
+        packed_alleles += static_cast<size_t>(ncand[2 * k + 1]);
+        if (plan[k].batched && !pos_only) ev_bytes += static_cast<size_t>(ctrs[static_cast<size_t>(k) * 4]) * sizeof(int32_t);
+      }
+    }
+    const size_t sites_at = ev_bytes;
+    ev_bytes += packed_sites * sizeof(dv_candidate_site);
+    const size_t alleles_at = ev_bytes;
+    if (!pos_only) ev_bytes += packed_alleles * sizeof(dv_candidate_allele);
     // the events (and gVCF records) of every region into one pinned image, one synchronisation
     static thread_local PinnedBytes h_ev;
     if (int rc = h_ev.reserve(ev_bytes)) return fail_all(rc);
-    size_t at = 0;
+    size_t at = 0, wat = words_at;
     for (int32_t k = 0; k < n; ++k) {
       const Plan& p = plan[k];
-      if (!p.batched || !out[k]) continue;
-      const size_t bytes = static_cast<size_t>(ctrs[static_cast<size_t>(k) * 4]) * sizeof(dv_allele_event);
+      if (!p.batched || pos_only) continue;
+      const size_t n_ev = ctrs[static_cast<size_t>(k) * 4];
+      const size_t bytes = n_ev * sizeof(dv_allele_event);
       if (bytes) {
         DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + at, static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off, bytes,
                                     hipMemcpyDeviceToHost, stream));
+        if (co) {
+          DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + wat, static_cast<const int32_t*>(d_cword.ptr) + p.ev_off,
+                                      n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        }
       }
       at += bytes;
+      if (co) wat += n_ev * sizeof(int32_t);
+    }
+    if (packed_sites) {
+      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + sites_at, d_cpsite.ptr, packed_sites * sizeof(dv_candidate_site),
+                                  hipMemcpyDeviceToHost, stream));
+    }
+    if (packed_alleles && !pos_only) {
+      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + alleles_at, d_cpall.ptr, packed_alleles * sizeof(dv_candidate_allele),
+                                  hipMemcpyDeviceToHost, stream));
     }
     if (packed_blocks) {
       DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + packed_at, d_gpack.ptr, packed_blocks * sizeof(dv_gvcf_block),
@@ -900,13 +1150,33 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     }
     DV_HIP_CHECK(hipStreamSynchronize(stream));
     at = 0;
+    wat = words_at;
     for (int32_t k = 0; k < n; ++k) {
       const Plan& p = plan[k];
-      if (!p.batched || !out[k]) continue;
+      if (!p.batched || pos_only) continue;
       const size_t n_ev = ctrs[static_cast<size_t>(k) * 4];
       if (n_ev) std::memcpy(out[k]->raw.ptr, h_ev.ptr + at, n_ev * sizeof(dv_allele_event));
       at += n_ev * sizeof(dv_allele_event);
-      order_events(out[k], n_ev);
+      if (co) {
+        order_events_with_words(out[k], n_ev, reinterpret_cast<const int32_t*>(h_ev.ptr + wat), &cout[k]->words);
+        wat += n_ev * sizeof(int32_t);
+      } else {
+        order_events(out[k], n_ev);
+      }
+    }
+    if (co) {
+      size_t sat = sites_at, aat = alleles_at;
+      for (int32_t k = 0; k < n; ++k) {
+        if (plan[k].cd_slot < 0) continue;
+        const size_t sbytes = static_cast<size_t>(ncand[2 * k]) * sizeof(dv_candidate_site);
+        const size_t abytes = static_cast<size_t>(ncand[2 * k + 1]) * sizeof(dv_candidate_allele);
+        if (plan[k].batched) {
+          if (sbytes) std::memcpy(cout[k]->sites.data(), h_ev.ptr + sat, sbytes);
+          if (abytes && !pos_only) std::memcpy(cout[k]->alleles.data(), h_ev.ptr + aat, abytes);
+        }
+        sat += sbytes;
+        aat += abytes;
+      }
     }
     at = packed_at;
     for (int32_t k = 0; k < n; ++k) {
@@ -918,8 +1188,11 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     }
   }
   for (int32_t k = 0; k < n; ++k) {
-    if (out[k]) continue;
+    if (done[k]) continue;
     if (int rc = dv_count_alleles(reads[k], options[k], &out[k], stream_v)) return rc;
+    if (co) {
+      if (int rc = candidates_from_counts(out[k], options[k], reads[k], keys_of(k), co, stream, &cout[k])) return rc;
+    }
     if (gv) {
       if (!d_table) {
         if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
@@ -930,20 +1203,46 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
   return DV_OK;
   };
   const int rc = body();
-  return rc == DV_OK ? DV_OK : fail_all(rc);
+  if (rc != DV_OK) return fail_all(rc);
+  for (dv_allele_counts* c : own_out) delete c;
+  return DV_OK;
 }
 
 int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                            dv_allele_counts** out, void* stream_v) {
-  return count_batch(n, reads, options, nullptr, nullptr, out, nullptr, stream_v, "dv_count_alleles_batch");
+  return count_batch(n, reads, options, nullptr, nullptr, nullptr, out, nullptr, nullptr, stream_v, "dv_count_alleles_batch");
 }
 
 int dv_count_alleles_gvcf_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                                 const int32_t* const* read_keys, const dv_gvcf_options* gvcf,
                                 dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out, void* stream) {
   if (!gvcf) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles_gvcf_batch: gvcf options are null");
-  return count_batch(n, reads, options, read_keys, gvcf, counts_out, blocks_out, stream, "dv_count_alleles_gvcf_batch");
+  return count_batch(n, reads, options, read_keys, gvcf, nullptr, counts_out, blocks_out, nullptr, stream,
+                     "dv_count_alleles_gvcf_batch");
 }
+
+int dv_call_candidates_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                             const int32_t* const* read_keys, const dv_candidate_options* candidate_options,
+                             const dv_gvcf_options* gvcf, dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out,
+                             dv_candidates** candidates_out, void* stream) {
+  if (!candidate_options) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_call_candidates_batch: candidate options are null");
+  return count_batch(n, reads, options, read_keys, gvcf, candidate_options, counts_out, blocks_out, candidates_out, stream,
+                     "dv_call_candidates_batch");
+}
+
+int64_t dv_candidates_arrays(const dv_candidates* c, const dv_candidate_site** sites,
+                             const dv_candidate_allele** alleles, int32_t* n_alleles, const int32_t** event_words,
+                             uint32_t* n_events) {
+  if (!c) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_candidates_arrays: null");
+  if (sites) *sites = c->sites.data();
+  if (alleles) *alleles = c->alleles.data();
+  if (n_alleles) *n_alleles = static_cast<int32_t>(c->alleles.size());
+  if (event_words) *event_words = c->words.data();
+  if (n_events) *n_events = static_cast<uint32_t>(c->words.size());
+  return static_cast<int64_t>(c->sites.size());
+}
+
+void dv_candidates_free(dv_candidates* c) { delete c; }
 
 int64_t dv_gvcf_blocks_arrays(const dv_gvcf_blocks* b, const dv_gvcf_block** blocks) {
   if (!b) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_gvcf_blocks_arrays: null");

@@ -2,7 +2,8 @@
 // counter kernel left on the device (allele_counter.hip), queued behind it on the same stream.
 //
 // Five launches per batch of regions (blockIdx.y / blockIdx.x = region), no synchronisation:
-//   gvcf_link     every event pushed on a per-position list (atomicExch on the list head)
+//   gvcf_link     every event pushed on a per-position list (atomicExch on the list head; event_lists.h,
+//                 shared with candidates.hip)
 //   gvcf_resolve  per event: is it the last allele of its read key at its position (read_alleles is a
 //                 map keyed by read key: a later allele of the same key overwrites)?  If so and it is
 //                 neither low quality nor REFERENCE, it adds one to the position's non-reference count
@@ -17,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "event_lists.h"
 #include "gvcf.h"
 
 // the layouts deepvariant_amd/_lib.py mirrors
@@ -29,10 +31,6 @@ namespace {
 constexpr int kThreads = 256;
 
 __device__ __forceinline__ bool canonical_base(uint8_t b) { return b == 'A' || b == 'C' || b == 'G' || b == 'T'; }
-
-__device__ __forceinline__ int32_t key_of(const dv::GvcfRegion& g, uint32_t read) {
-  return g.read_key ? g.read_key[read] : static_cast<int32_t>(read);
-}
 
 // scratch slices (dv::gvcf_scratch_ints)
 struct Slices {
@@ -56,33 +54,27 @@ __device__ __forceinline__ uint32_t n_events(const dv::GvcfRegion& g) {
   return n < g.event_cap ? n : g.event_cap;
 }
 
+__device__ __forceinline__ dv::EventLists lists(const dv::GvcfRegion& g, const Slices& s) {
+  return dv::EventLists{g.events, g.read_key, s.head, s.next};
+}
+
 __global__ __launch_bounds__(kThreads) void gvcf_link_kernel(const dv::GvcfRegion* regions) {
   const dv::GvcfRegion& g = regions[blockIdx.y];
-  const Slices s = slices(g);
+  const dv::EventLists l = lists(g, slices(g));
   const uint32_t n = n_events(g);
-  for (uint32_t e = blockIdx.x * kThreads + threadIdx.x; e < n; e += gridDim.x * kThreads) {
-    const int32_t p = g.events[e].position;     // the counter emits positions inside the interval only
-    s.next[e] = atomicExch(&s.head[p], static_cast<int32_t>(e + 1));
-  }
+  for (uint32_t e = blockIdx.x * kThreads + threadIdx.x; e < n; e += gridDim.x * kThreads) dv::link_event(l, e);
 }
 
 __global__ __launch_bounds__(kThreads) void gvcf_resolve_kernel(const dv::GvcfRegion* regions) {
   const dv::GvcfRegion& g = regions[blockIdx.y];
   const Slices s = slices(g);
+  const dv::EventLists l = lists(g, s);
   const uint32_t n = n_events(g);
   for (uint32_t e = blockIdx.x * kThreads + threadIdx.x; e < n; e += gridDim.x * kThreads) {
     const dv_allele_event ev = g.events[e];
     const uint32_t type = (ev.length_type >> 28) & 7u;
     if ((ev.length_type >> 31) || type == 1u) continue;        // low quality or REFERENCE: never counted
-    const int32_t key = key_of(g, ev.read);
-    bool last = true;
-    for (int32_t j = s.head[ev.position]; j != 0 && last; j = s.next[j - 1]) {
-      const dv_allele_event o = g.events[j - 1];
-      if (static_cast<uint32_t>(j - 1) == e || key_of(g, o.read) != key) continue;
-      // the host's order of one position's events is (read, read_offset): the larger one is stored later
-      last = !(o.read > ev.read || (o.read == ev.read && o.read_offset > ev.read_offset));
-    }
-    if (last) atomicAdd(&s.alt[ev.position], 1);
+    if (dv::event_stands(l, e, ev)) atomicAdd(&s.alt[ev.position], 1);
   }
 }
 

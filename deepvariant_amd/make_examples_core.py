@@ -296,7 +296,7 @@ class RegionProcessor:
     if po.gvcf:
       # summary_counts(left_padding, right_padding): the padding of a padded region is not reported
       opts = self._gvcf_options(region.start - effective.start, effective.end - region.end)
-      allelecounter.AlleleCounter.run_batch([counter], gvcf=opts)
+      allelecounter.AlleleCounter.run_batch([counter], gvcf=opts, **self._device_call())
       self.gvcf_records = [counter.gvcf_blocks(opts)]
     candidates = self.variant_caller.calls_from_allele_counter(counter)
     if self.direct_phasing is not None:
@@ -311,6 +311,13 @@ class RegionProcessor:
     if padded_region is not None:                 # filter_candidates_by_region, :2579-2606
       candidates = [c for c in candidates if region.start <= c.variant.start < region.end]
     return candidates
+
+  def _device_call(self, positions_only: bool = False) -> dict:
+    """run_batch's `call=` argument when the counter offers the device candidate caller (candidates.hip):
+    the candidates then come out of the counting pass; {} otherwise (the caller walks the counts)."""
+    if getattr(allelecounter.AlleleCounter, 'candidates', None) is None:
+      return {}
+    return {'call': self.variant_caller.candidate_options(positions_only)}
 
   def _gvcf_options(self, left_padding: int = 0, right_padding: int = 0) -> 'variant_calling.GvcfOptions':
     caller_options = self.variant_caller._options          # pylint: disable=protected-access
@@ -401,8 +408,9 @@ class RegionProcessor:
                      ) -> List[Tuple[List[T.DeepVariantCall], 'packing.ReadTable']]:
     """Candidates of a batch of calling regions: -> [(candidates, realigned table)] per region.  The
     regions' allele counters are filled in one device call per pass (AlleleCounter.run_batch: one
-    upload, kernels back to back -- two passes with track_ref_reads), the caller then reads each
-    region's counts on its own."""
+    upload, kernels back to back -- two passes with track_ref_reads, the first of which brings home
+    the candidate positions only), and the candidate caller runs behind the counter on the device
+    (AlleleCounter.candidates); the calls are then built region by region for its sites."""
     if realigned_tables is None:
       realigned_tables = self.realign_tables(tables, regions)
     out = [([], realigned) for realigned in realigned_tables]
@@ -412,22 +420,22 @@ class RegionProcessor:
       if len(rows):
         slots.append(k)
         in_region.append(realigned.take(rows))
-    run_batch = getattr(allelecounter.AlleleCounter, 'run_batch', None) or (lambda counters: None)
+    run_batch = getattr(allelecounter.AlleleCounter, 'run_batch', None) or (lambda counters, **kwargs: None)
     positions = [()] * len(slots)
     if self.processor_options.track_ref_reads:
       first_pass = [self._allele_counter(regions[k], t) for k, t in zip(slots, in_region)]
-      run_batch(first_pass)
+      run_batch(first_pass, **self._device_call(positions_only=True))
       positions = [self.variant_caller.call_positions_from_allele_counter(c) for c in first_pass]
     counters = [self._allele_counter(regions[k], t, p) for k, t, p in zip(slots, in_region, positions)]
     if self.processor_options.gvcf:
       # the same counts, with the regions' gVCF blocks computed behind them on the device
       opts = self._gvcf_options()
-      allelecounter.AlleleCounter.run_batch(counters, gvcf=opts)
+      allelecounter.AlleleCounter.run_batch(counters, gvcf=opts, **self._device_call())
       self.gvcf_records = [[] for _ in regions]
       for k, counter in zip(slots, counters):
         self.gvcf_records[k] = counter.gvcf_blocks(opts)
     else:
-      run_batch(counters)
+      run_batch(counters, **self._device_call())
     for k, counter in zip(slots, counters):
       out[k] = (self.variant_caller.calls_from_allele_counter(counter), realigned_tables[k])
     return out

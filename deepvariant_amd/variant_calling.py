@@ -23,6 +23,13 @@ make_gvcfs with nucleus genomics_math.normalize_log10_probs / log10_ptrue_to_phr
 tabulates it for the device pass (allelecounter.AlleleCounter.gvcf_blocks) and `make_gvcfs` merges
 sites into blocks on the host -- the checker, and the route for callers that hold Python counts.
 Which points of it rest on memory rather than the reference's source: DESIGN.md section 9.
+
+Candidates on the device: when the allele counter offers `candidates` /
+`candidate_positions` (allelecounter.AlleleCounter over deepvariant_amd/csrc/candidates.hip),
+calls_from_allele_counter / call_positions_from_allele_counter take the sites the device selected and
+build DeepVariantCalls for those only.  call_variant / calls_from_allele_counts / select_alt_alleles
+stay the restatement of the rules, the checker of the device route, and the route for callers that
+hold Python counts.
 """
 from __future__ import annotations
 
@@ -158,6 +165,42 @@ class GvcfOptions:
   def key(self) -> tuple:
     return (self.sample_name, self.p_error, self.max_gq, self.gq_resolution, self.max_cache_coverage,
             self.include_med_dp, self.left_padding, self.right_padding)
+
+
+class CandidateOptions:
+  """What the device candidate pass needs (dv_candidate_options): the caller's thresholds, with the
+  fractions rounded to float32 as the reference's proto fields are."""
+
+  def __init__(self, min_count_snps: int = 0, min_count_indels: int = 0, min_fraction_snps: float = 0.0,
+               min_fraction_indels: float = 0.0, track_ref_reads: bool = False, positions_only: bool = False):
+    for value in (min_count_snps, min_count_indels, min_fraction_snps, min_fraction_indels):
+      if value < 0:
+        raise ValueError('candidate thresholds must be >= 0')
+    self.min_count_snps, self.min_count_indels = int(min_count_snps), int(min_count_indels)
+    self.min_fraction_snps = float(np.float32(min_fraction_snps))
+    self.min_fraction_indels = float(np.float32(min_fraction_indels))
+    self.track_ref_reads, self.positions_only = bool(track_ref_reads), bool(positions_only)
+
+  @classmethod
+  def from_caller_options(cls, options: VariantCallerOptions, positions_only: bool = False) -> 'CandidateOptions':
+    return cls(options.min_count_snps, options.min_count_indels, options.min_fraction_snps,
+               options.min_fraction_indels, options.track_ref_reads, positions_only)
+
+  def _with(self, positions_only: bool) -> 'CandidateOptions':
+    if self.positions_only == positions_only:
+      return self
+    return CandidateOptions(self.min_count_snps, self.min_count_indels, self.min_fraction_snps,
+                            self.min_fraction_indels, self.track_ref_reads, positions_only)
+
+  def positions_form(self) -> 'CandidateOptions':
+    return self._with(True)
+
+  def calls_form(self) -> 'CandidateOptions':
+    return self._with(False)
+
+  def key(self) -> tuple:
+    """What the selection depends on (a full pass answers a positions query with the same key)."""
+    return (self.min_count_snps, self.min_count_indels, self.min_fraction_snps, self.min_fraction_indels)
 
 
 def _deletion_size(allele) -> int:
@@ -312,6 +355,10 @@ class VariantCaller:
     alt_alleles = self.select_alt_alleles(allele_count)
     if not alt_alleles:
       return None                              # (KeepReferenceSite is not restated)
+    return self._call_with_alt_alleles(allele_count, alt_alleles, ac.total_allele_counts(allele_count))
+
+  def _call_with_alt_alleles(self, allele_count, alt_alleles, dp: int) -> T.DeepVariantCall:
+    """CallVariant behind SelectAltAlleles (:640-671); `dp` = TotalAlleleCounts(allele_count)."""
     refbases = calc_ref_bases(allele_count.ref_base, alt_alleles)
     allele_map = build_allele_map(alt_alleles, refbases)
     alternate_bases = sorted(allele_map.values())
@@ -321,7 +368,7 @@ class VariantCaller:
                         alternate_bases=alternate_bases,
                         calls=[T.VariantCall(call_set_name=self._options.sample_name, genotype=[-1, -1])])
     call = T.DeepVariantCall(variant=variant)
-    self._add_read_depths(allele_count, alt_alleles, allele_map, refbases, variant)
+    self._add_read_depths(allele_count, alt_alleles, allele_map, refbases, variant, dp)
     self._add_supporting_reads(allele_count.read_alleles, allele_map, refbases, call)
     return call
 
@@ -336,10 +383,21 @@ class VariantCaller:
   def _least_allele_count(self) -> int:
     return min(self._options.min_count_snps, self._options.min_count_indels)
 
+  def candidate_options(self, positions_only: bool = False) -> CandidateOptions:
+    return CandidateOptions.from_caller_options(self._options, positions_only)
+
   def calls_from_allele_counter(self, allele_counter) -> List[T.DeepVariantCall]:
+    on_device = getattr(allele_counter, 'candidates', None)
+    if on_device is not None:
+      # the device selected the alleles (candidates.hip); the calls are built for its sites only
+      return [self._call_with_alt_alleles(site, site.selected, site.total)
+              for site in on_device(self.candidate_options())]
     return self.calls_from_allele_counts(_worth_looking_at(allele_counter, self._least_allele_count()))
 
   def call_positions_from_allele_counter(self, allele_counter) -> List[int]:
+    on_device = getattr(allele_counter, 'candidate_positions', None)
+    if on_device is not None:
+      return on_device(self.candidate_options(positions_only=True))
     return self.call_positions_from_allele_counts(_worth_looking_at(allele_counter, self._least_allele_count()))
 
   def call_positions_from_allele_counts(self, allele_counts: Sequence) -> List[int]:
@@ -355,10 +413,11 @@ class VariantCaller:
     return out
 
   # ---- annotations
-  def _add_read_depths(self, allele_count, alt_alleles, allele_map, refbases, variant):
+  def _add_read_depths(self, allele_count, alt_alleles, allele_map, refbases, variant, dp=None):
     """AddReadDepths (:298-351): DP, AD, VAF on the first call."""
     info = variant.calls[0].info
-    dp = ac.total_allele_counts(allele_count)
+    if dp is None:
+      dp = ac.total_allele_counts(allele_count)
     info['DP'] = T.ListValue(values=[T.Value(int_value=dp)])
     by_simplified = {}
     counts = {_allele_order(a): a.count for a in alt_alleles}

@@ -773,6 +773,66 @@ int dv_count_alleles_gvcf_batch(int32_t n, const dv_batch* const* reads, const d
 int64_t dv_gvcf_blocks_arrays(const dv_gvcf_blocks* b, const dv_gvcf_block** blocks);
 void dv_gvcf_blocks_free(dv_gvcf_blocks* b);
 
+/* ---- candidate caller (device) --------------------------------------------------
+ * VariantCaller::CallsFromAlleleCounter / CallPositionsFromAlleleCounts of the reference's
+ * deepvariant/variant_calling.cc:365-382 and variant_calling_multisample.cc:940-1004, single-sample form
+ * (SelectAltAlleles / IsGoodAltAllele :232-258 over SumAlleleCounts / TotalAlleleCounts,
+ * allelecounter.cc:78-203), computed behind the allele counter from the counts and events where they
+ * lie on the device.  Per interval position the later event of one read key stands; the standing
+ * events are grouped into alleles by (type, text) -- substitution: the base; deletion: length and
+ * anchor base; insertion / soft clip: length, anchor base and the inserted read bases -- low-quality
+ * events belonging to their group without counting; total = good non-REFERENCE events +
+ * ref_supporting_read_count; an allele is selected when it is neither REFERENCE nor SOFT_CLIP,
+ * count >= min_count_* and (1.0 * count) / total >= (double)min_fraction_* (the thresholds are proto
+ * `float` fields: the comparison is IEEE double against the float32 value), on an A/C/G/T reference
+ * base.  Not restated: multi-sample filtering, complex alleles, reference-site sampling, methylation. */
+typedef struct dv_candidate_options {
+  int32_t min_count_snps, min_count_indels;       /* VariantCallerOptions, >= 0 */
+  float min_fraction_snps, min_fraction_indels;   /* >= 0 */
+  int32_t track_ref_reads;   /* VariantCallerOptions.track_ref_reads: REFERENCE events (counter options'
+                                track_ref_reads) take part in the read-key rule and get "uncalled" words either
+                                way; the flag travels for the host, which names them only when it is set */
+  int32_t positions_only;    /* CallPositionsFromAlleleCounts: only the sites' offsets are produced; no
+                                events, counts, allele records or event words come back */
+} dv_candidate_options;
+
+typedef struct dv_candidate_site {   /* one position CallVariant returns a call for, in position order */
+  int32_t offset;         /* position - interval_start */
+  int32_t ref_count;      /* ref_supporting_read_count (AD[0]) */
+  int32_t total;          /* TotalAlleleCounts (DP) */
+  int32_t first_allele;   /* index of the site's first record among the region's allele records */
+  int32_t n_alleles;      /* selected alleles, >= 1 */
+} dv_candidate_site;
+
+typedef struct dv_candidate_allele {   /* one selected alternate allele */
+  uint32_t length_type;   /* as dv_allele_event.length_type, low-quality bit clear */
+  int32_t count;          /* good-quality reads that carry it */
+  uint32_t read, read_offset;   /* a representative event (the first in event order): where its text is */
+} dv_candidate_allele;
+
+#define DV_CANDIDATE_EVENT_UNCALLED (-1)      /* the event stands, its allele was not selected (UNCALLED_ALLELE) */
+#define DV_CANDIDATE_EVENT_OVERWRITTEN (-2)   /* a later event of the same read key replaced it */
+
+typedef struct dv_candidates dv_candidates;   /* owns the host copies of one region's result */
+
+/* dv_count_alleles_batch plus the candidates of every region from the same counts in the same device
+ * pass (no further synchronisation), and -- with `gvcf` / blocks_out, both optional -- the gVCF records
+ * of dv_count_alleles_gvcf_batch as well.  read_keys as there.  candidates_out[k] receives region k's
+ * sites (freed with dv_candidates_free); counts_out as for dv_count_alleles_batch.  With
+ * positions_only, counts_out may be NULL and is left untouched, and `gvcf` must be NULL.  Negative
+ * thresholds are DV_ERR_INVALID_ARGUMENT; on an error no result is left allocated. */
+int dv_call_candidates_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                             const int32_t* const* read_keys, const dv_candidate_options* candidate_options,
+                             const dv_gvcf_options* gvcf, dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out,
+                             dv_candidates** candidates_out, void* stream);
+/* -> the number of sites.  event_words[i] belongs to event i of dv_allele_counts_arrays: the ordinal
+ * (0 .. n_alleles - 1) of its site's selected allele that the event supports, or one of the two
+ * negative codes above; n_events is 0 with positions_only. */
+int64_t dv_candidates_arrays(const dv_candidates* c, const dv_candidate_site** sites,
+                             const dv_candidate_allele** alleles, int32_t* n_alleles, const int32_t** event_words,
+                             uint32_t* n_events);
+void dv_candidates_free(dv_candidates* c);
+
 /* CRC32C (Castagnoli) as used by TFRecord framing
  * (third_party/nucleus/io/example_writer.cc:88-104 via tensorflow::io::RecordWriter). */
 uint32_t dv_crc32c(const uint8_t* data, size_t n);
