@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     'dv_aligner_read_alignment', 'dv_aligner_merge_alignment', 'dv_aligner_is_normalized',
     'dv_aligner_score_threshold', 'dv_aligner_kmer_occurrences', 'dv_positions_map',
     'dv_merge_cigar_op', 'dv_local_align', 'dv_local_align_many',
+    'dv_local_align_pairs_device', 'dv_local_align_device_last_stats', 'dv_realign_regions_device',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
@@ -178,6 +179,16 @@ class DvLocalAlignment(C.Structure):
   _fields_ = [('score', C.c_int32), ('ref_begin', C.c_int32), ('ref_end', C.c_int32),
               ('query_begin', C.c_int32), ('query_end', C.c_int32), ('mismatches', C.c_int32),
               ('cigar', C.c_char * 512)]
+
+
+# include/dvhip.h: what one pair may measure for the device form of the local aligner (longer ones are
+# aligned by the host code inside the same call)
+DV_LOCAL_ALIGN_DEVICE_MAX_QUERY = 2048
+DV_LOCAL_ALIGN_DEVICE_MAX_REFERENCE = 65534
+
+
+class DvRealignDeviceStats(C.Structure):
+  _fields_ = [('pairs', C.c_int64), ('pairs_on_host', C.c_int64), ('cells', C.c_int64), ('launches', C.c_int64)]
 
 
 class DvDebruijnOptions(C.Structure):
@@ -383,6 +394,11 @@ def lib():
     l.dv_merge_cigar_op.argtypes = [C.c_void_p, C.c_int32, C.c_char, C.c_int32, C.c_int32]
     l.dv_local_align.argtypes = [C.c_char_p, C.c_char_p] + [C.c_int32] * 4 + [C.c_void_p]
     l.dv_local_align_many.argtypes = [C.c_char_p, C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]
+    l.dv_local_align_pairs_device.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
+                                              [C.c_int32] * 4 + [C.c_void_p, C.c_void_p])
+    l.dv_local_align_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     l.dv_debruijn_destroy.argtypes = [C.c_void_p]

@@ -14,6 +14,7 @@
 struct dv_aligner {
   dv::FastPassAligner a;
   std::vector<uint32_t> cigar_words;
+  bool in_phases = false;   // DV_ALIGNER_ALIGN_IN_PHASES
 };
 
 struct dv_debruijn_graph {
@@ -105,7 +106,17 @@ int dv_aligner_align_reads(dv_aligner* h, int32_t n, const char* const* sequence
   if (!h || n < 0 || (n && (!sequences || !out)) || !cigar) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_aligner_align_reads");
   }
-  const std::vector<dv::RealignedRead> res = h->a.align_reads(strings(n, sequences));
+  std::vector<dv::RealignedRead> res;
+  if (h->in_phases) {
+    dv::AlignmentPairs pairs;
+    h->a.prepare_alignments(strings(n, sequences), &pairs);
+    std::vector<dv::LocalAlignment> results;
+    std::vector<char> ok;
+    h->a.align_pairs_on_host(pairs, 0, pairs.pair_ref.size(), &results, &ok);
+    res = h->a.finish_alignments(pairs, results.data(), ok.data());
+  } else {
+    res = h->a.align_reads(strings(n, sequences));
+  }
   h->cigar_words.clear();
   for (int32_t i = 0; i < n; ++i) {
     out[i].status = res[i].status;
@@ -129,6 +140,7 @@ int dv_aligner_stage(dv_aligner* h, int32_t stage, int32_t arg) {
     case DV_ALIGNER_POSITION_MAPS: h->a.calculate_position_maps(); break;
     case DV_ALIGNER_LOCAL_ALIGN_READS: h->a.local_align_reads_to_haplotypes(arg); break;
     case DV_ALIGNER_SCORE_THRESHOLD: h->a.calculate_score_threshold(); break;
+    case DV_ALIGNER_ALIGN_IN_PHASES: h->in_phases = arg != 0; break;
     default: return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_aligner_stage: unknown stage");
   }
   return DV_OK;

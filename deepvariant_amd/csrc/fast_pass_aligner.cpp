@@ -240,7 +240,19 @@ void FastPassAligner::init_local_aligner() {   // InitSswLib, :155-160
   aligner_ = std::make_unique<LocalAligner>(match_, mismatch_, gap_open_, gap_extend_);
 }
 
-void FastPassAligner::align_haplotypes_to_reference() {   // :336-375
+void FastPassAligner::align_pairs_on_host(const AlignmentPairs& pairs, size_t first, size_t last,
+                                          std::vector<LocalAlignment>* results, std::vector<char>* ok) const {
+  std::vector<const CodedSequence*> refs, queries;
+  refs.reserve(last - first);
+  queries.reserve(last - first);
+  for (size_t k = first; k < last; ++k) {
+    refs.push_back(&pairs.sequences[pairs.pair_ref[k]]);
+    queries.push_back(&pairs.sequences[pairs.pair_query[k]]);
+  }
+  aligner_->align_pairs(refs, queries, results, ok);
+}
+
+void FastPassAligner::collect_haplotype_pairs(AlignmentPairs* pairs) {   // :336-375, up to the alignments
   aligner_->set_reference(reference_);
   if (alignments_.empty()) {
     for (size_t i = 0; i < haplotypes_.size(); ++i) {
@@ -251,10 +263,11 @@ void FastPassAligner::align_haplotypes_to_reference() {   // :336-375
       alignments_.push_back(std::move(ha));
     }
   }
-  // the haplotypes that differ from the reference are aligned to it together (16 per SIMD batch)
-  std::vector<HaplotypeAlignment*> todo;
-  std::vector<std::string> queries;
-  for (HaplotypeAlignment& ha : alignments_) {
+  *pairs = AlignmentPairs();
+  pairs->haplotype_sequence.assign(alignments_.size(), -1);
+  // the haplotypes that differ from the reference are aligned to it together
+  for (size_t a = 0; a < alignments_.size(); ++a) {
+    HaplotypeAlignment& ha = alignments_[a];
     const std::string& hap = haplotypes_[ha.haplotype_index];
     if (hap == reference_) {
       ha.is_reference = true;
@@ -262,22 +275,37 @@ void FastPassAligner::align_haplotypes_to_reference() {   // :336-375
       ha.cigar_ops = parse_cigar(ha.cigar);
       ha.ref_pos = 0;
     } else {
-      todo.push_back(&ha);
-      queries.push_back(hap);
+      if (pairs->sequences.empty()) pairs->sequences.push_back(encode_sequence(reference_));
+      pairs->haplotype_sequence[a] = static_cast<int32_t>(pairs->sequences.size());
+      pairs->sequences.push_back(encode_sequence(hap));
+      pairs->haplotype_todo.push_back(a);
+      pairs->pair_ref.push_back(0);
+      pairs->pair_query.push_back(pairs->haplotype_sequence[a]);
     }
   }
-  std::vector<LocalAlignment> results;
-  std::vector<char> ok;
-  aligner_->align_many_to_reference(queries, &results, &ok);
-  for (size_t k = 0; k < todo.size(); ++k) {
+  pairs->n_haplotype_pairs = pairs->haplotype_todo.size();
+}
+
+void FastPassAligner::apply_haplotype_alignments(const AlignmentPairs& pairs, const LocalAlignment* results,
+                                                 const char* ok) {
+  for (size_t k = 0; k < pairs.haplotype_todo.size(); ++k) {
     const LocalAlignment& al = results[k];
     if (!ok[k] || al.score <= 0) continue;
-    HaplotypeAlignment& ha = *todo[k];
-    ha.is_reference = al.cigar == std::to_string(queries[k].size()) + "=";
+    HaplotypeAlignment& ha = alignments_[pairs.haplotype_todo[k]];
+    ha.is_reference = al.cigar == std::to_string(haplotypes_[ha.haplotype_index].size()) + "=";
     ha.cigar = al.cigar;
     ha.cigar_ops = parse_cigar(al.cigar);
     ha.ref_pos = static_cast<uint64_t>(al.ref_begin);
   }
+}
+
+void FastPassAligner::align_haplotypes_to_reference() {   // :336-375
+  AlignmentPairs pairs;
+  collect_haplotype_pairs(&pairs);
+  std::vector<LocalAlignment> results;
+  std::vector<char> ok;
+  align_pairs_on_host(pairs, 0, pairs.n_haplotype_pairs, &results, &ok);
+  apply_haplotype_alignments(pairs, results.data(), ok.data());
 }
 
 void FastPassAligner::calculate_position_maps() {   // :652-657
@@ -286,52 +314,72 @@ void FastPassAligner::calculate_position_maps() {   // :652-657
   }
 }
 
-void FastPassAligner::local_align_reads_to_haplotypes(int score_threshold) {   // :377-418
-  const int threshold = static_cast<uint16_t>(score_threshold);
+// The (unplaced read, haplotype) pairs of SswAlignReadsToHaplotypes, :377-418, appended to `pairs`.  A
+// haplotype is a target when the fast pass gave it a score, or under force_alignment when it is the
+// reference; with !reference_known (its alignment to the reference is still to come) every
+// haplotype may turn out to be the reference, and apply_read_alignments() drops the ones that do not.
+void FastPassAligner::collect_read_pairs(bool reference_known, AlignmentPairs* pairs) const {
+  pairs->haplotype_sequence.resize(alignments_.size(), -1);
   // the haplotypes a read is aligned to do not depend on the read: encode them once
-  std::vector<HaplotypeAlignment*> targets;
-  std::vector<CodedSequence> coded;
-  for (HaplotypeAlignment& ha : alignments_) {
-    const bool forced = force_alignment_ && ha.is_reference;
+  for (size_t a = 0; a < alignments_.size(); ++a) {
+    const HaplotypeAlignment& ha = alignments_[a];
+    const bool forced = force_alignment_ && (ha.is_reference || !reference_known);
     if (ha.haplotype_score == 0 && !forced) continue;
-    targets.push_back(&ha);
-    coded.push_back(encode_sequence(haplotypes_[ha.haplotype_index]));
+    pairs->read_targets.push_back(a);
   }
-  // every (unplaced read, haplotype) pair goes through the aligner in one batch call: its SIMD
-  // lanes take 16 pairs at a time whatever read or haplotype they belong to
-  std::vector<size_t> unplaced;
-  std::vector<CodedSequence> coded_reads;
   for (size_t r = 0; r < reads_.size(); ++r) {
     bool aligned = false;
     for (const HaplotypeAlignment& ha : alignments_) aligned = aligned || ha.reads[r].score > 0;
-    if (aligned || targets.empty()) continue;
-    unplaced.push_back(r);
-    coded_reads.push_back(encode_sequence(reads_[r]));
+    if (aligned || pairs->read_targets.empty()) continue;
+    pairs->unplaced_reads.push_back(r);
   }
-  std::vector<const CodedSequence*> refs, queries;
-  for (size_t u = 0; u < unplaced.size(); ++u) {
-    for (const CodedSequence& c : coded) {
-      refs.push_back(&c);
-      queries.push_back(&coded_reads[u]);
+  if (pairs->unplaced_reads.empty()) return;
+  for (size_t a : pairs->read_targets) {
+    if (pairs->haplotype_sequence[a] < 0) {
+      pairs->haplotype_sequence[a] = static_cast<int32_t>(pairs->sequences.size());
+      pairs->sequences.push_back(encode_sequence(haplotypes_[alignments_[a].haplotype_index]));
     }
   }
-  std::vector<LocalAlignment> results;
-  std::vector<char> ok;
-  aligner_->align_pairs(refs, queries, &results, &ok);
-  for (size_t u = 0; u < unplaced.size(); ++u) {
-    const size_t r = unplaced[u];
-    for (size_t t = 0; t < targets.size(); ++t) {
-      HaplotypeAlignment& ha = *targets[t];
-      const size_t k = u * targets.size() + t;
+  // every (unplaced read, haplotype) pair goes through the aligner in one batch call: its SIMD
+  // lanes take 16 pairs at a time whatever read or haplotype they belong to
+  for (size_t r : pairs->unplaced_reads) {
+    const int32_t read_sequence = static_cast<int32_t>(pairs->sequences.size());
+    pairs->sequences.push_back(encode_sequence(reads_[r]));
+    for (size_t a : pairs->read_targets) {
+      pairs->pair_ref.push_back(pairs->haplotype_sequence[a]);
+      pairs->pair_query.push_back(read_sequence);
+    }
+  }
+}
+
+void FastPassAligner::apply_read_alignments(const AlignmentPairs& pairs, int score_threshold,
+                                            const LocalAlignment* results, const char* ok) {
+  const int threshold = static_cast<uint16_t>(score_threshold);
+  for (size_t u = 0; u < pairs.unplaced_reads.size(); ++u) {
+    const size_t r = pairs.unplaced_reads[u];
+    for (size_t t = 0; t < pairs.read_targets.size(); ++t) {
+      HaplotypeAlignment& ha = alignments_[pairs.read_targets[t]];
+      const bool forced = force_alignment_ && ha.is_reference;
+      if (ha.haplotype_score == 0 && !forced) continue;     // collected before is_reference was known
+      const size_t k = u * pairs.read_targets.size() + t;
       const LocalAlignment& al = results[k];
       if (!ok[k] || al.score <= 0) continue;
-      if (al.score >= threshold || (force_alignment_ && ha.is_reference)) {
+      if (al.score >= threshold || forced) {
         ha.reads[r].score = al.score;
         ha.reads[r].cigar = al.cigar;
         ha.reads[r].position = static_cast<uint16_t>(al.ref_begin);
       }
     }
   }
+}
+
+void FastPassAligner::local_align_reads_to_haplotypes(int score_threshold) {   // :377-418
+  AlignmentPairs pairs;
+  collect_read_pairs(true, &pairs);
+  std::vector<LocalAlignment> results;
+  std::vector<char> ok;
+  align_pairs_on_host(pairs, 0, pairs.pair_ref.size(), &results, &ok);
+  apply_read_alignments(pairs, score_threshold, results.data(), ok.data());
 }
 
 bool FastPassAligner::best_read_alignment(size_t read, int* best_hap) const {   // :659-674
@@ -474,12 +522,16 @@ bool FastPassAligner::is_alignment_normalized(const Cigar& cigar, int ref_offset
 }
 
 // ---------------------------------------------------------------- entry point
-std::vector<RealignedRead> FastPassAligner::align_reads(const std::vector<std::string>& sequences) {   // :131-177
+void FastPassAligner::add_reads(const std::vector<std::string>& sequences) {
   for (const std::string& s : sequences) {
     std::string up(s);
     for (char& c : up) c = static_cast<char>(std::toupper(static_cast<unsigned char>(c)));
     reads_.push_back(std::move(up));
   }
+}
+
+std::vector<RealignedRead> FastPassAligner::align_reads(const std::vector<std::string>& sequences) {   // :131-177
+  add_reads(sequences);
   calculate_score_threshold();
   build_index();
   fast_align_reads_to_haplotypes();
@@ -487,13 +539,36 @@ std::vector<RealignedRead> FastPassAligner::align_reads(const std::vector<std::s
   align_haplotypes_to_reference();
   calculate_position_maps();
   local_align_reads_to_haplotypes(score_threshold_);
+  return realign_reads_to_reference(sequences.size());
+}
+
+void FastPassAligner::prepare_alignments(const std::vector<std::string>& sequences, AlignmentPairs* pairs) {
+  add_reads(sequences);
+  calculate_score_threshold();
+  build_index();
+  fast_align_reads_to_haplotypes();
+  init_local_aligner();
+  collect_haplotype_pairs(pairs);
+  collect_read_pairs(false, pairs);
+  pairs->n_input_reads = sequences.size();
+}
+
+std::vector<RealignedRead> FastPassAligner::finish_alignments(const AlignmentPairs& pairs,
+                                                              const LocalAlignment* results, const char* ok) {
+  apply_haplotype_alignments(pairs, results, ok);
+  calculate_position_maps();
+  apply_read_alignments(pairs, score_threshold_, results + pairs.n_haplotype_pairs, ok + pairs.n_haplotype_pairs);
+  return realign_reads_to_reference(pairs.n_input_reads);
+}
+
+std::vector<RealignedRead> FastPassAligner::realign_reads_to_reference(size_t n_reads) {
   std::sort(alignments_.begin(), alignments_.end(),
             [](const HaplotypeAlignment& a, const HaplotypeAlignment& b) {
               return a.haplotype_score < b.haplotype_score;
             });
   // RealignReadsToReference, :486-571
-  std::vector<RealignedRead> out(sequences.size());
-  for (size_t r = 0; r < sequences.size(); ++r) {
+  std::vector<RealignedRead> out(n_reads);
+  for (size_t r = 0; r < n_reads; ++r) {
     int best = -1;
     if (!best_read_alignment(r, &best)) {
       out[r].status = force_alignment_ ? 2 : 0;

@@ -72,6 +72,21 @@ struct RealignedRead {
   Cigar cigar;
 };
 
+// The local alignments a window needs, as pairs of indices into a table of unique coded sequences
+// (the reference, each haplotype and each read appear once however many pairs use them): first the
+// haplotype -> reference pairs, then the read -> haplotype pairs.  Filled by the collect_* steps,
+// read back by the apply_* steps; any aligner that gives LocalAligner's results can run in between.
+struct AlignmentPairs {
+  std::vector<CodedSequence> sequences;
+  std::vector<int32_t> pair_ref, pair_query;        // pair k = (sequences[pair_ref[k]], sequences[pair_query[k]])
+  size_t n_haplotype_pairs = 0;
+  size_t n_input_reads = 0;
+  // bookkeeping between collect and apply
+  std::vector<int32_t> haplotype_sequence;          // per haplotype alignment: its entry in `sequences`, or -1
+  std::vector<size_t> haplotype_todo;               // haplotype alignment of each haplotype -> reference pair
+  std::vector<size_t> read_targets, unplaced_reads; // read pair (u, t) = unplaced_reads[u] x read_targets[t]
+};
+
 class FastPassAligner {
  public:
   void set_reference(const std::string& r) { reference_ = r; }
@@ -84,6 +99,23 @@ class FastPassAligner {
   bool set_options(const AlignerOptions& o, std::string* error);
 
   std::vector<RealignedRead> align_reads(const std::vector<std::string>& sequences);
+
+  // align_reads() in three steps, for a caller that runs the local alignments of many windows in
+  // one batch (the device route of dv_realign_regions_device):
+  //   prepare_alignments   everything up to the local alignments; `pairs` lists both groups at once
+  //   (the caller)         results[k], ok[k] = LocalAligner::align for pair k
+  //   finish_alignments    position maps, thresholds, best alignment per read, merge, normalisation
+  // The read pairs are chosen before the haplotype -> reference results exist.  Those results only
+  // decide a target under force_alignment (is_reference), so there every haplotype is aligned
+  // against and the results of the ones that turn out not to be targets are dropped: the outcome is
+  // align_reads()'s, field for field.
+  void prepare_alignments(const std::vector<std::string>& sequences, AlignmentPairs* pairs);
+  std::vector<RealignedRead> finish_alignments(const AlignmentPairs& pairs, const LocalAlignment* results,
+                                               const char* ok);   // [pairs.pair_ref.size()]
+  // pairs [first, last) through the host aligner
+  void align_pairs_on_host(const AlignmentPairs& pairs, size_t first, size_t last, std::vector<LocalAlignment>* results,
+                           std::vector<char>* ok) const;
+  const LocalAligner& local_aligner() const { return *aligner_; }
 
   void build_index();
   void fast_align_reads_to_haplotype(std::string_view haplotype, int* haplotype_score,
@@ -107,6 +139,14 @@ class FastPassAligner {
 
  private:
   void fast_align_reads_to_haplotypes();
+  void add_reads(const std::vector<std::string>& sequences);
+  // the two halves of align_haplotypes_to_reference() and of local_align_reads_to_haplotypes()
+  void collect_haplotype_pairs(AlignmentPairs* pairs);
+  void apply_haplotype_alignments(const AlignmentPairs& pairs, const LocalAlignment* results, const char* ok);
+  void collect_read_pairs(bool reference_known, AlignmentPairs* pairs) const;
+  void apply_read_alignments(const AlignmentPairs& pairs, int score_threshold, const LocalAlignment* results,
+                             const char* ok);
+  std::vector<RealignedRead> realign_reads_to_reference(size_t n_reads);
   int fast_align_strings(std::string_view a, std::string_view b, int max_mismatches, int* mismatches) const;
 
   std::string reference_;

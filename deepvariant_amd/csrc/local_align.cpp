@@ -406,6 +406,16 @@ bool LocalAligner::finish(const CodedSequence& ref, const CodedSequence& q, int 
   return describe(ref, q, score1, ref_begin, ref_end, q_end - k, q_end, out);
 }
 
+bool LocalAligner::complete(const CodedSequence& ref, const CodedSequence& q, const SweepCorners& c,
+                            LocalAlignment* out) const {
+  *out = LocalAlignment();
+  if (ref.empty() || q.empty()) return false;
+  out->score = c.score;
+  if (c.score <= 0) return true;
+  if (c.reverse_score != c.score) return false;
+  return describe(ref, q, c.score, c.ref_begin, c.ref_end, c.query_begin, c.query_end, out);
+}
+
 // CIGAR and text form of the alignment whose corner points are known
 bool LocalAligner::describe(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_begin, int ref_end,
                             int q_begin, int q_end, LocalAlignment* out) const {

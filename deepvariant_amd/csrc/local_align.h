@@ -40,6 +40,15 @@ struct LocalAlignment {
 using CodedSequence = std::vector<int8_t>;
 CodedSequence encode_sequence(const std::string& s);
 
+// What the two sweeps of one alignment find: the end point of the forward pass and the begin
+// point of the pass over the reversed prefixes, in the sequences' own coordinates.  The device
+// form of the aligner (local_align_device.h) returns these; complete() turns them into the
+// LocalAlignment align() gives.
+struct SweepCorners {
+  int score = 0, ref_end = -1, query_end = -1;
+  int reverse_score = 0, ref_begin = -1, query_begin = -1;
+};
+
 class LocalAligner {
  public:
   LocalAligner(int match, int mismatch, int gap_open, int gap_extend);
@@ -61,6 +70,15 @@ class LocalAligner {
   void align_pairs(const std::vector<const CodedSequence*>& references,
                    const std::vector<const CodedSequence*>& queries, std::vector<LocalAlignment>* out,
                    std::vector<char>* ok) const;
+  // The rest of align() for a pair whose sweeps ran elsewhere: the banded CIGAR between the
+  // corner points.  Returns what align() returns: false for an empty sequence, or when the
+  // reverse pass did not reach the forward score.
+  bool complete(const CodedSequence& ref, const CodedSequence& q, const SweepCorners& corners,
+                LocalAlignment* out) const;
+  int match() const { return match_; }
+  int mismatch() const { return mismatch_; }
+  int gap_open() const { return gap_open_; }
+  int gap_extend() const { return gap_extend_; }
 
  private:
   int score(int8_t a, int8_t b) const { return mat_[a * 5 + b]; }

@@ -11,6 +11,15 @@
 //            the haplotypes padded with the reference out to the reads' span + margin
 //            (call_fast_pass_aligner, :740-793).
 //
+// dv_realign_regions_device is the same call with the local alignments of phase 2 on the device
+// (local_align.hip): phase 2 becomes
+//   2a, one task per window: the aligner is set up and runs up to its local alignments
+//       (FastPassAligner::prepare_alignments), leaving the pairs it needs;
+//   2b, once: the pairs of all windows go through one kernel launch; the CIGARs of the pairs that
+//       aligned (LocalAligner::complete) are spread over the worker pool;
+//   2c, one task per window: FastPassAligner::finish_alignments.
+// Phase 1, the read assignment and the result arrays are the same code for both routes.
+//
 // Tasks are independent (each builds its own graph / aligner; the aligner's scratch buffers are
 // thread_local), so a phase is a parallel loop over a task list ordered longest first.
 #include <algorithm>
@@ -31,6 +40,7 @@
 #include "debruijn_graph.h"
 #include "dv_internal.h"
 #include "fast_pass_aligner.h"
+#include "local_align_device.h"
 
 struct dv_realign_result {
   std::vector<int64_t> region_row_off;
@@ -49,6 +59,15 @@ struct Window {            // one candidate window of one region
   std::vector<std::string> haplotypes;   // empty: dropped
   std::vector<int32_t> rows;             // the reads it claimed, ascending
   std::vector<dv::RealignedRead> aligned;   // parallel to rows; empty: alignments kept
+  // device route, between 2a and 2c
+  std::unique_ptr<dv::FastPassAligner> aligner;
+  dv::AlignmentPairs pairs;
+  size_t first_pair = 0;                    // of this window in the batch's pair list
+};
+
+struct DeviceRoute {       // dv_realign_regions_device's extra arguments
+  void* stream;
+  dv_realign_device_stats* stats;
 };
 
 // The worker threads live as long as the library: no thread creation per call, and the aligner's
@@ -167,13 +186,13 @@ std::vector<int> longest_first(const std::vector<int64_t>& cost) {
 extern "C" {
 
 static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* o,
-                                dv_realign_result** out, dv_realign_output* arrays);
+                                dv_realign_result** out, dv_realign_output* arrays, const DeviceRoute* device);
 
 // The exception barrier of the entry point: nothing unwinds through extern "C" into ctypes.
 int dv_realign_regions(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* o,
                        dv_realign_result** out, dv_realign_output* arrays) {
   try {
-    return realign_regions_impl(regions, n_regions, o, out, arrays);
+    return realign_regions_impl(regions, n_regions, o, out, arrays, nullptr);
   } catch (const std::bad_alloc&) {
     if (out) *out = nullptr;
     return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_realign_regions: out of host memory");
@@ -183,8 +202,24 @@ int dv_realign_regions(const dv_realign_region* regions, int32_t n_regions, cons
   }
 }
 
+int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* o,
+                              void* stream, dv_realign_result** out, dv_realign_output* arrays,
+                              dv_realign_device_stats* stats) {
+  try {
+    if (stats) *stats = dv_realign_device_stats{0, 0, 0, 0};
+    const DeviceRoute device{stream, stats};
+    return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
+  } catch (const std::bad_alloc&) {
+    if (out) *out = nullptr;
+    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_realign_regions_device: out of host memory");
+  } catch (const std::exception& e) {
+    if (out) *out = nullptr;
+    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_realign_regions_device: ") + e.what());
+  }
+}
+
 static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* o,
-                                dv_realign_result** out, dv_realign_output* arrays) {
+                                dv_realign_result** out, dv_realign_output* arrays, const DeviceRoute* device) {
   if (!out || !arrays || !o || n_regions < 0 || (n_regions > 0 && !regions)) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_realign_regions: null argument");
   }
@@ -220,6 +255,12 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
       win.index = w;
       windows.push_back(std::move(win));
       cost.push_back((b - a) * static_cast<int64_t>(r.n_reads + 1));
+    }
+  }
+  if (device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
+      return dv::fail(DV_ERR_NO_DEVICE, "dv_realign_regions_device: no HIP device (dv_realign_regions is the host route)");
     }
   }
   int n_threads = o->n_threads;
@@ -311,7 +352,8 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
   }
   std::mutex error_lock;
   std::string error;
-  parallel_tasks(align_tasks, n_threads, [&](int t) {
+  // a window's aligner, set up, and its reads' bases; false: the original alignments stay (or `error` is set)
+  auto set_up = [&](int t, dv::FastPassAligner& aligner, std::vector<std::string>& sequences) -> bool {
     Window& win = windows[t];
     const dv_realign_region& r = regions[win.region];
     const int64_t a = r.window_start[win.index], b = r.window_end[win.index];
@@ -322,11 +364,11 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     }
     const int64_t ref_start = std::max<int64_t>(0, std::min(lo, a) - o->ref_align_margin);
     const int64_t ref_end = std::min(r.contig_len, std::max(hi, b) + o->ref_align_margin);
-    if (ref_end <= b) return;            // no room for a suffix: the original alignments stay
+    if (ref_end <= b) return false;      // no room for a suffix: the original alignments stay
     if (ref_start < r.ref_start || ref_end > r.ref_start + r.ref_len) {
       std::lock_guard<std::mutex> hold(error_lock);
       error = "dv_realign_regions: reads of a window reach outside the reference bases handed over";
-      return;
+      return false;
     }
     const std::string prefix(r.ref + (ref_start - r.ref_start), static_cast<size_t>(a - ref_start));
     const std::string window_ref(r.ref + (a - r.ref_start), static_cast<size_t>(b - a));
@@ -338,10 +380,10 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
       if (haplotypes.back().size() >= 0xffff) {
         std::lock_guard<std::mutex> hold(error_lock);
         error = "haplotypes are limited to 65534 bases (16-bit read offsets)";
-        return;
+        return false;
       }
     }
-    std::vector<std::string> sequences;
+    sequences.clear();
     sequences.reserve(win.rows.size());
     for (int32_t i : win.rows) {
       sequences.emplace_back(reinterpret_cast<const char*>(r.bases) + r.read_seq_off[i],
@@ -357,12 +399,11 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     ao.max_num_of_mismatches = o->aln.max_num_of_mismatches;
     ao.similarity_threshold = o->aln.realignment_similarity_threshold;
     ao.force_alignment = false;
-    dv::FastPassAligner aligner;
     std::string why;
     if (!aligner.set_options(ao, &why)) {
       std::lock_guard<std::mutex> hold(error_lock);
       error = why;
-      return;
+      return false;
     }
     aligner.set_normalize_reads(o->aln.normalize_reads != 0);
     aligner.set_ref_prefix_len(static_cast<int>(prefix.size()));
@@ -370,8 +411,87 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     aligner.set_reference(prefix + window_ref + suffix);
     aligner.set_ref_start(static_cast<uint64_t>(ref_start));
     aligner.set_haplotypes(haplotypes);
-    win.aligned = aligner.align_reads(sequences);
-  });
+    return true;
+  };
+  if (!device) {
+    parallel_tasks(align_tasks, n_threads, [&](int t) {
+      dv::FastPassAligner aligner;
+      std::vector<std::string> sequences;
+      if (set_up(t, aligner, sequences)) windows[t].aligned = aligner.align_reads(sequences);
+    });
+  } else {
+    // ---- 2a: everything up to the local alignments
+    parallel_tasks(align_tasks, n_threads, [&](int t) {
+      auto aligner = std::make_unique<dv::FastPassAligner>();
+      std::vector<std::string> sequences;
+      if (!set_up(t, *aligner, sequences)) return;
+      aligner->prepare_alignments(sequences, &windows[t].pairs);
+      windows[t].aligner = std::move(aligner);
+    });
+    if (!error.empty()) return dv::fail(DV_ERR_BAD_INPUT, error);
+    // ---- 2b: the pairs of all windows in one device call
+    std::vector<const dv::CodedSequence*> sequences;
+    std::vector<int32_t> pair_ref, pair_query;
+    const dv::LocalAligner* scoring = nullptr;     // the same for every window: it comes from `o`
+    for (int t : align_tasks) {
+      Window& win = windows[t];
+      if (!win.aligner) continue;
+      scoring = &win.aligner->local_aligner();
+      const int32_t base = static_cast<int32_t>(sequences.size());
+      for (const dv::CodedSequence& s : win.pairs.sequences) sequences.push_back(&s);
+      win.first_pair = pair_ref.size();
+      for (size_t k = 0; k < win.pairs.pair_ref.size(); ++k) {
+        pair_ref.push_back(base + win.pairs.pair_ref[k]);
+        pair_query.push_back(base + win.pairs.pair_query[k]);
+      }
+    }
+    std::vector<dv::LocalAlignment> results(pair_ref.size());
+    std::vector<char> ok(pair_ref.size(), 0);
+    if (!pair_ref.empty()) {
+      std::vector<dv::SweepCorners> corners;
+      std::vector<uint8_t> route;
+      dv::DeviceAlignStats stats;
+      if (int rc = dv::sweep_pairs_on_device(sequences, pair_ref, pair_query, scoring->match(), scoring->mismatch(),
+                                             scoring->gap_open(), scoring->gap_extend(), device->stream, &corners,
+                                             &route, &stats)) {
+        return rc;
+      }
+      if (device->stats) {
+        device->stats->pairs = stats.pairs;
+        device->stats->pairs_on_host = stats.pairs_on_host;
+        device->stats->cells = stats.cells;
+        device->stats->launches = stats.launches;
+      }
+      // the CIGARs (and the whole alignment of a pair outside the kernel's limits) on the worker pool
+      constexpr size_t kPairsPerTask = 16;
+      std::vector<int> chunks((pair_ref.size() + kPairsPerTask - 1) / kPairsPerTask);
+      for (size_t c = 0; c < chunks.size(); ++c) chunks[c] = static_cast<int>(c);
+      parallel_tasks(chunks, n_threads, [&](int c) {
+        const size_t end = std::min(pair_ref.size(), (static_cast<size_t>(c) + 1) * kPairsPerTask);
+        for (size_t k = static_cast<size_t>(c) * kPairsPerTask; k < end; ++k) {
+          const dv::CodedSequence& ref = *sequences[pair_ref[k]];
+          const dv::CodedSequence& q = *sequences[pair_query[k]];
+          if (route[k] == dv::kRouteDevice) {
+            ok[k] = scoring->complete(ref, q, corners[k], &results[k]);
+          } else if (route[k] == dv::kRouteHost) {
+            std::vector<dv::LocalAlignment> one;
+            std::vector<char> one_ok;
+            scoring->align_pairs({&ref}, {&q}, &one, &one_ok);
+            results[k] = std::move(one[0]);
+            ok[k] = one_ok[0];
+          }
+        }
+      });
+    }
+    // ---- 2c: the rest of align_reads per window
+    parallel_tasks(align_tasks, n_threads, [&](int t) {
+      Window& win = windows[t];
+      if (!win.aligner) return;
+      win.aligned = win.aligner->finish_alignments(win.pairs, results.data() + win.first_pair, ok.data() + win.first_pair);
+      win.aligner.reset();
+      win.pairs = dv::AlignmentPairs();
+    });
+  }
   if (!error.empty()) return dv::fail(DV_ERR_BAD_INPUT, error);
 
   // ---- results

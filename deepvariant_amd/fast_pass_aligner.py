@@ -216,6 +216,35 @@ def local_align_many(reference: str, queries: Sequence[str], match=2, mismatch=2
   return [None if out[k].score < 0 else out[k] for k in range(n)]
 
 
+def local_align_pairs_device(sequences: Sequence[str], pairs: Sequence[Tuple[int, int]], scoring=(2, 2, 3, 1),
+                             stream: int = 0, with_stats: bool = False):
+  """`local_align(sequences[r], sequences[q])` for every (r, q) of `pairs`, with the two Smith-Waterman
+  sweeps of all pairs in ONE kernel launch (csrc/local_align.hip) and the CIGARs built on the host.
+  `scoring` = (match, mismatch, gap_open, gap_extend).  An entry is None where local_align would
+  raise; pairs beyond the kernel's limits (_lib.DV_LOCAL_ALIGN_DEVICE_MAX_*) are aligned by the host
+  code inside the call.  There is no CPU fallback: without a GPU this raises DV_ERR_NO_DEVICE.
+  with_stats: -> (alignments, _lib.DvRealignDeviceStats of this call)."""
+  import numpy as np
+  raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
+  off = np.zeros(len(raw) + 1, np.int64)
+  np.cumsum([len(b) for b in raw], out=off[1:])
+  bases = b''.join(raw)
+  ref = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+  query = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+  n = len(ref)
+  out = (_lib.DvLocalAlignment * max(n, 1))()
+  match, mismatch, gap_open, gap_extend = scoring
+  _lib.check(_lib.lib().dv_local_align_pairs_device(len(raw), bases, off.ctypes.data, n, ref.ctypes.data,
+                                                    query.ctypes.data, match, mismatch, gap_open, gap_extend, out,
+                                                    stream or None))
+  res = [None if out[k].score < 0 else out[k] for k in range(n)]
+  if not with_stats:
+    return res
+  stats = _lib.DvRealignDeviceStats()
+  _lib.check(_lib.lib().dv_local_align_device_last_stats(C.byref(stats)))
+  return res, stats
+
+
 def realign_reads_to_haplotype(haplotype: str, reads: Sequence, contig: str, ref_start: int, ref_end: int,
                                ref_reader, aln_config: Optional[dict] = None) -> List[Optional[T.Read]]:
   """RealignReadsToHaplotype (alt_aligned_pileup_lib.cc:278-313).

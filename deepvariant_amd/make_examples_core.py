@@ -43,6 +43,7 @@ class RegionProcessorOptions:
   """The MakeExamplesOptions fields this slice reads (flag defaults of make_examples_options.py)."""
   realigner_enabled: bool = True
   realigner_options: Optional[realigner_module.RealignerOptions] = None    # None = realigner_config()
+  realign_on_device: Optional[bool] = None    # the table path's local alignments on the GPU; None = DV_REALIGN_DEVICE
   max_read_length_to_realign: int = 500
   vsc_min_count_snps: int = 2
   vsc_min_count_indels: int = 2
@@ -240,7 +241,7 @@ class RegionProcessor:
     self.realigner = None
     if po.realigner_enabled:
       self.realigner = realigner_module.Realigner(po.realigner_options or realigner_module.realigner_config(),
-                                                  ref_reader)
+                                                  ref_reader, device_align=po.realign_on_device)
     sample = options.sample_options[0]
     self.variant_caller = variant_calling.VariantCaller(variant_calling.VariantCallerOptions(
         po.vsc_min_count_snps, po.vsc_min_count_indels, po.vsc_min_fraction_snps, po.vsc_min_fraction_indels,

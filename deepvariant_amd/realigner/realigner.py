@@ -42,6 +42,9 @@ _THREADS = max(1, int(os.environ.get('DV_REALIGN_THREADS', '4')))
 # The table path hands all windows of a batch of regions to one native call (dv_realign_regions),
 # which runs them on its own host threads: DV_REALIGN_THREADS, or one per hardware thread up to 16.
 _NATIVE_THREADS = max(0, int(os.environ.get('DV_REALIGN_THREADS', '0')))
+# DV_REALIGN_DEVICE=1: the table path runs its local alignments on the GPU (dv_realign_regions_device).  Off by
+# default; the results are the host route's either way.
+_DEVICE_ALIGN = os.environ.get('DV_REALIGN_DEVICE', '0') == '1'
 _pool: Optional[concurrent.futures.ThreadPoolExecutor] = None
 
 
@@ -303,8 +306,10 @@ class RealignJob:
   """One dv_realign_regions call over a batch of regions: arguments marshalled by `add`, the native
   call in `start` (optionally on an executor thread), the write-back in `result`."""
 
-  def __init__(self, n_slots: int, want_haplotypes: bool, options: '_lib.DvRealignOptions'):
+  def __init__(self, n_slots: int, want_haplotypes: bool, options: '_lib.DvRealignOptions', device_align: bool = False):
     self.results: List = [None] * n_slots
+    self._device_align = device_align
+    self.device_stats = None       # _lib.DvRealignDeviceStats of the call, device route only
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -340,8 +345,16 @@ class RealignJob:
       d.ref, d.ref_start, d.ref_len, d.contig_len = ref, ref_lo, len(ref), n_contig
     handle = C.c_void_p()
     out = _lib.DvRealignOutput()
-    _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
-                                             C.byref(out)))
+    if self._device_align:
+      # the local alignments of all windows in one kernel launch, on a stream the library owns (this may be an
+      # executor thread: the native call sets up its own device context)
+      stats = _lib.DvRealignDeviceStats()
+      _lib.check(_lib.lib().dv_realign_regions_device(descs, len(self._jobs), C.byref(self._options), None,
+                                                      C.byref(handle), C.byref(out), C.byref(stats)))
+      self.device_stats = stats
+    else:
+      _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
+                                               C.byref(out)))
     return handle, out
 
   def start(self, executor=None) -> None:
@@ -407,10 +420,13 @@ class Realigner:
   """Realigner(config, ref_reader) (:675-893).  `ref_reader`: n_bases(contig) /
   get_bases(contig, start, end), as everywhere in this package."""
 
-  def __init__(self, config: RealignerOptions, ref_reader, shared_header=None):
+  def __init__(self, config: RealignerOptions, ref_reader, shared_header=None, device_align: Optional[bool] = None):
+    """device_align: the table path (realign_tables) aligns on the GPU; None = DV_REALIGN_DEVICE=1, off by
+    default.  The object path (realign_reads) always uses the host aligner."""
     self.config = config
     self.ref_reader = ref_reader
     self.shared_header = shared_header
+    self.device_align = _DEVICE_ALIGN if device_align is None else bool(device_align)
 
   # ---- reference access in the reference's terms
   def _is_valid(self, r: T.Range) -> bool:          # GenomeReference::IsValidInterval, reference.cc:95-102
@@ -528,7 +544,7 @@ class Realigner:
     holds no Python lock)."""
     if self.config.split_skip_reads:
       raise NotImplementedError('split_skip_reads works on Read objects (realign_reads)')
-    job = RealignJob(len(tables), want_haplotypes, self._native_options())
+    job = RealignJob(len(tables), want_haplotypes, self._native_options(), self.device_align)
     tables, regions = list(tables), list(regions)
     all_windows = window_selector.select_windows_of_tables(self.config.ws_config, self.ref_reader, tables, regions)
     for slot, (table, region, windows) in enumerate(zip(tables, regions, all_windows)):

@@ -498,7 +498,9 @@ enum {
   DV_ALIGNER_ALIGN_HAPLOTYPES = 2,   /* AlignHaplotypesToReference */
   DV_ALIGNER_POSITION_MAPS = 3,      /* CalculatePositionMaps */
   DV_ALIGNER_LOCAL_ALIGN_READS = 4,  /* SswAlignReadsToHaplotypes(arg = score threshold) */
-  DV_ALIGNER_SCORE_THRESHOLD = 5     /* CalculateSswAlignmentScoreThreshold */
+  DV_ALIGNER_SCORE_THRESHOLD = 5,    /* CalculateSswAlignmentScoreThreshold */
+  DV_ALIGNER_ALIGN_IN_PHASES = 6     /* test hook: arg != 0 makes dv_aligner_align_reads run as the device route
+                                        does -- prepare, ONE batch of pairs through the host aligner, finish */
 };
 int dv_aligner_stage(dv_aligner* a, int32_t stage, int32_t arg);
 int dv_aligner_fast_align(dv_aligner* a, const char* haplotype, int32_t* haplotype_score,
@@ -526,6 +528,32 @@ int dv_local_align(const char* reference, const char* query, int32_t match, int3
  * out[k].score = -1 where dv_local_align would fail (empty query). */
 int dv_local_align_many(const char* reference, int32_t n, const char* const* queries, int32_t match,
                         int32_t mismatch, int32_t gap_open, int32_t gap_extend, dv_local_alignment* out);
+
+/* The same alignments with the two Smith-Waterman sweeps on the device (csrc/local_align.hip): one upload,
+ * one kernel launch and one download for the whole list, on `stream` (a hipStream_t; NULL = a
+ * non-blocking stream the library owns); CIGARs are built on the host from the corner points.
+ * Sequences are ASCII: sequence s is bases[seq_off[s], seq_off[s + 1]); pair k aligns query
+ * pair_query[k] to reference pair_ref[k], so a sequence that many pairs share is uploaded once.
+ * out[k] is what dv_local_align(reference, query, ...) returns; out[k].score = -1 where it would fail
+ * (an empty sequence).  A pair outside the kernel's limits below is aligned by the host code
+ * inside the same call.  Argument errors (null pointers, descending offsets, an index out of
+ * range, negative counts, match outside [1, 127] or a penalty outside [0, 127] -- the host
+ * class keeps its score matrix in int8_t) are DV_ERR_INVALID_ARGUMENT before any device work;
+ * n_pairs = 0 is DV_OK without a device; no device is DV_ERR_NO_DEVICE. */
+#define DV_LOCAL_ALIGN_DEVICE_MAX_QUERY 2048        /* bases of a query the kernel holds in registers */
+#define DV_LOCAL_ALIGN_DEVICE_MAX_REFERENCE 65534   /* bases of a reference */
+typedef struct dv_realign_device_stats {
+  int64_t pairs;          /* alignments asked for */
+  int64_t pairs_on_host;  /* of them outside the kernel's limits: aligned by the host code */
+  int64_t cells;          /* sum of |reference| * |query| over the forward passes on the device */
+  int64_t launches;       /* kernel launches */
+} dv_realign_device_stats;
+int dv_local_align_pairs_device(int32_t n_seqs, const char* bases, const int64_t* seq_off, int32_t n_pairs,
+                                const int32_t* pair_ref, const int32_t* pair_query, int32_t match,
+                                int32_t mismatch, int32_t gap_open, int32_t gap_extend,
+                                dv_local_alignment* out, void* stream);
+/* What the calling thread's last dv_local_align_pairs_device did (for tests and tools). */
+int dv_local_align_device_last_stats(dv_realign_device_stats* out);
 
 /* ---- local assembly for the window realigner (host only) -----------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
@@ -610,6 +638,15 @@ typedef struct dv_realign_result dv_realign_result;
 int dv_realign_regions(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
                        dv_realign_result** out, dv_realign_output* arrays);
 void dv_realign_result_free(dv_realign_result* r);
+/* The same call with the local alignments of phase 2 on the device: the (haplotype, reference) and
+ * (read, haplotype) pairs of every window of the batch go through ONE dv_local_align_pairs_device-style
+ * launch on `stream` (NULL = the library's own), between a host loop that prepares the windows and one
+ * that finishes them.  `out` / `arrays` are identical, array by array, to dv_realign_regions' and are
+ * freed by dv_realign_result_free.  `stats` (may be NULL) receives what the device did.  Opt-in:
+ * dv_realign_regions itself never touches a device.  DV_ERR_NO_DEVICE without a GPU. */
+int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
+                              void* stream, dv_realign_result** out, dv_realign_output* arrays,
+                              dv_realign_device_stats* stats);
 
 /* ---- read phasing for the long-read path (host only) ---------------------------
  * Replaces deepvariant/direct_phasing.{h,cc} (DirectPhasing::PhaseReads / GetPhasedVariants;

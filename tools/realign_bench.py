@@ -1,0 +1,136 @@
+"""The window realigner over the NA12878 100 kb BAM's 1 kb calling regions in one batch, through
+Realigner.realign_tables: the host route (dv_realign_regions) against the device route
+(dv_realign_regions_device: the local alignments of all windows in one kernel launch, csrc/local_align.hip),
+alternating in one process.  The two routes' tables and haplotypes are compared before anything is timed.
+Prints one JSON line: per DV_REALIGN_THREADS setting (16 and 4) and per route the median wall time of
+realign_tables over --repeats batches after a warm-up, the share of it spent in the native call, every run's
+time (the spread), and the device route's stats: pairs, forward-pass cells, share of pairs aligned on the host.
+Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
+measures an older checkout.  Kernel time is not measured here: run this under
+`rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
+`cells` by local_align_sweeps' time per call.
+
+  python tools/realign_bench.py [--regions 100] [--repeats 7] [--threads 16,4] [--out result.json]
+"""
+import argparse
+import dataclasses
+import gc
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from deepvariant_amd import _lib                           # noqa: E402
+from deepvariant_amd import dv_types as T                  # noqa: E402
+from deepvariant_amd import packing                        # noqa: E402
+from deepvariant_amd.realigner import realigner as R       # noqa: E402
+
+
+class _Ref:
+  def __init__(self, seq, offset):
+    self.seq, self.offset = seq, offset
+
+  def n_bases(self, contig):
+    return self.offset + len(self.seq)
+
+  def get_bases(self, contig, start, end):
+    lo, hi = max(start, self.offset), min(end, self.offset + len(self.seq))
+    inner = self.seq[lo - self.offset:hi - self.offset] if hi > lo else ''
+    return 'N' * max(0, min(lo, end) - start) + inner + 'N' * max(0, end - max(hi, start))
+
+
+def _same(a, b):
+  for f in dataclasses.fields(packing.ReadTable):
+    x, y = getattr(a, f.name), getattr(b, f.name)
+    if not (np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y):
+      return False
+  return True
+
+
+def main(argv=None):
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--regions', type=int, default=100, help='calling regions per batch')
+  ap.add_argument('--repeats', type=int, default=7)
+  ap.add_argument('--threads', default='16,4', help='DV_REALIGN_THREADS settings to measure')
+  ap.add_argument('--out', default='')
+  args = ap.parse_args(argv)
+  if _lib.device_count() == 0:
+    raise SystemExit('realign_bench: no GPU (the device route has no CPU fallback)')
+  import torch
+  torch.cuda.init()
+  with np.load(os.path.join(ROOT, 'tests', 'golden', 'na12878_100kb.npz')) as z, tempfile.TemporaryDirectory() as tmp:
+    bam = os.path.join(tmp, 'reads.bam')
+    with open(bam, 'wb') as f:
+      f.write(z['bam'].tobytes())
+    with open(bam + '.bai', 'wb') as f:
+      f.write(z['bai'].tobytes())
+    ref = _Ref(z['ref_bases'].tobytes().decode(), int(z['ref_start'][0]))
+    lo, hi = ref.offset, ref.offset + len(ref.seq)
+    table = packing.ReadTable.from_bam(bam, 'chr20', lo, hi, min_mapping_quality=5)
+  ends, starts = table.read_end.astype(np.int64), table.read_pos.astype(np.int64)
+  batch = []
+  for start in range(lo, hi, 1000):
+    end = min(start + 1000, hi)
+    batch.append((T.Range('chr20', start, end), table.take(np.nonzero((ends > start) & (starts < end))[0])))
+  batch = [b for b in batch if b[1].n_reads][:args.regions]
+  regions, tables = [b[0] for b in batch], [b[1] for b in batch]
+  has_device = hasattr(_lib, 'DvRealignDeviceStats')
+  if has_device:
+    routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
+              'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
+  else:
+    routes = {'host': R.Realigner(R.realigner_config(), ref)}
+
+  def run(route):
+    gc.collect()
+    t0 = time.perf_counter()
+    job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
+    t1 = time.perf_counter()
+    out = job.result()                                                                    # the native call + write-back
+    t2 = time.perf_counter()
+    return t2 - t0, t2 - t1, out, getattr(job, 'device_stats', None)
+
+  # the routes must agree before either is timed (this is the warm-up too)
+  _, _, want, _ = run('host')
+  ms = lambda x: round(x * 1e3, 3)                         # noqa: E731
+  result = {'regions': len(regions), 'reads': int(sum(t.n_reads for t in tables)), 'device_route': has_device,
+            'threads': {}}
+  if has_device:
+    _, _, got, stats = run('device')
+    assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device route differs'
+    assert stats.pairs > 0 and stats.launches == 1
+    result['stats'] = {'pairs': stats.pairs, 'cells': stats.cells, 'pairs_on_host': stats.pairs_on_host,
+                       'share_on_host': round(stats.pairs_on_host / stats.pairs, 6), 'launches': stats.launches}
+  for threads in [int(t) for t in args.threads.split(',')]:
+    R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
+    runs = {route: [] for route in routes}
+    for route in runs:
+      run(route)
+    for _ in range(args.repeats):
+      for route in runs:                                    # alternating arms
+        whole, native, _, _ = run(route)
+        runs[route].append((whole, native))
+    entry = {}
+    for route, r in runs.items():
+      entry[route] = {'realign_tables_ms': ms(float(np.median([x[0] for x in r]))),
+                      'native_call_ms': ms(float(np.median([x[1] for x in r]))),
+                      'realign_tables_runs_ms': [ms(x[0]) for x in r],
+                      'native_call_runs_ms': [ms(x[1]) for x in r]}
+    if has_device:
+      entry['device_over_host_native'] = round(entry['device']['native_call_ms'] / entry['host']['native_call_ms'], 4)
+    result['threads'][str(threads)] = entry
+  line = json.dumps(result)
+  print(line)
+  if args.out:
+    with open(args.out, 'w') as f:
+      f.write(line + '\n')
+
+
+if __name__ == '__main__':
+  main()
