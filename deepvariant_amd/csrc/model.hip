@@ -15,7 +15,7 @@
 // weights and an fp32 per-channel shift at load time.
 //
 // The plan (tensors, ops, planning passes) is model_graph.h / model_graph.cpp; the kernels are conv_mfma.hip (MFMA
-// convolutions), model_kernels.hip (front end, pools, head), stem.hip, imgconv.hip, chain.hip and block35.hip.  This
+// convolutions), model_kernels.hip (front end, pools, head), stem.hip, imgconv.hip, chain.hip, block35.hip and mixed3.hip.  This
 // file packs the weights, enqueues the plan's launches (run_ops) and holds the C entry points.
 #include <algorithm>
 #include <map>
@@ -31,6 +31,7 @@
 #include "model_graph.h"
 #include "model_kernels.h"
 #include "block35.h"
+#include "mixed3.h"
 #include "chain.h"
 #include "stem_fused.h"
 #include "calib.h"
@@ -315,6 +316,72 @@ int enqueue_block35(const Pass& ps, int oi) {
   dv::ProfileScope prof(dv::kProfConv, ps.stream);
   dv::launch_block35(a, m->n_cus, ps.stream);
   return 8;
+}
+
+// DV_MIXED3_PROF (tuning aid, eager only): the launch with its per-wave phase counters read back and printed.
+void report_mixed3_profile(dv::Mixed3Args a, int n_cus, hipStream_t stream) {
+  const int grid = std::min(a.N, n_cus);
+  const size_t words = static_cast<size_t>(grid) * 4 * 12;
+  unsigned long long* d = nullptr;
+  if (hipMalloc(&d, words * 8) != hipSuccess) return;
+  (void)hipMemsetAsync(d, 0, words * 8, stream);
+  a.prof = d;
+  dv::launch_mixed3(a, n_cus, stream);
+  std::vector<unsigned long long> h(words);
+  (void)hipStreamSynchronize(stream);
+  (void)hipMemcpy(h.data(), d, words * 8, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  for (int w = 0; w < 4; ++w) {
+    double sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < grid; ++b)
+      for (int i = 0; i < 9; ++i) sum[i] += static_cast<double>(h[(static_cast<size_t>(b) * 4 + w) * 12 + i]);
+    const double tiles = static_cast<double>(a.N);
+    fprintf(stderr, "[dv-mixed3 wave %d] cycles/tile (chunk-barrier wait, mfma steps, closing barrier + epilogue): 1x1 %.0f %.0f "
+                    "%.0f | 3x3 %.0f %.0f %.0f | 3x3/2 %.0f %.0f %.0f\n", w, sum[0] / tiles, sum[1] / tiles, sum[2] / tiles,
+            sum[3] / tiles, sum[4] / tiles, sum[5] / tiles, sum[6] / tiles, sum[7] / tiles, sum[8] / tiles);
+  }
+}
+
+int enqueue_mixed3(const Pass& ps, int oi) {
+  const dv_model* m = ps.m;
+  const int n = ps.n;
+  const Op &op = m->ops[oi], &c3a = m->ops[oi + 1], &c3b = m->ops[oi + 2];
+  const BufferDesc& ib = m->buffers[op.in_buf];
+  dv::Mixed3Args a{};
+  a.in = m->buf_ptr(op.in_buf);
+  a.ig = ib.geom();
+  a.in_img_bytes = static_cast<unsigned>(ib.bytes_per_example());
+  a.N = n;
+  a.h = op.oh;
+  a.w = op.ow;
+  a.n_chunks = op.cin / kChunk;
+  a.w1 = m->w_ptr(op);
+  a.sh1 = m->shift_ptr(op);
+  a.w3a = m->w_ptr(c3a);
+  a.sh3a = m->shift_ptr(c3a);
+  a.w3b = m->w_ptr(c3b);
+  a.sh3b = m->shift_ptr(c3b);
+  a.out = m->buf_ptr(c3b.out_buf);
+  a.og = m->buffers[c3b.out_buf].geom();
+  a.oh = c3b.oh;
+  a.ow = c3b.ow;
+  a.goff = c3b.out_coff / 8;
+  const double px = static_cast<double>(n) * op.oh * op.ow, opx = static_cast<double>(n) * c3b.oh * c3b.ow;
+  const std::string tr_label = "mixed3 dbl " + std::to_string(op.cin) + "->" + std::to_string(op.cout) + " 1x1|" +
+                               std::to_string(c3a.cin) + "->" + std::to_string(c3a.cout) + " 3x3|" +
+                               std::to_string(c3b.cin) + "->" + std::to_string(c3b.cout) + " 3x3/2 @" +
+                               std::to_string(op.oh) + "x" + std::to_string(op.ow);
+  TraceScope tr(ps.stream, tr_label,
+                2.0 * (px * (static_cast<double>(op.cin) * op.cout + 9.0 * c3a.cin * c3a.cout) + opx * 9.0 * c3b.cin * c3b.cout),
+                2.0 * (px * op.cin + opx * c3b.cout));
+  dv::ProfileScope prof(dv::kProfConv, ps.stream);
+  static const bool mixed3_prof = getenv("DV_MIXED3_PROF") != nullptr;
+  if (mixed3_prof && g_trace != nullptr) {
+    report_mixed3_profile(a, m->n_cus, ps.stream);
+  } else {
+    dv::launch_mixed3(a, m->n_cus, ps.stream);
+  }
+  return 3;
 }
 
 // DV_CHAIN_PROF (tuning aid, eager only): the chain with its per-wave phase counters read back and printed.
@@ -616,6 +683,8 @@ int run_ops(dv_model* m, int first, int last, int n, hipStream_t stream,
       ran = enqueue_stem_b(ps, oi);
     } else if (op.b35 == 1) {
       ran = enqueue_block35(ps, oi);
+    } else if (op.m3 == 1) {
+      ran = enqueue_mixed3(ps, oi);
     } else if (op.chain_len > 0) {
       ran = enqueue_chain(ps, oi);
     } else if (op.first_u8) {
@@ -886,8 +955,19 @@ int dv_model_load_weights(dv_model* m, const float* weights, int64_t n) {
           }
       return;
     }
-    if (op.chain_len > 0 || op.in_chain || op.b35 >= 5) {
-      // chain.hip, block35.hip: [channel chunk][tap][k-group][cout_pad][8]
+    if (op.m3 == 1) {
+      // mixed3.hip's 1x1: [channel chunk][k-group][64 couts][8]
+      _Float16* dst = packed.data() + op.w_off;
+      for (int cc = 0; cc < l.cin / kChunk; ++cc)
+        for (int co = 0; co < op.cout; ++co)
+          for (int jj = 0; jj < kChunk; ++jj) {
+            const float v = w[static_cast<size_t>(cc * kChunk + jj) * l.cout + co];
+            dst[((static_cast<size_t>(cc) * 2 + jj / 8) * dv::kMixed3Red + co) * 8 + (jj % 8)] = static_cast<_Float16>(v * inv[co]);
+          }
+      return;
+    }
+    if (op.chain_len > 0 || op.in_chain || op.b35 >= 5 || op.m3 >= 2) {
+      // chain.hip, block35.hip, mixed3.hip: [channel chunk][tap][k-group][cout_pad][8]
       const int cout_pad = (op.cout + 31) / 32 * 32, taps = op.kh * op.kw;
       _Float16* dst = packed.data() + op.w_off;
       for (int cc = 0; cc < l.cin / kChunk; ++cc)
@@ -1126,7 +1206,7 @@ int dv_model_op_label(const dv_model* m, int op_index, char* buf, int capacity) 
   snprintf(buf, static_cast<size_t>(capacity), "%s layer=%d k=%dx%d s=%d cin=%d cout=%d out=%dx%d raw=%d in_buf=%d out_buf=%d coff=%d lds_only=%d",
            kind, op.layer, op.kh, op.kw, op.stride, op.cin, op.cout, op.oh, op.ow, op.raw ? 1 : 0, op.in_buf, op.out_buf,
            op.out_coff, (op.type == kOpConv && (op.stem_a || op.stem_b)) || (op_index + 1 < static_cast<int>(m->ops.size()) && m->ops[op_index + 1].in_chain && m->ops[op_index + 1].in_buf == op.out_buf) ||
-               (op.b35 >= 2 && op.b35 <= 4) || op.b35 == 6 ? 1 : 0);
+               (op.b35 >= 2 && op.b35 <= 4) || op.b35 == 6 || op.m3 == 1 || op.m3 == 2 ? 1 : 0);
   return DV_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "model_graph.h"
 #include "model_kernels.h"
 #include "block35.h"
+#include "mixed3.h"
 #include "chain.h"
 #include "stem_fused.h"
 
@@ -546,6 +547,47 @@ void dv_model::choose_block35() {
   }
 }
 
+// mixed3's double-3x3 branch as ONE launch (mixed3.hip): a 1x1 Cin->64 that reads a full concat buffer, the 3x3 'same'
+// 64->96 that alone reads it and the 3x3 / 2 'valid' 96->96 that alone reads that, on tiles of one whole input map
+// with both intermediates in LDS only.  Declines, keeping the three launches (conv_mfma, imgconv, conv_mfma), for
+// wide / split / float32 / pool_in / pool_out / band / grouped ops, maps of more than 256 pixels or smaller than 3x3,
+// and anything else it does not recognise.  DV_NO_MIXED3_FUSE keeps the three launches; DV_NO_CHAIN implies it.
+void dv_model::choose_mixed3() {
+  if (getenv("DV_NO_MIXED3_FUSE") != nullptr || getenv("DV_NO_CHAIN") != nullptr) return;
+  std::vector<int> readers(buffers.size(), 0);
+  for (const Op& o : ops) readers[o.in_buf]++;
+  for (size_t i = 0; i + 2 < ops.size(); ++i) {
+    const Op &a = ops[i], &b = ops[i + 1], &c = ops[i + 2];
+    auto plain = [&](const Op& o) {
+      return o.type == kOpConv && !o.split && !o.in_wide && !buffers[o.out_buf].wide && !buffers[o.out_buf].f32 &&
+             !o.pool_in && !o.pool_out && !o.first_u8 && !o.stem_a && !o.stem_b && !o.band && !o.raw &&
+             o.group_followers == 0 && o.chain_len == 0 && !o.in_chain && o.b35 == 0 && o.m3 == 0 &&
+             o.side_pool_partner < 0 && o.avg_partner < 0 && o.cin % kChunk == 0 && o.cin == o.cin_real;
+    };
+    bool follower = false;   // a sibling inside another op's grouped launch
+    for (size_t j = 0; j < i; ++j) follower = follower || (ops[j].type == kOpConv && j + ops[j].group_followers >= i);
+    const bool ok =
+        !follower && plain(a) && plain(b) && plain(c) &&
+        a.kh == 1 && a.kw == 1 && a.stride == 1 && a.cout == dv::kMixed3Red && a.cin == buffers[a.in_buf].c &&
+        a.cin / kChunk >= dv::mixed3_min_chunks() && a.out_coff == 0 && buffers[a.out_buf].c == a.cout &&
+        readers[a.out_buf] == 1 &&
+        b.in_buf == a.out_buf && b.kh == 3 && b.kw == 3 && b.stride == 1 && b.pad_h == 1 && b.pad_w == 1 &&
+        b.cin == dv::kMixed3Red && b.cout == dv::kMixed3Mid && b.out_coff == 0 && buffers[b.out_buf].c == b.cout &&
+        readers[b.out_buf] == 1 &&
+        c.in_buf == b.out_buf && c.kh == 3 && c.kw == 3 && c.stride == 2 && c.pad_h == 0 && c.pad_w == 0 &&
+        c.cin == dv::kMixed3Mid && c.cout == dv::kMixed3Out && c.out_coff % 8 == 0 &&
+        a.ih >= 3 && a.iw >= 3 && a.ih * a.iw <= dv::kMixed3TilePx && c.oh * c.ow <= dv::kMixed3MaxOutPx;
+    if (!ok) continue;
+    for (int k = 0; k < 3; ++k) {
+      Op& o = ops[i + k];
+      o.m3 = k + 1;
+      o.v2 = false;
+    }
+    for (int buf : {a.out_buf, b.out_buf}) buffers[buf] = {1, 1, buffers[buf].c, 0};   // LDS only
+    i += 2;
+  }
+}
+
 // tf_keras applications/inception_v3.py, construction order = layer order.
 void dv_model::build() {
   const int in_buf = new_buffer(desc.height, desc.width, 16);
@@ -737,6 +779,7 @@ void dv_model::build() {
   choose_side_pool();
   choose_avg_epilogue();
   choose_block35();
+  choose_mixed3();
   for (size_t i = 0; i < ops.size(); ++i) {  // packed-weight image per LAUNCH (after grouping)
     Op& op = ops[i];
     if (op.type != kOpConv) continue;
@@ -746,7 +789,8 @@ void dv_model::build() {
     for (int gi = 0; gi <= op.group_followers; ++gi) ops[i + gi].w_off = packed_halfs;
     packed_halfs += op.first_u8 ? static_cast<size_t>(kFirstMaxChunks) * 32 * kChunk
                     : op.b35 == 1 ? static_cast<size_t>(2) * (op.cin / kChunk) * 2 * 128 * 8   // block35.hip's heads
-                    : (op.chain_len > 0 || op.in_chain || op.b35 >= 5)
+                    : op.m3 == 1 ? static_cast<size_t>(op.cin / kChunk) * 2 * dv::kMixed3Red * 8       // mixed3.hip's 1x1
+                    : (op.chain_len > 0 || op.in_chain || op.b35 >= 5 || op.m3 >= 2)
                         ? static_cast<size_t>(op.n_chunks) * 2 * ((op.cout + 31) / 32 * 32) * 8
                     : op.v2     ? static_cast<size_t>(op.v2_tiles) * op.v2_steps *
                                       dv::imgconv_wslab_halfs(op.kh, op.kw, op.nb)

@@ -89,6 +89,9 @@ struct Op {
   // role in the block: 1 = b1 (the leader), 2 = 5x5 reducer, 3 = 3x3dbl reducer, 4 = pooled projection (raw 1x1),
   // 5 = 5x5, 6 = 3x3 64->96, 7 = 3x3 96->96, 8 = the average pool; ops 2-8 follow the leader in this order
   int b35 = 0;
+  // mixed3.hip: mixed3's double-3x3 branch as ONE launch (choose_mixed3), placed at its 1x1; role in the branch:
+  // 1 = 1x1 Cin->64 (the leader), 2 = 3x3 64->96, 3 = 3x3 / 2 96->96; ops 2-3 follow the leader in this order
+  int m3 = 0;
 };
 
 struct LayerInfo {
@@ -177,6 +180,7 @@ struct dv_model {
   void choose_avg_epilogue();
   void choose_chains();
   void choose_block35();
+  void choose_mixed3();
   void build();
   // the flat corrections vector of dv_model_calibrate (layer order, cout values each, no padding): the offset into
   // the shift array of every value's channel

@@ -984,6 +984,9 @@ int dv_model_set_blank_skip(dv_model* m, int enabled);
  * switches it on for inputs of more than 8 channels (PACBIO, ONT_R104) and off otherwise; the environment variable
  * DV_PRECISE=0 / 1 read at dv_model_create overrides.  Same ABI, same weights, same outputs to within the tolerance. */
 int dv_model_is_precise(const dv_model* m);
+/* Planner knobs, environment variables read at dv_model_create (A/B runs and tests; the outputs are bit-identical either
+ * way): DV_NO_CHAIN=1 keeps every layer of the fused chain family on its own launch, DV_NO_BLOCK35=1 only the 35x35
+ * blocks' (block35.hip), DV_NO_MIXED3_FUSE=1 only mixed3's 1x1 -> 3x3 -> 3x3/2 branch (mixed3.hip). */
 int dv_model_blank_thresholds(dv_model* m, int n, int32_t* out);
 
 /* dv_model_infer for a caller that KNOWS how many rows of each image are drawn (ABI v8): `rows_used` is a device
