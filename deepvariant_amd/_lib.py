@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     'dv_aligner_score_threshold', 'dv_aligner_kmer_occurrences', 'dv_positions_map',
     'dv_merge_cigar_op', 'dv_local_align', 'dv_local_align_many',
     'dv_local_align_pairs_device', 'dv_local_align_device_last_stats', 'dv_realign_regions_device',
+    'dv_local_align_device_last_traceback_stats', 'dv_local_align_band',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
@@ -189,6 +190,17 @@ DV_LOCAL_ALIGN_DEVICE_MAX_REFERENCE = 65534
 
 class DvRealignDeviceStats(C.Structure):
   _fields_ = [('pairs', C.c_int64), ('pairs_on_host', C.c_int64), ('cells', C.c_int64), ('launches', C.c_int64)]
+
+
+# include/dvhip.h: what the device's banded trace-back holds per pair (one band diagonal per lane; run words);
+# a pair past either is traced back by the host code inside the same call
+DV_LOCAL_ALIGN_DEVICE_MAX_BAND = 31
+DV_LOCAL_ALIGN_DEVICE_MAX_RUNS = 64
+
+
+class DvRealignTracebackStats(C.Structure):
+  _fields_ = [('traced_on_device', C.c_int64), ('traced_on_host', C.c_int64), ('band_cells', C.c_int64),
+              ('widest_band', C.c_int64)]
 
 
 class DvDebruijnOptions(C.Structure):
@@ -397,6 +409,8 @@ def lib():
     l.dv_local_align_pairs_device.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p] +
                                               [C.c_int32] * 4 + [C.c_void_p, C.c_void_p])
     l.dv_local_align_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_local_align_device_last_traceback_stats.argtypes = [C.c_void_p]
+    l.dv_local_align_band.argtypes = [C.c_char_p, C.c_char_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
     l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

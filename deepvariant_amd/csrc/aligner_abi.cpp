@@ -249,6 +249,19 @@ int dv_local_align(const char* reference, const char* query, int32_t match, int3
   return copy_text(r.cigar, out->cigar, sizeof(out->cigar));
 }
 
+// the band and the run count behind dv_local_align's CIGAR: what decides the device's trace-back route
+int dv_local_align_band(const char* reference, const char* query, int32_t match, int32_t mismatch, int32_t gap_open,
+                        int32_t gap_extend, int32_t* band, int32_t* runs) {
+  if (!reference || !query || !band || !runs) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_local_align_band");
+  dv::LocalAligner a(match, mismatch, gap_open, gap_extend);
+  a.set_reference(reference);
+  dv::LocalAlignment r;
+  const bool ok = a.align(query, &r);
+  *band = ok ? r.band : 0;
+  *runs = ok ? r.runs : 0;
+  return DV_OK;
+}
+
 // n queries against one reference through the 16-lane batch path; out[k].score < 0 marks a
 // query the aligner refuses (empty, or an oversized sub-problem)
 int dv_local_align_many(const char* reference, int32_t n, const char* const* queries, int32_t match,

@@ -210,7 +210,7 @@ void LocalAligner::sweep(const int8_t* ref, int ref_first, int ref_last, int dir
 //   1 diagonal | 2 insertion, extended | 3 insertion, opened | 4 deletion, extended |
 //   5 deletion, opened
 bool LocalAligner::banded_cigar(const int8_t* ref, int ref_len, const int8_t* q, int q_len, int target,
-                                std::vector<std::pair<char, int>>* ops) const {
+                                CigarRuns* ops, int* final_band) const {
   int band = std::abs(ref_len - q_len) + 1;
   const size_t cells = static_cast<size_t>(q_len) * ref_len;
   if (cells > (size_t{1} << 27)) return false;   // 128 M cells (~1.5 GB of tables): not a window-sized problem
@@ -295,6 +295,7 @@ bool LocalAligner::banded_cigar(const int8_t* ref, int ref_len, const int8_t* q,
   for (size_t k = rev.size(); k-- > 0;) {
     if (rev[k].second > 0) ops->push_back(rev[k]);
   }
+  *final_band = band;
   return true;
 }
 
@@ -416,17 +417,34 @@ bool LocalAligner::complete(const CodedSequence& ref, const CodedSequence& q, co
   return describe(ref, q, c.score, c.ref_begin, c.ref_end, c.query_begin, c.query_end, out);
 }
 
+void LocalAligner::complete_with_runs(const CodedSequence& ref, const CodedSequence& q, const SweepCorners& c,
+                                      const CigarRuns& runs, int band, LocalAlignment* out) const {
+  describe_runs(ref, q, c.score, c.ref_begin, c.ref_end, c.query_begin, c.query_end, runs, band, out);
+}
+
 // CIGAR and text form of the alignment whose corner points are known
 bool LocalAligner::describe(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_begin, int ref_end,
                             int q_begin, int q_end, LocalAlignment* out) const {
   *out = LocalAlignment();
   out->score = score1;
-  const int q_len = static_cast<int>(q.size());
-  std::vector<std::pair<char, int>> ops;
+  CigarRuns ops;
+  int band = 0;
   if (!banded_cigar(ref.data() + ref_begin, ref_end - ref_begin + 1, q.data() + q_begin,
-                    q_end - q_begin + 1, score1, &ops)) {
+                    q_end - q_begin + 1, score1, &ops, &band)) {
     return false;
   }
+  describe_runs(ref, q, score1, ref_begin, ref_end, q_begin, q_end, ops, band, out);
+  return true;
+}
+
+void LocalAligner::describe_runs(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_begin,
+                                 int ref_end, int q_begin, int q_end, const CigarRuns& ops, int band,
+                                 LocalAlignment* out) const {
+  *out = LocalAlignment();
+  out->score = score1;
+  out->band = band;
+  out->runs = static_cast<int>(ops.size());
+  const int q_len = static_cast<int>(q.size());
   out->ref_begin = ref_begin;
   out->ref_end = ref_end;
   out->query_begin = q_begin;
@@ -465,7 +483,6 @@ bool LocalAligner::describe(const CodedSequence& ref, const CodedSequence& q, in
   }
   emit(q_len - q_end - 1, 'S');
   out->cigar = cigar;
-  return true;
 }
 
 }  // namespace dv

@@ -34,7 +34,11 @@ struct LocalAlignment {
   int query_begin = -1, query_end = -1;  // inclusive, 0-based
   int mismatches = 0;
   std::string cigar;                     // e.g. "3S4=1X4=1I5=2S"; empty if nothing aligned
+  int band = 0, runs = 0;                // of the CIGAR: the band banded_cigar ended with, its M/I/D runs (0: no CIGAR)
 };
+
+// the M/I/D runs of an alignment between its corner points, in alignment order
+using CigarRuns = std::vector<std::pair<char, int>>;
 
 // a reference sequence in the aligner's 0..4 codes (A C G T other)
 using CodedSequence = std::vector<int8_t>;
@@ -75,6 +79,12 @@ class LocalAligner {
   // reverse pass did not reach the forward score.
   bool complete(const CodedSequence& ref, const CodedSequence& q, const SweepCorners& corners,
                 LocalAlignment* out) const;
+  // complete() for a pair whose banded trace-back ran elsewhere too: `runs` is what banded_cigar gives
+  // between the corner points, `band` the band it ended with.  Only the text half is left: soft clips,
+  // the '=' / 'X' split of the M runs and `mismatches`.  The corners must hold an alignment
+  // (score > 0, reverse_score == score).
+  void complete_with_runs(const CodedSequence& ref, const CodedSequence& q, const SweepCorners& corners,
+                          const CigarRuns& runs, int band, LocalAlignment* out) const;
   int match() const { return match_; }
   int mismatch() const { return mismatch_; }
   int gap_open() const { return gap_open_; }
@@ -85,13 +95,16 @@ class LocalAligner {
   // best local score over ref[r0..r1] (walked in direction dir) x q; see .cpp
   void sweep(const int8_t* ref, int ref_first, int ref_last, int dir, const std::vector<int8_t>& q,
              int stop_at, int* best, int* best_ref, int* best_q) const;
-  bool banded_cigar(const int8_t* ref, int ref_len, const int8_t* q, int q_len, int target,
-                    std::vector<std::pair<char, int>>* ops) const;
+  bool banded_cigar(const int8_t* ref, int ref_len, const int8_t* q, int q_len, int target, CigarRuns* ops,
+                    int* final_band) const;
   // reverse pass + CIGAR for a forward result (score1 at ref_end / q_end)
   bool finish(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_end, int q_end,
               LocalAlignment* out) const;
   bool describe(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_begin, int ref_end,
                 int q_begin, int q_end, LocalAlignment* out) const;
+  // the text half of describe(): `ops` between the corner points -> LocalAlignment
+  void describe_runs(const CodedSequence& ref, const CodedSequence& q, int score1, int ref_begin, int ref_end,
+                     int q_begin, int q_end, const CigarRuns& ops, int band, LocalAlignment* out) const;
 
   int match_, mismatch_, gap_open_, gap_extend_;
   int8_t mat_[25];

@@ -1,7 +1,8 @@
 // The two sweeps of the local aligner (local_align.h: LocalAligner::sweep forward, then the
 // reverse sweep of LocalAligner::finish) for a list of (reference, query) pairs in one kernel
-// launch.  CIGARs stay on the host: the corner points returned here go to
-// LocalAligner::complete.  Kernel and runtime: local_align.hip.
+// launch, and in the same launch the banded trace-back between the corner points it found.  The
+// corner points, and the M/I/D runs of the pairs the kernel traced back, return to the host, where
+// complete_on_device_route() writes the text form.  Kernel and runtime: local_align.hip.
 #ifndef DV_LOCAL_ALIGN_DEVICE_H_
 #define DV_LOCAL_ALIGN_DEVICE_H_
 
@@ -32,6 +33,26 @@ struct DeviceAlignStats {
   int64_t pairs = 0, pairs_on_host = 0, cells = 0, launches = 0;
 };
 
+// The trace-back of a call.  Pair k's runs, where traced[k], are words[first[k] .. first[k] + count[k]) in
+// alignment order: (length << 2) | 0 M / 1 I / 2 D; band[k] is the band banded_cigar would have ended with.
+// A pair with traced[k] == 0 holds no runs at all (band past DV_LOCAL_ALIGN_DEVICE_MAX_BAND, more than
+// DV_LOCAL_ALIGN_DEVICE_MAX_RUNS runs, scratch budget used up, or nothing to trace).
+struct DeviceRuns {
+  std::vector<uint8_t> traced;
+  std::vector<int32_t> band, first, count;
+  std::vector<uint32_t> words;
+};
+
+struct TracebackStats {   // dv_realign_traceback_stats
+  int64_t traced_on_device = 0, traced_on_host = 0, band_cells = 0, widest_band = 0;
+};
+// of the calling thread's last sweep_pairs_on_device; the C entry points reset it before they check anything
+TracebackStats& last_traceback_stats();
+
+// DV_REALIGN_DEVICE_TRACEBACK, read now; unset: kTracebackByDefault
+constexpr bool kTracebackByDefault = false;
+bool device_traceback_enabled();
+
 inline bool device_align_fits(size_t ref_len, size_t query_len) {
   return query_len <= static_cast<size_t>(kDeviceAlignMaxQuery) &&
          ref_len <= static_cast<size_t>(kDeviceAlignMaxReference);
@@ -41,11 +62,18 @@ inline bool device_align_fits(size_t ref_len, size_t query_len) {
 // limits: one upload, one launch, one download on `stream` (null: a non-blocking stream the
 // library owns), then waits for it.  Indices must be valid.  route[k] says what became of pair k;
 // stats (may be null) is added to.  Buffers are the calling thread's and are reused.
+// `traced` (may be null: no trace-back) receives the runs of the pairs the kernel traced back, when
+// device_traceback_enabled(); last_traceback_stats() says how the pairs holding an alignment were split.
 // Returns a dv_status; DV_ERR_NO_DEVICE without a GPU (only when there is device work).
 int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, const std::vector<int32_t>& pair_ref,
                           const std::vector<int32_t>& pair_query, int match, int mismatch, int gap_open,
                           int gap_extend, void* stream, std::vector<SweepCorners>* corners,
-                          std::vector<uint8_t>* route, DeviceAlignStats* stats);
+                          std::vector<uint8_t>* route, DeviceAlignStats* stats, DeviceRuns* traced);
+
+// LocalAligner::complete for pair k of a device call: the text form around the device's runs where the
+// kernel traced the pair back, complete() itself otherwise.  Returns what complete() returns.
+bool complete_on_device_route(const LocalAligner& aligner, const CodedSequence& ref, const CodedSequence& q,
+                              const SweepCorners& corners, const DeviceRuns* traced, size_t k, LocalAlignment* out);
 
 }  // namespace dv
 

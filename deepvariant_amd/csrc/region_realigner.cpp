@@ -207,6 +207,7 @@ int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_region
                               dv_realign_device_stats* stats) {
   try {
     if (stats) *stats = dv_realign_device_stats{0, 0, 0, 0};
+    dv::last_traceback_stats() = dv::TracebackStats();
     const DeviceRoute device{stream, stats};
     return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
   } catch (const std::bad_alloc&) {
@@ -451,9 +452,10 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
       std::vector<dv::SweepCorners> corners;
       std::vector<uint8_t> route;
       dv::DeviceAlignStats stats;
+      dv::DeviceRuns traced;
       if (int rc = dv::sweep_pairs_on_device(sequences, pair_ref, pair_query, scoring->match(), scoring->mismatch(),
                                              scoring->gap_open(), scoring->gap_extend(), device->stream, &corners,
-                                             &route, &stats)) {
+                                             &route, &stats, &traced)) {
         return rc;
       }
       if (device->stats) {
@@ -462,7 +464,8 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
         device->stats->cells = stats.cells;
         device->stats->launches = stats.launches;
       }
-      // the CIGARs (and the whole alignment of a pair outside the kernel's limits) on the worker pool
+      // the CIGARs' text form, the banded trace-back of the pairs the kernel did not trace, and the whole
+      // alignment of a pair outside the kernel's limits, on the worker pool
       constexpr size_t kPairsPerTask = 16;
       std::vector<int> chunks((pair_ref.size() + kPairsPerTask - 1) / kPairsPerTask);
       for (size_t c = 0; c < chunks.size(); ++c) chunks[c] = static_cast<int>(c);
@@ -472,7 +475,7 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
           const dv::CodedSequence& ref = *sequences[pair_ref[k]];
           const dv::CodedSequence& q = *sequences[pair_query[k]];
           if (route[k] == dv::kRouteDevice) {
-            ok[k] = scoring->complete(ref, q, corners[k], &results[k]);
+            ok[k] = dv::complete_on_device_route(*scoring, ref, q, corners[k], &traced, k, &results[k]);
           } else if (route[k] == dv::kRouteHost) {
             std::vector<dv::LocalAlignment> one;
             std::vector<char> one_ok;

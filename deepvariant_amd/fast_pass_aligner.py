@@ -216,14 +216,27 @@ def local_align_many(reference: str, queries: Sequence[str], match=2, mismatch=2
   return [None if out[k].score < 0 else out[k] for k in range(n)]
 
 
+def local_align_band(reference: str, query: str, match=2, mismatch=2, gap_open=3, gap_extend=1) -> Tuple[int, int]:
+  """-> (band, runs) of `local_align(reference, query)`'s CIGAR: the band the banded re-alignment ended with and
+  the number of M/I/D runs, (0, 0) where there is no CIGAR.  Host only.  The device traces a swept pair back
+  itself exactly when band <= _lib.DV_LOCAL_ALIGN_DEVICE_MAX_BAND and runs <= _lib.DV_LOCAL_ALIGN_DEVICE_MAX_RUNS."""
+  band, runs = C.c_int32(), C.c_int32()
+  _lib.check(_lib.lib().dv_local_align_band(reference.encode(), query.encode(), match, mismatch, gap_open,
+                                            gap_extend, C.byref(band), C.byref(runs)))
+  return band.value, runs.value
+
+
 def local_align_pairs_device(sequences: Sequence[str], pairs: Sequence[Tuple[int, int]], scoring=(2, 2, 3, 1),
-                             stream: int = 0, with_stats: bool = False):
+                             stream: int = 0, with_stats: bool = False, with_traceback_stats: bool = False):
   """`local_align(sequences[r], sequences[q])` for every (r, q) of `pairs`, with the two Smith-Waterman
-  sweeps of all pairs in ONE kernel launch (csrc/local_align.hip) and the CIGARs built on the host.
+  sweeps of all pairs in ONE kernel launch (csrc/local_align.hip).  With DV_REALIGN_DEVICE_TRACEBACK=1 the
+  same launch traces the alignments back and the host writes the CIGAR text from the device's M/I/D runs;
+  otherwise the host's banded re-alignment builds the CIGARs from the corner points.
   `scoring` = (match, mismatch, gap_open, gap_extend).  An entry is None where local_align would
   raise; pairs beyond the kernel's limits (_lib.DV_LOCAL_ALIGN_DEVICE_MAX_*) are aligned by the host
   code inside the call.  There is no CPU fallback: without a GPU this raises DV_ERR_NO_DEVICE.
-  with_stats: -> (alignments, _lib.DvRealignDeviceStats of this call)."""
+  with_stats: -> (alignments, _lib.DvRealignDeviceStats of this call);
+  with_traceback_stats: _lib.DvRealignTracebackStats of this call is appended to that."""
   import numpy as np
   raw = [s.encode() if isinstance(s, str) else bytes(s) for s in sequences]
   off = np.zeros(len(raw) + 1, np.int64)
@@ -238,11 +251,18 @@ def local_align_pairs_device(sequences: Sequence[str], pairs: Sequence[Tuple[int
                                                     query.ctypes.data, match, mismatch, gap_open, gap_extend, out,
                                                     stream or None))
   res = [None if out[k].score < 0 else out[k] for k in range(n)]
-  if not with_stats:
+  if not with_stats and not with_traceback_stats:
     return res
-  stats = _lib.DvRealignDeviceStats()
-  _lib.check(_lib.lib().dv_local_align_device_last_stats(C.byref(stats)))
-  return res, stats
+  ret = (res,)
+  if with_stats:
+    stats = _lib.DvRealignDeviceStats()
+    _lib.check(_lib.lib().dv_local_align_device_last_stats(C.byref(stats)))
+    ret += (stats,)
+  if with_traceback_stats:
+    traceback = _lib.DvRealignTracebackStats()
+    _lib.check(_lib.lib().dv_local_align_device_last_traceback_stats(C.byref(traceback)))
+    ret += (traceback,)
+  return ret
 
 
 def realign_reads_to_haplotype(haplotype: str, reads: Sequence, contig: str, ref_start: int, ref_end: int,

@@ -43,7 +43,8 @@ _THREADS = max(1, int(os.environ.get('DV_REALIGN_THREADS', '4')))
 # which runs them on its own host threads: DV_REALIGN_THREADS, or one per hardware thread up to 16.
 _NATIVE_THREADS = max(0, int(os.environ.get('DV_REALIGN_THREADS', '0')))
 # DV_REALIGN_DEVICE=1: the table path runs its local alignments on the GPU (dv_realign_regions_device).  Off by
-# default; the results are the host route's either way.
+# default; the results are the host route's either way.  On that route DV_REALIGN_DEVICE_TRACEBACK=1 (read by the
+# library at each call) moves the CIGARs' banded trace-back into the same kernel launch; off by default too.
 _DEVICE_ALIGN = os.environ.get('DV_REALIGN_DEVICE', '0') == '1'
 _pool: Optional[concurrent.futures.ThreadPoolExecutor] = None
 
@@ -310,6 +311,7 @@ class RealignJob:
     self.results: List = [None] * n_slots
     self._device_align = device_align
     self.device_stats = None       # _lib.DvRealignDeviceStats of the call, device route only
+    self.traceback_stats = None    # _lib.DvRealignTracebackStats of the call, device route only
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -352,6 +354,10 @@ class RealignJob:
       _lib.check(_lib.lib().dv_realign_regions_device(descs, len(self._jobs), C.byref(self._options), None,
                                                       C.byref(handle), C.byref(out), C.byref(stats)))
       self.device_stats = stats
+      # kept per calling thread by the library: read here, on the thread that made the call
+      traceback = _lib.DvRealignTracebackStats()
+      _lib.check(_lib.lib().dv_local_align_device_last_traceback_stats(C.byref(traceback)))
+      self.traceback_stats = traceback
     else:
       _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
                                                C.byref(out)))

@@ -531,7 +531,8 @@ int dv_local_align_many(const char* reference, int32_t n, const char* const* que
 
 /* The same alignments with the two Smith-Waterman sweeps on the device (csrc/local_align.hip): one upload,
  * one kernel launch and one download for the whole list, on `stream` (a hipStream_t; NULL = a
- * non-blocking stream the library owns); CIGARs are built on the host from the corner points.
+ * non-blocking stream the library owns); CIGARs are built on the host from the corner points, or from
+ * the device's M/I/D runs (below).
  * Sequences are ASCII: sequence s is bases[seq_off[s], seq_off[s + 1]); pair k aligns query
  * pair_query[k] to reference pair_ref[k], so a sequence that many pairs share is uploaded once.
  * out[k] is what dv_local_align(reference, query, ...) returns; out[k].score = -1 where it would fail
@@ -554,6 +555,32 @@ int dv_local_align_pairs_device(int32_t n_seqs, const char* bases, const int64_t
                                 dv_local_alignment* out, void* stream);
 /* What the calling thread's last dv_local_align_pairs_device did (for tests and tools). */
 int dv_local_align_device_last_stats(dv_realign_device_stats* out);
+
+/* The banded trace-back on the device.  For a pair the kernel has swept and that holds an alignment
+ * (score > 0 and the reverse pass reached it) the same launch also runs LocalAligner::banded_cigar
+ * between the corner points -- the band |ref_len - q_len| + 1, doubling until the score is reached, and
+ * the walk back from the bottom-right cell -- and returns the M/I/D runs; the host is left with the text
+ * form (soft clips, '=' / 'X', mismatches).  One diagonal of the band per lane, so a pair goes back to
+ * the host's banded_cigar, inside the same call and with the same result, when its band would pass
+ * DV_LOCAL_ALIGN_DEVICE_MAX_BAND, when its runs do not fit DV_LOCAL_ALIGN_DEVICE_MAX_RUNS, when the
+ * call's direction-byte scratch (256 MiB, about 64 bytes per query base) is used up, or when banded_cigar
+ * itself would fail.  DV_REALIGN_DEVICE_TRACEBACK=0 / 1 in the environment, read at each call, turns it
+ * off / on for both device entry points; unset it is off (DESIGN.md section 12 has the measurement). */
+#define DV_LOCAL_ALIGN_DEVICE_MAX_BAND 31   /* 2 * band + 1 diagonals in the 64 lanes of a wave */
+#define DV_LOCAL_ALIGN_DEVICE_MAX_RUNS 64   /* M/I/D runs of one alignment */
+typedef struct dv_realign_traceback_stats {
+  int64_t traced_on_device;  /* swept pairs holding an alignment whose runs came from the device */
+  int64_t traced_on_host;    /* ... and those that LocalAligner's host code traced back */
+  int64_t band_cells;        /* sum over the former of q_len * (2 * band + 1), final band: cells of its last DP */
+  int64_t widest_band;       /* the largest final band among the former */
+} dv_realign_traceback_stats;
+/* What the calling thread's last dv_local_align_pairs_device or dv_realign_regions_device did. */
+int dv_local_align_device_last_traceback_stats(dv_realign_traceback_stats* out);
+/* Host only, no device: the band banded_cigar ends with and the number of M/I/D runs of the CIGAR that
+ * dv_local_align(reference, query, ...) returns, which decide whether the device traces the pair back;
+ * 0 / 0 where there is no CIGAR (nothing aligns, or dv_local_align fails). */
+int dv_local_align_band(const char* reference, const char* query, int32_t match, int32_t mismatch,
+                        int32_t gap_open, int32_t gap_extend, int32_t* band, int32_t* runs);
 
 /* ---- local assembly for the window realigner (host only) -----------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,

@@ -5,6 +5,9 @@ alternating in one process.  The two routes' tables and haplotypes are compared 
 Prints one JSON line: per DV_REALIGN_THREADS setting (16 and 4) and per route the median wall time of
 realign_tables over --repeats batches after a warm-up, the share of it spent in the native call, every run's
 time (the spread), and the device route's stats: pairs, forward-pass cells, share of pairs aligned on the host.
+Where the library has the device trace-back, the device route is measured in two arms that alternate with the
+host route: `device` with DV_REALIGN_DEVICE_TRACEBACK=0 (every CIGAR's banded trace-back on the host) and
+`device_traceback` with =1 (in the kernel); the split of the trace-backs and the widest band are in `stats`.
 Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
 measures an older checkout.  Kernel time is not measured here: run this under
 `rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
@@ -81,20 +84,26 @@ def main(argv=None):
   batch = [b for b in batch if b[1].n_reads][:args.regions]
   regions, tables = [b[0] for b in batch], [b[1] for b in batch]
   has_device = hasattr(_lib, 'DvRealignDeviceStats')
+  has_traceback = hasattr(_lib, 'DvRealignTracebackStats')
+  switch = 'DV_REALIGN_DEVICE_TRACEBACK'
   if has_device:
     routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
               'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
+    if has_traceback:
+      routes['device_traceback'] = routes['device']
   else:
     routes = {'host': R.Realigner(R.realigner_config(), ref)}
 
   def run(route):
+    if has_traceback:
+      os.environ[switch] = '1' if route == 'device_traceback' else '0'      # read by the library at each call
     gc.collect()
     t0 = time.perf_counter()
     job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
     t1 = time.perf_counter()
     out = job.result()                                                                    # the native call + write-back
     t2 = time.perf_counter()
-    return t2 - t0, t2 - t1, out, getattr(job, 'device_stats', None)
+    return t2 - t0, t2 - t1, out, job
 
   # the routes must agree before either is timed (this is the warm-up too)
   _, _, want, _ = run('host')
@@ -102,11 +111,19 @@ def main(argv=None):
   result = {'regions': len(regions), 'reads': int(sum(t.n_reads for t in tables)), 'device_route': has_device,
             'threads': {}}
   if has_device:
-    _, _, got, stats = run('device')
+    _, _, got, job = run('device')
+    stats = job.device_stats
     assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device route differs'
     assert stats.pairs > 0 and stats.launches == 1
     result['stats'] = {'pairs': stats.pairs, 'cells': stats.cells, 'pairs_on_host': stats.pairs_on_host,
                        'share_on_host': round(stats.pairs_on_host / stats.pairs, 6), 'launches': stats.launches}
+  if has_traceback:
+    _, _, got, job = run('device_traceback')
+    assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device trace-back differs'
+    tb = job.traceback_stats
+    assert job.device_stats.launches == 1 and tb.traced_on_device > 0
+    result['stats'].update({'traced_on_device': tb.traced_on_device, 'traced_on_host': tb.traced_on_host,
+                            'band_cells': tb.band_cells, 'widest_band': tb.widest_band})
   for threads in [int(t) for t in args.threads.split(',')]:
     R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
     runs = {route: [] for route in routes}
@@ -124,6 +141,9 @@ def main(argv=None):
                       'native_call_runs_ms': [ms(x[1]) for x in r]}
     if has_device:
       entry['device_over_host_native'] = round(entry['device']['native_call_ms'] / entry['host']['native_call_ms'], 4)
+    if has_traceback:
+      entry['traceback_over_device_native'] = round(entry['device_traceback']['native_call_ms'] /
+                                                    entry['device']['native_call_ms'], 4)
     result['threads'][str(threads)] = entry
   line = json.dumps(result)
   print(line)
