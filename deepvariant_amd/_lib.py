@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     'dv_merge_cigar_op', 'dv_local_align', 'dv_local_align_many',
     'dv_local_align_pairs_device', 'dv_local_align_device_last_stats', 'dv_realign_regions_device',
     'dv_local_align_device_last_traceback_stats', 'dv_local_align_band',
+    'dv_fast_pass_batch', 'dv_fast_pass_batch_device', 'dv_fast_pass_device_last_stats',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
@@ -196,6 +197,23 @@ class DvRealignDeviceStats(C.Structure):
 # a pair past either is traced back by the host code inside the same call
 DV_LOCAL_ALIGN_DEVICE_MAX_BAND = 31
 DV_LOCAL_ALIGN_DEVICE_MAX_RUNS = 64
+
+
+# include/dvhip.h: what one haplotype may measure for the device form of the fast pass (it lives in LDS; a longer one
+# is run by the host code inside the same call), and the largest match / mismatch value the kernel takes
+DV_FAST_PASS_DEVICE_MAX_HAPLOTYPE = 8192
+DV_FAST_PASS_DEVICE_MAX_SCORING = 32767
+
+
+class DvFastPassWindow(C.Structure):
+  _fields_ = [('first_read', C.c_int32), ('n_reads', C.c_int32), ('first_haplotype', C.c_int32),
+              ('n_haplotypes', C.c_int32), ('reference', C.c_int32), ('ref_prefix_len', C.c_int32),
+              ('ref_suffix_len', C.c_int32), ('reserved', C.c_int32)]
+
+
+class DvFastPassStats(C.Structure):
+  _fields_ = [('haplotypes', C.c_int64), ('haplotypes_on_host', C.c_int64), ('pairs', C.c_int64),
+              ('cells', C.c_int64), ('launches', C.c_int64)]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -411,6 +429,9 @@ def lib():
     l.dv_local_align_device_last_stats.argtypes = [C.c_void_p]
     l.dv_local_align_device_last_traceback_stats.argtypes = [C.c_void_p]
     l.dv_local_align_band.argtypes = [C.c_char_p, C.c_char_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]
+    for fn in (l.dv_fast_pass_batch, l.dv_fast_pass_batch_device):
+      fn.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+    l.dv_fast_pass_device_last_stats.argtypes = [C.c_void_p]
     l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

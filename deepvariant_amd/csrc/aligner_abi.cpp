@@ -10,11 +10,13 @@
 #include "direct_phasing.h"
 #include "dv_internal.h"
 #include "fast_pass_aligner.h"
+#include "fast_pass_device.h"
 
 struct dv_aligner {
   dv::FastPassAligner a;
   std::vector<uint32_t> cigar_words;
   bool in_phases = false;   // DV_ALIGNER_ALIGN_IN_PHASES
+  bool split_fast_pass = false;   // DV_ALIGNER_ALIGN_IN_PHASES with arg 2
 };
 
 struct dv_debruijn_graph {
@@ -109,7 +111,16 @@ int dv_aligner_align_reads(dv_aligner* h, int32_t n, const char* const* sequence
   std::vector<dv::RealignedRead> res;
   if (h->in_phases) {
     dv::AlignmentPairs pairs;
-    h->a.prepare_alignments(strings(n, sequences), &pairs);
+    if (h->split_fast_pass) {
+      h->a.begin_alignments(strings(n, sequences));
+      dv::FastPassResults fast;
+      dv::fast_pass_on_host({dv::fast_pass_window_of(h->a)}, dv::fast_pass_scoring_of(h->a), &fast);
+      h->a.install_fast_pass(fast.haplotype_score.data(), fast.haplotype_discarded.data(), fast.read_position.data(),
+                             fast.read_score.data());
+      h->a.collect_alignments(static_cast<size_t>(n), &pairs);
+    } else {
+      h->a.prepare_alignments(strings(n, sequences), &pairs);
+    }
     std::vector<dv::LocalAlignment> results;
     std::vector<char> ok;
     h->a.align_pairs_on_host(pairs, 0, pairs.pair_ref.size(), &results, &ok);
@@ -140,7 +151,10 @@ int dv_aligner_stage(dv_aligner* h, int32_t stage, int32_t arg) {
     case DV_ALIGNER_POSITION_MAPS: h->a.calculate_position_maps(); break;
     case DV_ALIGNER_LOCAL_ALIGN_READS: h->a.local_align_reads_to_haplotypes(arg); break;
     case DV_ALIGNER_SCORE_THRESHOLD: h->a.calculate_score_threshold(); break;
-    case DV_ALIGNER_ALIGN_IN_PHASES: h->in_phases = arg != 0; break;
+    case DV_ALIGNER_ALIGN_IN_PHASES:
+      h->in_phases = arg != 0;
+      h->split_fast_pass = arg == 2;
+      break;
     default: return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_aligner_stage: unknown stage");
   }
   return DV_OK;

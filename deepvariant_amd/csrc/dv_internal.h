@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -32,6 +33,25 @@ struct DeviceBuffer {
   int reserve(size_t bytes);
   int reserve_on_current_device(size_t bytes);
   void release();
+};
+
+// Grow-only pinned host staging, one per host thread and direction.
+struct PinnedStage {
+  uint8_t* ptr = nullptr;
+  size_t cap = 0;
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return DV_OK;
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 16);
+    if (hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault) != hipSuccess) {
+      ptr = nullptr;
+      return fail(DV_ERR_OUT_OF_MEMORY, "hipHostMalloc (staging)");
+    }
+    cap = want;
+    return DV_OK;
+  }
 };
 
 // Optional per-launch timing with HIP events on the launch stream.

@@ -180,7 +180,8 @@ int FastPassAligner::fast_align_strings(std::string_view a, std::string_view b, 
 }
 
 void FastPassAligner::fast_align_reads_to_haplotype(std::string_view haplotype, int* haplotype_score,
-                                                    std::vector<ReadAlignment>* alignments) const {   // :207-286
+                                                    std::vector<ReadAlignment>* alignments, bool* discarded) const {   // :207-286
+  if (discarded) *discarded = false;
   const bool is_ref = haplotype == reference_;
   std::vector<int> coverage(haplotype.size(), 0);
   const int last_pos = static_cast<int>(haplotype.size()) - kmer_size_;
@@ -213,6 +214,7 @@ void FastPassAligner::fast_align_reads_to_haplotype(std::string_view haplotype, 
     if (coverage[i] == 0 && i >= ref_prefix_len_ &&
         static_cast<size_t>(i) < haplotype.size() - static_cast<size_t>(ref_suffix_len_) && !is_ref) {
       *haplotype_score = 0;
+      if (discarded) *discarded = true;
       return;
     }
   }
@@ -542,15 +544,45 @@ std::vector<RealignedRead> FastPassAligner::align_reads(const std::vector<std::s
   return realign_reads_to_reference(sequences.size());
 }
 
-void FastPassAligner::prepare_alignments(const std::vector<std::string>& sequences, AlignmentPairs* pairs) {
+void FastPassAligner::begin_alignments(const std::vector<std::string>& sequences) {
   add_reads(sequences);
   calculate_score_threshold();
-  build_index();
-  fast_align_reads_to_haplotypes();
+}
+
+void FastPassAligner::install_fast_pass(const int32_t* haplotype_score, const int32_t* haplotype_discarded,
+                                        const int32_t* read_position, const int32_t* read_score) {
+  const size_t n_reads = reads_.size();
+  for (size_t h = 0; h < haplotypes_.size(); ++h) {
+    HaplotypeAlignment ha;
+    ha.haplotype_index = h;
+    ha.haplotype_score = haplotype_discarded[h] ? 0 : haplotype_score[h];
+    ha.reads.assign(n_reads, ReadAlignment());
+    if (ha.haplotype_score != 0) {
+      for (size_t r = 0; r < n_reads; ++r) {
+        const size_t row = h * n_reads + r;
+        if (read_position[row] < 0) continue;
+        ReadAlignment& ra = ha.reads[r];
+        ra.position = static_cast<uint16_t>(read_position[row]);
+        ra.score = read_score[row];
+        ra.cigar = std::to_string(reads_[r].size()) + "=";
+      }
+    }
+    alignments_.push_back(std::move(ha));
+  }
+}
+
+void FastPassAligner::collect_alignments(size_t n_input_reads, AlignmentPairs* pairs) {
   init_local_aligner();
   collect_haplotype_pairs(pairs);
   collect_read_pairs(false, pairs);
-  pairs->n_input_reads = sequences.size();
+  pairs->n_input_reads = n_input_reads;
+}
+
+void FastPassAligner::prepare_alignments(const std::vector<std::string>& sequences, AlignmentPairs* pairs) {
+  begin_alignments(sequences);
+  build_index();
+  fast_align_reads_to_haplotypes();
+  collect_alignments(sequences.size(), pairs);
 }
 
 std::vector<RealignedRead> FastPassAligner::finish_alignments(const AlignmentPairs& pairs,

@@ -110,6 +110,18 @@ class FastPassAligner {
   // against and the results of the ones that turn out not to be targets are dropped: the outcome is
   // align_reads()'s, field for field.
   void prepare_alignments(const std::vector<std::string>& sequences, AlignmentPairs* pairs);
+  // prepare_alignments() itself in three steps, for a caller that runs the fast pass elsewhere (the device,
+  // fast_pass.hip) and never needs the k-mer index:
+  //   begin_alignments     the reads (upper-cased) and the score threshold
+  //   install_fast_pass    what fast_align_reads_to_haplotypes() leaves in alignments_, from arrays: per
+  //                        haplotype its score and discarded flag, per (haplotype, read) -- row h * reads + r --
+  //                        the position (-1: not aligned) and score; the cigar is "<L>="; the rows of a
+  //                        discarded haplotype and of one with score 0 are not read: its alignments are reset
+  //   collect_alignments   the local aligner and the pairs it has to align
+  void begin_alignments(const std::vector<std::string>& sequences);
+  void install_fast_pass(const int32_t* haplotype_score, const int32_t* haplotype_discarded,
+                         const int32_t* read_position, const int32_t* read_score);
+  void collect_alignments(size_t n_input_reads, AlignmentPairs* pairs);
   std::vector<RealignedRead> finish_alignments(const AlignmentPairs& pairs, const LocalAlignment* results,
                                                const char* ok);   // [pairs.pair_ref.size()]
   // pairs [first, last) through the host aligner
@@ -118,8 +130,9 @@ class FastPassAligner {
   const LocalAligner& local_aligner() const { return *aligner_; }
 
   void build_index();
+  // *discarded (may be null): the haplotype was given up for a position no read covers
   void fast_align_reads_to_haplotype(std::string_view haplotype, int* haplotype_score,
-                                     std::vector<ReadAlignment>* alignments) const;
+                                     std::vector<ReadAlignment>* alignments, bool* discarded = nullptr) const;
   void init_local_aligner();
   void align_haplotypes_to_reference();
   void calculate_position_maps();
@@ -132,6 +145,14 @@ class FastPassAligner {
 
   const std::vector<HaplotypeAlignment>& haplotype_alignments() const { return alignments_; }
   const std::vector<std::string>& reads() const { return reads_; }
+  const std::vector<std::string>& haplotypes() const { return haplotypes_; }
+  const std::string& reference() const { return reference_; }
+  int kmer_size() const { return kmer_size_; }
+  int max_num_of_mismatches() const { return max_num_of_mismatches_; }
+  int match() const { return match_; }
+  int mismatch() const { return mismatch_; }
+  int ref_prefix_len() const { return ref_prefix_len_; }
+  int ref_suffix_len() const { return ref_suffix_len_; }
   int score_threshold() const { return score_threshold_; }
   size_t index_size() const { return index_.size(); }
   // occurrences of a k-mer: (read, offset) pairs in insertion order

@@ -380,27 +380,8 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void local_align_sweeps(
   }
 }
 
-// Grow-only pinned staging, one per host thread and direction.
-struct PinnedStage {
-  uint8_t* ptr = nullptr;
-  size_t cap = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return DV_OK;
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 16);
-    if (hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault) != hipSuccess) {
-      ptr = nullptr;
-      return dv::fail(DV_ERR_OUT_OF_MEMORY, "hipHostMalloc (local aligner staging)");
-    }
-    cap = want;
-    return DV_OK;
-  }
-};
-
 struct ThreadState {
-  PinnedStage up, down;
+  dv::PinnedStage up, down;
   dv::DeviceBuffer d_up, d_down, d_scratch;   // d_scratch: the trace-back's direction bytes
   hipStream_t stream = nullptr;   // the library's own, for callers that pass none
   int stream_device = -1;

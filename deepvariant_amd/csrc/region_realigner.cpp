@@ -14,7 +14,10 @@
 // dv_realign_regions_device is the same call with the local alignments of phase 2 on the device
 // (local_align.hip): phase 2 becomes
 //   2a, one task per window: the aligner is set up and runs up to its local alignments
-//       (FastPassAligner::prepare_alignments), leaving the pairs it needs;
+//       (FastPassAligner::prepare_alignments), leaving the pairs it needs; with DV_REALIGN_DEVICE_FASTPASS=1
+//       in three steps: i, per window, set-up and reads (begin_alignments); ii, once, the fast pass of every
+//       (window, haplotype) of the batch in one kernel launch (fast_pass.hip); iii, per window, its results
+//       installed (install_fast_pass) and the pairs collected (collect_alignments);
 //   2b, once: the pairs of all windows go through one kernel launch; the CIGARs of the pairs that
 //       aligned (LocalAligner::complete) are spread over the worker pool;
 //   2c, one task per window: FastPassAligner::finish_alignments.
@@ -40,6 +43,7 @@
 #include "debruijn_graph.h"
 #include "dv_internal.h"
 #include "fast_pass_aligner.h"
+#include "fast_pass_device.h"
 #include "local_align_device.h"
 
 struct dv_realign_result {
@@ -208,6 +212,7 @@ int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_region
   try {
     if (stats) *stats = dv_realign_device_stats{0, 0, 0, 0};
     dv::last_traceback_stats() = dv::TracebackStats();
+    dv::last_fast_pass_stats() = dv::FastPassStats();
     const DeviceRoute device{stream, stats};
     return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
   } catch (const std::bad_alloc&) {
@@ -422,14 +427,55 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     });
   } else {
     // ---- 2a: everything up to the local alignments
-    parallel_tasks(align_tasks, n_threads, [&](int t) {
-      auto aligner = std::make_unique<dv::FastPassAligner>();
-      std::vector<std::string> sequences;
-      if (!set_up(t, *aligner, sequences)) return;
-      aligner->prepare_alignments(sequences, &windows[t].pairs);
-      windows[t].aligner = std::move(aligner);
-    });
-    if (!error.empty()) return dv::fail(DV_ERR_BAD_INPUT, error);
+    if (!dv::device_fast_pass_enabled()) {
+      parallel_tasks(align_tasks, n_threads, [&](int t) {
+        auto aligner = std::make_unique<dv::FastPassAligner>();
+        std::vector<std::string> sequences;
+        if (!set_up(t, *aligner, sequences)) return;
+        aligner->prepare_alignments(sequences, &windows[t].pairs);
+        windows[t].aligner = std::move(aligner);
+      });
+      if (!error.empty()) return dv::fail(DV_ERR_BAD_INPUT, error);
+    } else {
+      // 2a-i: set-up and reads
+      parallel_tasks(align_tasks, n_threads, [&](int t) {
+        auto aligner = std::make_unique<dv::FastPassAligner>();
+        std::vector<std::string> sequences;
+        if (!set_up(t, *aligner, sequences)) return;
+        aligner->begin_alignments(sequences);
+        windows[t].aligner = std::move(aligner);
+      });
+      if (!error.empty()) return dv::fail(DV_ERR_BAD_INPUT, error);
+      // 2a-ii: the fast pass of every (window, haplotype) in one device call
+      std::vector<dv::FastPassWindow> fast_windows;
+      std::vector<size_t> first_haplotype(windows.size(), 0);
+      size_t n_haplotypes = 0;
+      const dv::FastPassAligner* any = nullptr;      // the options are the same for every window: they come from `o`
+      for (int t : align_tasks) {
+        if (!windows[t].aligner) continue;
+        any = windows[t].aligner.get();
+        fast_windows.push_back(dv::fast_pass_window_of(*any));
+        first_haplotype[t] = n_haplotypes;
+        n_haplotypes += any->haplotypes().size();
+      }
+      dv::FastPassResults fast;
+      if (any) {
+        if (int rc = dv::fast_pass_on_device(fast_windows, dv::fast_pass_scoring_of(*any), device->stream, &fast,
+                                             &dv::last_fast_pass_stats())) {
+          return rc;
+        }
+      }
+      // 2a-iii: its results installed, then the pairs collected
+      parallel_tasks(align_tasks, n_threads, [&](int t) {
+        Window& win = windows[t];
+        if (!win.aligner) return;
+        const size_t h = first_haplotype[t];
+        const size_t row = static_cast<size_t>(fast.first_row[h]);
+        win.aligner->install_fast_pass(fast.haplotype_score.data() + h, fast.haplotype_discarded.data() + h,
+                                       fast.read_position.data() + row, fast.read_score.data() + row);
+        win.aligner->collect_alignments(win.aligner->reads().size(), &win.pairs);
+      });
+    }
     // ---- 2b: the pairs of all windows in one device call
     std::vector<const dv::CodedSequence*> sequences;
     std::vector<int32_t> pair_ref, pair_query;

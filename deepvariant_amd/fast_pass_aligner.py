@@ -18,6 +18,7 @@ from deepvariant_amd import dv_types as T
 K_REF_ALIGN_MARGIN = 0    # alt_aligned_pileup_lib.cc:62 kRefAlignMargin (the window realigner's is 20)
 
 BUILD_INDEX, INIT_LOCAL_ALIGNER, ALIGN_HAPLOTYPES, POSITION_MAPS, LOCAL_ALIGN_READS, SCORE_THRESHOLD = range(6)
+ALIGN_IN_PHASES = 6     # test hook of dv_aligner_align_reads (include/dvhip.h): arg 1 in phases, 2 with the fast pass split off
 
 
 def _strings(items: Sequence[str]):
@@ -263,6 +264,66 @@ def local_align_pairs_device(sequences: Sequence[str], pairs: Sequence[Tuple[int
     _lib.check(_lib.lib().dv_local_align_device_last_traceback_stats(C.byref(traceback)))
     ret += (traceback,)
   return ret
+
+
+def _fast_pass(entry, windows, options, stream):
+  import numpy as np
+  raw, descs = [], (_lib.DvFastPassWindow * max(len(windows), 1))()
+  as_bytes = lambda s: s.encode('latin-1') if isinstance(s, str) else bytes(s)      # noqa: E731
+  shapes = []
+  for d, w in zip(descs, windows):
+    reads, haplotypes = [as_bytes(r) for r in w['reads']], [as_bytes(h) for h in w['haplotypes']]
+    d.first_read, d.n_reads = len(raw), len(reads)
+    raw += reads
+    d.first_haplotype, d.n_haplotypes = len(raw), len(haplotypes)
+    raw += haplotypes
+    d.reference = -1
+    if w.get('reference') is not None:
+      d.reference = len(raw)
+      raw.append(as_bytes(w['reference']))
+    d.ref_prefix_len, d.ref_suffix_len = w.get('ref_prefix_len', 0), w.get('ref_suffix_len', 0)
+    shapes.append((len(haplotypes), len(reads)))
+  off = np.zeros(len(raw) + 1, np.int64)
+  np.cumsum([len(b) for b in raw], out=off[1:])
+  table = b''.join(raw)
+  n_haps = sum(h for h, _ in shapes)
+  n_rows = sum(h * r for h, r in shapes)
+  hap_score, hap_discarded = np.zeros(max(n_haps, 1), np.int32), np.zeros(max(n_haps, 1), np.int32)
+  position, score = np.zeros(max(n_rows, 1), np.int32), np.zeros(max(n_rows, 1), np.int32)
+  opt = _lib.DvAlignerOptions()
+  for name, value in (options or {}).items():
+    setattr(opt, name, value)
+  _lib.check(entry(len(raw), table, off.ctypes.data, len(windows), descs, C.byref(opt), stream or None,
+                   hap_score.ctypes.data, hap_discarded.ctypes.data, position.ctypes.data, score.ctypes.data))
+  out, h0, r0 = [], 0, 0
+  for n_h, n_r in shapes:
+    rows = slice(r0, r0 + n_h * n_r)
+    out.append(dict(haplotype_score=hap_score[h0:h0 + n_h].copy(), haplotype_discarded=hap_discarded[h0:h0 + n_h].copy(),
+                    read_position=position[rows].reshape(n_h, n_r).copy(), read_score=score[rows].reshape(n_h, n_r).copy()))
+    h0, r0 = h0 + n_h, r0 + n_h * n_r
+  return out
+
+
+def fast_pass_batch(windows: Sequence[dict], options: Optional[dict] = None):
+  """FastPassAligner's fast pass (FastAlignReadsToHaplotype) for every haplotype of every window, host code.
+  A window is dict(reads=[...], haplotypes=[...], reference=str or None, ref_prefix_len=0, ref_suffix_len=0); reads
+  are upper-cased by the call.  `options`: fields of dv_aligner_options (match, mismatch, kmer_size,
+  max_num_of_mismatches; 0 or absent keeps the class default).  -> per window dict(haplotype_score int32[h],
+  haplotype_discarded int32[h], read_position int32[h, r] (-1: not aligned), read_score int32[h, r])."""
+  return _fast_pass(_lib.lib().dv_fast_pass_batch, windows, options, 0)
+
+
+def fast_pass_batch_device(windows: Sequence[dict], options: Optional[dict] = None, stream: int = 0,
+                           with_stats: bool = False):
+  """`fast_pass_batch` with every (window, haplotype) in ONE kernel launch (csrc/fast_pass.hip); identical arrays.
+  A haplotype longer than _lib.DV_FAST_PASS_DEVICE_MAX_HAPLOTYPE is run by the host code inside the call.  There is
+  no CPU fallback: without a GPU this raises DV_ERR_NO_DEVICE.  with_stats: -> (windows, _lib.DvFastPassStats)."""
+  res = _fast_pass(_lib.lib().dv_fast_pass_batch_device, windows, options, stream)
+  if not with_stats:
+    return res
+  stats = _lib.DvFastPassStats()
+  _lib.check(_lib.lib().dv_fast_pass_device_last_stats(C.byref(stats)))
+  return res, stats
 
 
 def realign_reads_to_haplotype(haplotype: str, reads: Sequence, contig: str, ref_start: int, ref_end: int,

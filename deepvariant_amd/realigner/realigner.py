@@ -45,6 +45,8 @@ _NATIVE_THREADS = max(0, int(os.environ.get('DV_REALIGN_THREADS', '0')))
 # DV_REALIGN_DEVICE=1: the table path runs its local alignments on the GPU (dv_realign_regions_device).  Off by
 # default; the results are the host route's either way.  On that route DV_REALIGN_DEVICE_TRACEBACK=1 (read by the
 # library at each call) moves the CIGARs' banded trace-back into the same kernel launch; off by default too.
+# DV_REALIGN_DEVICE_FASTPASS=1 (read by the library at each call as well) moves the fast pass of every window there,
+# one more launch per call and no k-mer index on the host; off by default, same results.
 _DEVICE_ALIGN = os.environ.get('DV_REALIGN_DEVICE', '0') == '1'
 _pool: Optional[concurrent.futures.ThreadPoolExecutor] = None
 
@@ -312,6 +314,8 @@ class RealignJob:
     self._device_align = device_align
     self.device_stats = None       # _lib.DvRealignDeviceStats of the call, device route only
     self.traceback_stats = None    # _lib.DvRealignTracebackStats of the call, device route only
+    self.fast_pass_stats = None    # _lib.DvFastPassStats of the call, device route only (all zero unless
+                                   # DV_REALIGN_DEVICE_FASTPASS=1 moved the fast pass to the device)
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -358,6 +362,9 @@ class RealignJob:
       traceback = _lib.DvRealignTracebackStats()
       _lib.check(_lib.lib().dv_local_align_device_last_traceback_stats(C.byref(traceback)))
       self.traceback_stats = traceback
+      fast_pass = _lib.DvFastPassStats()
+      _lib.check(_lib.lib().dv_fast_pass_device_last_stats(C.byref(fast_pass)))
+      self.fast_pass_stats = fast_pass
     else:
       _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
                                                C.byref(out)))

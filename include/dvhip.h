@@ -500,7 +500,10 @@ enum {
   DV_ALIGNER_LOCAL_ALIGN_READS = 4,  /* SswAlignReadsToHaplotypes(arg = score threshold) */
   DV_ALIGNER_SCORE_THRESHOLD = 5,    /* CalculateSswAlignmentScoreThreshold */
   DV_ALIGNER_ALIGN_IN_PHASES = 6     /* test hook: arg != 0 makes dv_aligner_align_reads run as the device route
-                                        does -- prepare, ONE batch of pairs through the host aligner, finish */
+                                        does -- prepare, ONE batch of pairs through the host aligner, finish;
+                                        arg == 2 also splits the prepare step as DV_REALIGN_DEVICE_FASTPASS does --
+                                        reads, dv_fast_pass_batch's host code with its arrays installed, pairs --
+                                        and never builds the k-mer index */
 };
 int dv_aligner_stage(dv_aligner* a, int32_t stage, int32_t arg);
 int dv_aligner_fast_align(dv_aligner* a, const char* haplotype, int32_t* haplotype_score,
@@ -581,6 +584,65 @@ int dv_local_align_device_last_traceback_stats(dv_realign_traceback_stats* out);
  * 0 / 0 where there is no CIGAR (nothing aligns, or dv_local_align fails). */
 int dv_local_align_band(const char* reference, const char* query, int32_t match, int32_t mismatch,
                         int32_t gap_open, int32_t gap_extend, int32_t* band, int32_t* runs);
+
+/* ---- the fast pass over many windows in one call -----------------------------------
+ * FastPassAligner::FastAlignReadsToHaplotype (fast_pass_aligner.cc:207-286) for every (window, haplotype)
+ * of a batch, without the k-mer index and without its order dependence.  For a haplotype H of n bytes, a read
+ * R of L bytes (upper-cased by the call), k = kmer_size, M = max_num_of_mismatches:
+ *   - a read with L <= k or L > n takes no part;
+ *   - a seed is (i, off) with H[i..i+k) == R[off..off+k) byte for byte ('N' equals only 'N'); it names the
+ *     start s = max(0, i - off), which takes part when s + L <= n; the discovery key of (R, s) is its
+ *     lexicographically smallest seed;
+ *   - mm(R, s) counts the positions p with H[s+p] != R[p] where neither byte is 'N'; (R, s) is accepted when
+ *     it has a seed and mm <= M; its score is (L - mm) * match - mm * mismatch;
+ *   - a read's alignment is its accepted start with the largest score > 0, the smallest discovery key on
+ *     ties; none: position -1, score 0;
+ *   - every accepted (R, s) covers haplotype positions [key.i, s + L); a haplotype whose bytes differ from
+ *     the window's reference is discarded (score 0, no alignments) when a position i <= n - k with
+ *     ref_prefix_len <= i < n - ref_suffix_len stays uncovered although H[i..i+k) occurs in some read longer
+ *     than k (the host looks at a position's coverage only after its k-mer was found in the index);
+ *   - the haplotype's score is the sum of its reads' scores.
+ * Sequences are raw bytes: sequence s is bytes[seq_off[s], seq_off[s + 1]).  Haplotypes are taken as given.
+ * Haplotype h of the call is the h-th of all windows' haplotypes in window order, and its reads' rows are
+ * [sum of n_reads over the haplotypes before it, + its window's n_reads).  read_position is -1 where the read is
+ * not aligned.  options: as dv_aligner_create (0 keeps the class default; only match, mismatch, kmer_size and
+ * max_num_of_mismatches are read).  Argument errors (null pointers, negative counts or lengths, descending
+ * offsets, a range or index outside the table, options the class refuses) are DV_ERR_INVALID_ARGUMENT
+ * before any device work. */
+typedef struct dv_fast_pass_window {
+  int32_t first_read, n_reads;             /* its reads: sequences [first_read, first_read + n_reads) */
+  int32_t first_haplotype, n_haplotypes;   /* its haplotypes: sequences [first_haplotype, ...) */
+  int32_t reference;                       /* the sequence holding the window's reference, or -1: no haplotype is it */
+  int32_t ref_prefix_len, ref_suffix_len;  /* reference padding around the haplotypes */
+  int32_t reserved;
+} dv_fast_pass_window;
+/* Host code (FastPassAligner itself, k-mer index included). */
+int dv_fast_pass_batch(int32_t n_seqs, const char* bytes, const int64_t* seq_off, int32_t n_windows,
+                       const dv_fast_pass_window* windows, const dv_aligner_options* options, void* stream,
+                       int32_t* haplotype_score, int32_t* haplotype_discarded, int32_t* read_position,
+                       int32_t* read_score);
+/* The same on the device (csrc/fast_pass.hip): one upload, ONE kernel launch over every (window, haplotype),
+ * one download and one synchronisation on `stream` (NULL = a non-blocking stream the library owns); identical
+ * arrays.  A haplotype longer than DV_FAST_PASS_DEVICE_MAX_HAPLOTYPE (it lives in LDS beside its coverage
+ * marks; reads are never longer than their haplotype) or scoring values past DV_FAST_PASS_DEVICE_MAX_SCORING
+ * are not an error: the host code runs that haplotype inside the same call.  No haplotypes is DV_OK without a
+ * device; no device is DV_ERR_NO_DEVICE (there is no CPU fallback). */
+#define DV_FAST_PASS_DEVICE_MAX_HAPLOTYPE 8192
+#define DV_FAST_PASS_DEVICE_MAX_SCORING 32767
+int dv_fast_pass_batch_device(int32_t n_seqs, const char* bytes, const int64_t* seq_off, int32_t n_windows,
+                              const dv_fast_pass_window* windows, const dv_aligner_options* options, void* stream,
+                              int32_t* haplotype_score, int32_t* haplotype_discarded, int32_t* read_position,
+                              int32_t* read_score);
+typedef struct dv_fast_pass_stats {
+  int64_t haplotypes;          /* (window, haplotype) items asked for */
+  int64_t haplotypes_on_host;  /* of them outside the kernel's limits: run by the host code */
+  int64_t pairs;               /* (haplotype, read) pairs of the items on the device */
+  int64_t cells;               /* diagonals x read length over those pairs: byte comparisons at most */
+  int64_t launches;            /* kernel launches */
+} dv_fast_pass_stats;
+/* What the calling thread's last dv_fast_pass_batch_device or dv_realign_regions_device did with the fast
+ * pass (all zero when the latter ran it on the host: DV_REALIGN_DEVICE_FASTPASS unset). */
+int dv_fast_pass_device_last_stats(dv_fast_pass_stats* out);
 
 /* ---- local assembly for the window realigner (host only) -----------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
@@ -670,7 +732,11 @@ void dv_realign_result_free(dv_realign_result* r);
  * launch on `stream` (NULL = the library's own), between a host loop that prepares the windows and one
  * that finishes them.  `out` / `arrays` are identical, array by array, to dv_realign_regions' and are
  * freed by dv_realign_result_free.  `stats` (may be NULL) receives what the device did.  Opt-in:
- * dv_realign_regions itself never touches a device.  DV_ERR_NO_DEVICE without a GPU. */
+ * dv_realign_regions itself never touches a device.  DV_ERR_NO_DEVICE without a GPU.
+ * DV_REALIGN_DEVICE_FASTPASS=1 in the environment, read at each call, also moves the fast pass of every
+ * window there (dv_fast_pass_batch_device's kernel: one more launch per call, no k-mer index on the host);
+ * unset or 0 it runs on the host threads.  Results are identical either way; `stats` keeps counting the
+ * sweep kernel only, dv_fast_pass_device_last_stats reports the fast pass. */
 int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
                               void* stream, dv_realign_result** out, dv_realign_output* arrays,
                               dv_realign_device_stats* stats);

@@ -8,12 +8,15 @@ time (the spread), and the device route's stats: pairs, forward-pass cells, shar
 Where the library has the device trace-back, the device route is measured in two arms that alternate with the
 host route: `device` with DV_REALIGN_DEVICE_TRACEBACK=0 (every CIGAR's banded trace-back on the host) and
 `device_traceback` with =1 (in the kernel); the split of the trace-backs and the widest band are in `stats`.
-Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
+Where it has the device fast pass, `device_fast_pass` is one more alternating arm: DV_REALIGN_DEVICE_FASTPASS=1 with the
+trace-back on the host, against `device` with both switches 0; its (haplotype, read) pairs and diagonal cells are in
+`stats`.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
 measures an older checkout.  Kernel time is not measured here: run this under
 `rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
-`cells` by local_align_sweeps' time per call.
+`cells` by local_align_sweeps' time per call (fast_pass_kernel: `fast_pass_cells`, with DV_REALIGN_DEVICE_FASTPASS=1
+-- the tool sets the switches per arm itself, so profile with `--arms device_fast_pass`).
 
-  python tools/realign_bench.py [--regions 100] [--repeats 7] [--threads 16,4] [--out result.json]
+  python tools/realign_bench.py [--regions 100] [--repeats 7] [--threads 16,4] [--arms a,b] [--out result.json]
 """
 import argparse
 import dataclasses
@@ -61,6 +64,7 @@ def main(argv=None):
   ap.add_argument('--regions', type=int, default=100, help='calling regions per batch')
   ap.add_argument('--repeats', type=int, default=7)
   ap.add_argument('--threads', default='16,4', help='DV_REALIGN_THREADS settings to measure')
+  ap.add_argument('--arms', default='', help='time only these arms (comma-separated); default: every arm')
   ap.add_argument('--out', default='')
   args = ap.parse_args(argv)
   if _lib.device_count() == 0:
@@ -85,18 +89,23 @@ def main(argv=None):
   regions, tables = [b[0] for b in batch], [b[1] for b in batch]
   has_device = hasattr(_lib, 'DvRealignDeviceStats')
   has_traceback = hasattr(_lib, 'DvRealignTracebackStats')
-  switch = 'DV_REALIGN_DEVICE_TRACEBACK'
+  has_fast_pass = hasattr(_lib, 'DvFastPassStats')
+  switch, fast_pass_switch = 'DV_REALIGN_DEVICE_TRACEBACK', 'DV_REALIGN_DEVICE_FASTPASS'
   if has_device:
     routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
               'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
     if has_traceback:
       routes['device_traceback'] = routes['device']
+    if has_fast_pass:
+      routes['device_fast_pass'] = routes['device']
   else:
     routes = {'host': R.Realigner(R.realigner_config(), ref)}
 
   def run(route):
     if has_traceback:
       os.environ[switch] = '1' if route == 'device_traceback' else '0'      # read by the library at each call
+    if has_fast_pass:
+      os.environ[fast_pass_switch] = '1' if route == 'device_fast_pass' else '0'
     gc.collect()
     t0 = time.perf_counter()
     job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
@@ -124,9 +133,16 @@ def main(argv=None):
     assert job.device_stats.launches == 1 and tb.traced_on_device > 0
     result['stats'].update({'traced_on_device': tb.traced_on_device, 'traced_on_host': tb.traced_on_host,
                             'band_cells': tb.band_cells, 'widest_band': tb.widest_band})
+  if has_fast_pass:
+    _, _, got, job = run('device_fast_pass')
+    assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device fast pass differs'
+    fp = job.fast_pass_stats
+    assert job.device_stats.launches == 1 and fp.launches == 1 and fp.haplotypes > 0
+    result['stats'].update({'fast_pass_haplotypes': fp.haplotypes, 'fast_pass_haplotypes_on_host': fp.haplotypes_on_host,
+                            'fast_pass_pairs': fp.pairs, 'fast_pass_cells': fp.cells, 'fast_pass_launches': fp.launches})
   for threads in [int(t) for t in args.threads.split(',')]:
     R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
-    runs = {route: [] for route in routes}
+    runs = {route: [] for route in routes if not args.arms or route in args.arms.split(',')}
     for route in runs:
       run(route)
     for _ in range(args.repeats):
@@ -139,11 +155,16 @@ def main(argv=None):
                       'native_call_ms': ms(float(np.median([x[1] for x in r]))),
                       'realign_tables_runs_ms': [ms(x[0]) for x in r],
                       'native_call_runs_ms': [ms(x[1]) for x in r]}
-    if has_device:
+    if 'device' in entry and 'host' in entry:
       entry['device_over_host_native'] = round(entry['device']['native_call_ms'] / entry['host']['native_call_ms'], 4)
-    if has_traceback:
+    if 'device_traceback' in entry and 'device' in entry:
       entry['traceback_over_device_native'] = round(entry['device_traceback']['native_call_ms'] /
                                                     entry['device']['native_call_ms'], 4)
+    if 'device_fast_pass' in entry and 'device' in entry:
+      entry['fast_pass_over_device_native'] = round(entry['device_fast_pass']['native_call_ms'] /
+                                                    entry['device']['native_call_ms'], 4)
+      entry['fast_pass_median_below_device_min'] = (entry['device_fast_pass']['native_call_ms'] <
+                                                    min(entry['device']['native_call_runs_ms']))
     result['threads'][str(threads)] = entry
   line = json.dumps(result)
   print(line)
