@@ -55,7 +55,8 @@ ABI_SYMBOLS = [
     'dv_local_align_device_last_traceback_stats', 'dv_local_align_band',
     'dv_fast_pass_batch', 'dv_fast_pass_batch_device', 'dv_fast_pass_device_last_stats',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
-    'dv_debruijn_graphviz', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
+    'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
+    'dv_debruijn_device_last_stats', 'dv_debruijn_from_compact', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
     'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
@@ -224,6 +225,30 @@ class DvRealignTracebackStats(C.Structure):
 class DvDebruijnOptions(C.Structure):
   _fields_ = [(n, C.c_int32) for n in ('min_k', 'max_k', 'step_k', 'min_mapq', 'min_base_quality',
                                        'min_edge_weight', 'max_num_paths', 'disable_graph_pruning')]
+
+
+# include/dvhip.h: what one window may measure for the device form of the assembly (a larger one is built by the host
+# code inside the same call)
+DV_DEBRUIJN_DEVICE_MAX_VERTICES = 8192
+DV_DEBRUIJN_DEVICE_MAX_EDGES = 8192
+DV_DEBRUIJN_DEVICE_MAX_BASES = 131072
+
+
+class DvDebruijnWindow(C.Structure):
+  _fields_ = [('reference', C.c_int32), ('first_read', C.c_int32), ('n_reads', C.c_int32), ('reserved', C.c_int32)]
+
+
+class DvDebruijnCompact(C.Structure):
+  _fields_ = [('k', C.POINTER(C.c_int32)), ('k_tries', C.POINTER(C.c_int32)), ('vertex_off', C.POINTER(C.c_int64)),
+              ('vertex_seq', C.POINTER(C.c_int32)), ('vertex_pos', C.POINTER(C.c_int32)),
+              ('edge_off', C.POINTER(C.c_int64)), ('edge_from', C.POINTER(C.c_int32)), ('edge_to', C.POINTER(C.c_int32)),
+              ('edge_weight', C.POINTER(C.c_int32)), ('edge_is_ref', C.POINTER(C.c_int32)),
+              ('edge_seq', C.POINTER(C.c_int32)), ('edge_pos', C.POINTER(C.c_int32))]
+
+
+class DvDebruijnDeviceStats(C.Structure):
+  _fields_ = [('windows', C.c_int64), ('windows_on_host', C.c_int64), ('kmers', C.c_int64), ('k_tries', C.c_int64),
+              ('launches', C.c_int64), ('windows_rejected', C.c_int64)]
 
 
 class DvRealignRegion(C.Structure):
@@ -441,6 +466,16 @@ def lib():
     l.dv_debruijn_kmer_size.argtypes = [C.c_void_p]
     l.dv_debruijn_haplotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_debruijn_graphviz.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_debruijn_compact_batch.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.dv_debruijn_compact_batch_device.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.dv_debruijn_compact_free.argtypes = [C.c_void_p]
+    l.dv_debruijn_compact_free.restype = None
+    l.dv_debruijn_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_debruijn_from_compact.argtypes = ([C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7)
     l.dv_realign_regions.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_realign_result_free.argtypes = [C.c_void_p]
     l.dv_realign_result_free.restype = None

@@ -346,6 +346,70 @@ int dv_debruijn_build(const char* ref, int64_t ref_len, const uint8_t* bases, co
   return DV_OK;
 }
 
+int dv_debruijn_from_compact(const char* ref, int64_t ref_len, const uint8_t* bases, const uint8_t* quals,
+                             int64_t n_bases, const uint32_t* read_seq_off, const uint8_t* read_mapq,
+                             int32_t n_table_reads, const int32_t* reads, int32_t n_reads,
+                             const dv_debruijn_options* o, int32_t k, int32_t n_vertices, const int32_t* vertex_seq,
+                             const int32_t* vertex_pos, int32_t n_edges, const int32_t* edge_from,
+                             const int32_t* edge_to, const int32_t* edge_weight, const int32_t* edge_is_ref,
+                             const int32_t* edge_seq, const int32_t* edge_pos, dv_debruijn_graph** out) {
+  if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_debruijn_from_compact: null out");
+  *out = nullptr;
+  if (!ref || ref_len < 0 || !o || n_reads < 0 || n_table_reads < 0 || n_bases < 0 || n_vertices < 0 || n_edges < 0 ||
+      (n_reads > 0 && (!bases || !quals || !read_seq_off || !read_mapq || !reads)) ||
+      (n_vertices > 0 && (!vertex_seq || !vertex_pos)) ||
+      (n_edges > 0 && (!edge_from || !edge_to || !edge_weight || !edge_is_ref || !edge_seq || !edge_pos))) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_debruijn_from_compact: null argument or negative count");
+  }
+  if (o->step_k <= 0 || o->min_k <= 0) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_debruijn_from_compact: min_k and step_k must be positive");
+  }
+  try {
+    std::vector<dv::AssemblyRead> rs;
+    rs.reserve(n_reads);
+    for (int32_t i = 0; i < n_reads; ++i) {
+      const int32_t r = reads[i];
+      if (r < 0 || r >= n_table_reads || read_seq_off[r + 1] < read_seq_off[r] || read_seq_off[r + 1] > n_bases) {
+        return dv::fail(DV_ERR_BAD_INPUT, "dv_debruijn_from_compact: read index or its bases outside the table");
+      }
+      const uint32_t a = read_seq_off[r], b = read_seq_off[r + 1];
+      rs.push_back(dv::AssemblyRead{std::string_view(reinterpret_cast<const char*>(bases) + a, b - a), quals + a,
+                                    read_mapq[r]});
+    }
+    dv::DeBruijnOptions opt;
+    opt.min_k = o->min_k;
+    opt.max_k = o->max_k;
+    opt.step_k = o->step_k;
+    opt.min_mapq = o->min_mapq;
+    opt.min_base_quality = o->min_base_quality;
+    opt.min_edge_weight = o->min_edge_weight;
+    opt.max_num_paths = o->max_num_paths;
+    opt.disable_graph_pruning = o->disable_graph_pruning != 0;
+    dv::CompactGraph c;
+    c.k = k;
+    c.vertex_seq.assign(vertex_seq, vertex_seq + n_vertices);
+    c.vertex_pos.assign(vertex_pos, vertex_pos + n_vertices);
+    c.edge_from.assign(edge_from, edge_from + n_edges);
+    c.edge_to.assign(edge_to, edge_to + n_edges);
+    c.edge_weight.assign(edge_weight, edge_weight + n_edges);
+    c.edge_is_ref.assign(edge_is_ref, edge_is_ref + n_edges);
+    c.edge_seq.assign(edge_seq, edge_seq + n_edges);
+    c.edge_pos.assign(edge_pos, edge_pos + n_edges);
+    std::unique_ptr<dv::DeBruijnGraph> g;
+    std::string error;
+    if (!dv::DeBruijnGraph::from_compact(std::string_view(ref, static_cast<size_t>(ref_len)), rs, opt, c, &g, &error)) {
+      return dv::fail(DV_ERR_BAD_INPUT, "dv_debruijn_from_compact: " + error);
+    }
+    if (!g) return DV_OK;            // k = 0: *out stays NULL
+    auto h = std::make_unique<dv_debruijn_graph>();
+    h->g = std::move(g);
+    *out = h.release();
+    return DV_OK;
+  } catch (const std::bad_alloc&) {
+    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_debruijn_from_compact: out of host memory");
+  }
+}
+
 void dv_debruijn_destroy(dv_debruijn_graph* h) { delete h; }
 
 int dv_debruijn_kmer_size(const dv_debruijn_graph* h) {

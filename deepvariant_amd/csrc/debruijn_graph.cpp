@@ -49,6 +49,136 @@ std::unique_ptr<DeBruijnGraph> DeBruijnGraph::build(std::string_view ref, const 
   return nullptr;
 }
 
+void DeBruijnGraph::build_compact(std::string_view ref, const std::vector<AssemblyRead>& reads,
+                                  const DeBruijnOptions& options, CompactGraph* out) {
+  *out = CompactGraph();
+  if (options.step_k <= 0) return;
+  const int max_k = std::min(options.max_k, static_cast<int>(ref.size()) - 1);
+  int tries = 0;
+  bool started = false;            // a repeat-free k stays repeat-free for every larger k
+  for (int k = options.min_k; k <= max_k; k += options.step_k) {
+    if (k <= 0) continue;
+    ++tries;
+    if (!started) {
+      DeBruijnOptions one = options;
+      one.min_k = one.max_k = k;
+      if (first_k_without_reference_repeat(ref, one, k) < 0) continue;
+      started = true;
+    }
+    DeBruijnGraph g(ref, reads, options, k);
+    if (g.has_cycle()) continue;
+    *out = g.compact();
+    break;
+  }
+  out->k_tries = tries;
+}
+
+CompactGraph DeBruijnGraph::compact() const {
+  CompactGraph c;
+  c.k = k_;
+  for (const Occurrence& o : vertex_first_) {
+    c.vertex_seq.push_back(o.seq);
+    c.vertex_pos.push_back(o.pos);
+  }
+  for (size_t e = 0; e < edges_.size(); ++e) {
+    c.edge_from.push_back(edges_[e].from);
+    c.edge_to.push_back(edges_[e].to);
+    c.edge_weight.push_back(edges_[e].weight);
+    c.edge_is_ref.push_back(edges_[e].is_ref ? 1 : 0);
+    c.edge_seq.push_back(edge_first_[e].seq);
+    c.edge_pos.push_back(edge_first_[e].pos);
+  }
+  return c;
+}
+
+bool DeBruijnGraph::from_compact(std::string_view ref, const std::vector<AssemblyRead>& reads,
+                                 const DeBruijnOptions& options, const CompactGraph& c,
+                                 std::unique_ptr<DeBruijnGraph>* out, std::string* error) {
+  out->reset();
+  auto bad = [&](const char* what) {
+    if (error) *error = what;
+    return false;
+  };
+  const int k = c.k;
+  if (k == 0) return true;
+  const size_t nv = c.vertex_seq.size(), ne = c.edge_from.size();
+  if (k < 0 || static_cast<size_t>(k) >= ref.size()) return bad("k outside [1, |ref| - 1]");
+  if (c.vertex_pos.size() != nv || c.edge_to.size() != ne || c.edge_weight.size() != ne ||
+      c.edge_is_ref.size() != ne || c.edge_seq.size() != ne || c.edge_pos.size() != ne) {
+    return bad("arrays of different lengths");
+  }
+  const size_t n_ref = ref.size() - static_cast<size_t>(k) + 1;       // the reference's k-mers: all distinct
+  if (nv < n_ref) return bad("fewer vertices than the reference has k-mers");
+  auto length_of = [&](int32_t seq) {
+    return static_cast<int64_t>(seq == 0 ? ref.size() : reads[static_cast<size_t>(seq) - 1].bases.size());
+  };
+  for (size_t v = 0; v < nv; ++v) {
+    const int32_t seq = c.vertex_seq[v], pos = c.vertex_pos[v];
+    if (seq < 0 || static_cast<size_t>(seq) > reads.size() || pos < 0 || static_cast<int64_t>(pos) + k > length_of(seq)) {
+      return bad("a vertex occurrence outside its sequence");
+    }
+    if (v < n_ref ? (seq != 0 || static_cast<size_t>(pos) != v) : seq == 0) {
+      return bad("the reference's vertices are not 0 .. |ref| - k, in order");
+    }
+    if (v > 0 && (seq < c.vertex_seq[v - 1] || (seq == c.vertex_seq[v - 1] && pos <= c.vertex_pos[v - 1]))) {
+      return bad("vertices not sorted by first occurrence");
+    }
+  }
+  for (size_t e = 0; e < ne; ++e) {
+    const int32_t seq = c.edge_seq[e], pos = c.edge_pos[e];
+    if (c.edge_from[e] < 0 || static_cast<size_t>(c.edge_from[e]) >= nv || c.edge_to[e] < 0 ||
+        static_cast<size_t>(c.edge_to[e]) >= nv) {
+      return bad("an edge endpoint out of range");
+    }
+    if (seq < 0 || static_cast<size_t>(seq) > reads.size() || pos < 0 ||
+        static_cast<int64_t>(pos) + k + 1 > length_of(seq)) {
+      return bad("an edge occurrence outside its sequence");
+    }
+    if (c.edge_weight[e] < 1) return bad("an edge weight below 1");
+    if (e > 0 && (seq < c.edge_seq[e - 1] || (seq == c.edge_seq[e - 1] && pos <= c.edge_pos[e - 1]))) {
+      return bad("edges not sorted by first occurrence");
+    }
+  }
+  std::unique_ptr<DeBruijnGraph> g(new DeBruijnGraph(options, k));
+  std::vector<std::string> upper(reads.size());        // a read's upper-cased bases, made when a vertex first needs them
+  for (size_t v = 0; v < nv; ++v) {
+    const int32_t seq = c.vertex_seq[v];
+    std::string_view from = ref;
+    if (seq > 0) {
+      std::string& u = upper[static_cast<size_t>(seq) - 1];
+      const std::string_view raw = reads[static_cast<size_t>(seq) - 1].bases;
+      if (u.empty() && !raw.empty()) {
+        u.assign(raw);
+        for (char& ch : u) {
+          if (ch >= 'a' && ch <= 'z') ch = static_cast<char>(ch - 'a' + 'A');
+        }
+      }
+      from = u;
+    }
+    g->kmers_.emplace_back(from.substr(static_cast<size_t>(c.vertex_pos[v]), static_cast<size_t>(k)));
+    g->vertex_alive_.push_back(1);
+    g->vertex_first_.push_back(Occurrence{seq, c.vertex_pos[v]});
+    g->vertex_of_.emplace(std::string_view(g->kmers_.back()), static_cast<int>(v));
+  }
+  g->out_.resize(nv);
+  g->in_.resize(nv);
+  for (size_t e = 0; e < ne; ++e) {
+    g->edges_.push_back(Edge{c.edge_from[e], c.edge_to[e], c.edge_weight[e], c.edge_is_ref[e] != 0, true});
+    g->edge_first_.push_back(Occurrence{c.edge_seq[e], c.edge_pos[e]});
+    g->out_[static_cast<size_t>(c.edge_from[e])].push_back(static_cast<int>(e));
+    g->in_[static_cast<size_t>(c.edge_to[e])].push_back(static_cast<int>(e));
+  }
+  g->source_ = 0;
+  g->sink_ = static_cast<int>(n_ref) - 1;
+  if (options.disable_graph_pruning) {
+    g->prune_lite();
+  } else {
+    g->prune();
+  }
+  *out = std::move(g);
+  return true;
+}
+
 DeBruijnGraph::DeBruijnGraph(std::string_view ref, const std::vector<AssemblyRead>& reads,
                              const DeBruijnOptions& options, int k)
     : options_(options), k_(k) {
@@ -56,23 +186,25 @@ DeBruijnGraph::DeBruijnGraph(std::string_view ref, const std::vector<AssemblyRea
   source_ = vertex_of_.at(ref.substr(0, k_));
   sink_ = vertex_of_.at(ref.substr(ref.size() - k_, k_));
   for (const AssemblyRead& read : reads) {
+    ++walking_;
     if (read.mapq >= options_.min_mapq) add_edges_for_read(read);
   }
 }
 
-int DeBruijnGraph::ensure_vertex(std::string_view kmer) {
+int DeBruijnGraph::ensure_vertex(std::string_view kmer, int pos) {
   auto it = vertex_of_.find(kmer);
   if (it != vertex_of_.end()) return it->second;
   const int v = static_cast<int>(kmers_.size());
   kmers_.emplace_back(kmer);
   vertex_alive_.push_back(1);
+  vertex_first_.push_back(Occurrence{walking_, pos});
   out_.emplace_back();
   in_.emplace_back();
   vertex_of_.emplace(std::string_view(kmers_.back()), v);
   return v;
 }
 
-void DeBruijnGraph::add_edge(int from, int to, bool is_ref) {
+void DeBruijnGraph::add_edge(int from, int to, bool is_ref, int pos) {
   for (int e : out_[from]) {
     if (edges_[e].to == to) {
       ++edges_[e].weight;
@@ -82,6 +214,7 @@ void DeBruijnGraph::add_edge(int from, int to, bool is_ref) {
   }
   const int e = static_cast<int>(edges_.size());
   edges_.push_back(Edge{from, to, 1, is_ref, true});
+  edge_first_.push_back(Occurrence{walking_, pos});
   out_[from].push_back(e);
   in_[to].push_back(e);
 }
@@ -91,10 +224,10 @@ void DeBruijnGraph::add_edge(int from, int to, bool is_ref) {
 // leaves its first k-mer behind as a vertex.
 void DeBruijnGraph::add_kmers_and_edges(std::string_view bases, int start, int end, bool is_ref) {
   if (end <= 0) return;
-  int prev = ensure_vertex(bases.substr(start, k_));
+  int prev = ensure_vertex(bases.substr(start, k_), start);
   for (int i = start + 1; i <= end; ++i) {
-    const int cur = ensure_vertex(bases.substr(i, k_));
-    add_edge(prev, cur, is_ref);
+    const int cur = ensure_vertex(bases.substr(i, k_), i);
+    add_edge(prev, cur, is_ref, i - 1);
     prev = cur;
   }
 }

@@ -41,12 +41,37 @@ struct AssemblyRead {         // what the graph reads of a nucleus Read
   int mapq;
 };
 
+// The graph of the winning k BEFORE pruning, as integers: what the device builds (debruijn.hip) and what
+// from_compact turns back into the object.  An occurrence is (seq, pos): seq 0 is the reference window, seq 1 + j
+// the j-th read of the list (a read below min_mapq keeps its number and never occurs), pos the offset of the
+// k-mer's first byte.  Vertices and edges are in insertion order, which is ascending first occurrence: the
+// constructor walks the reference, then the reads in order, each left to right.  An edge's occurrence is that of
+// its `from` k-mer in the walk that created the edge.
+struct CompactGraph {
+  int k = 0;                  // 0: build returns null
+  int k_tries = 0;            // k values of the schedule visited, the reference-repeat test included
+  std::vector<int32_t> vertex_seq, vertex_pos;
+  std::vector<int32_t> edge_from, edge_to, edge_weight, edge_is_ref, edge_seq, edge_pos;
+};
+
 class DeBruijnGraph {
  public:
   // nullptr when no k in range gives an acyclic graph (the caller then keeps the reference
   // as the only haplotype)
   static std::unique_ptr<DeBruijnGraph> build(std::string_view ref, const std::vector<AssemblyRead>& reads,
                                               const DeBruijnOptions& options);
+
+  // build up to, but not including, prune / prune_lite, as integers (out->k = 0 where build returns null)
+  static void build_compact(std::string_view ref, const std::vector<AssemblyRead>& reads, const DeBruijnOptions& options,
+                            CompactGraph* out);
+  // The object build returns, rebuilt from its compact form and pruned as build prunes; null for k = 0.  `compact`
+  // is validated before anything is indexed by it (occurrences inside their sequences, endpoints in range, the
+  // reference's vertices 0 .. |ref| - k in order, both lists sorted by occurrence): false and *error on a
+  // malformed one.
+  static bool from_compact(std::string_view ref, const std::vector<AssemblyRead>& reads, const DeBruijnOptions& options,
+                           const CompactGraph& compact, std::unique_ptr<DeBruijnGraph>* out, std::string* error);
+  // the unpruned graph of this object (pruning only clears `alive` marks)
+  CompactGraph compact() const;
 
   int kmer_size() const { return k_; }
   std::vector<std::string> candidate_haplotypes() const;
@@ -58,10 +83,15 @@ class DeBruijnGraph {
     bool is_ref, alive;
   };
 
+  struct Occurrence {
+    int32_t seq, pos;
+  };
+
   DeBruijnGraph(std::string_view ref, const std::vector<AssemblyRead>& reads, const DeBruijnOptions& options,
                 int k);
-  int ensure_vertex(std::string_view kmer);
-  void add_edge(int from, int to, bool is_ref);
+  DeBruijnGraph(const DeBruijnOptions& options, int k) : options_(options), k_(k) {}
+  int ensure_vertex(std::string_view kmer, int pos);
+  void add_edge(int from, int to, bool is_ref, int pos);
   void add_kmers_and_edges(std::string_view bases, int start, int end, bool is_ref);
   void add_edges_for_read(const AssemblyRead& read);
   bool has_cycle() const;
@@ -79,6 +109,8 @@ class DeBruijnGraph {
   std::unordered_map<std::string_view, int> vertex_of_;
   std::vector<Edge> edges_;                            // insertion order
   std::vector<std::vector<int>> out_, in_;             // vertex -> edge ids
+  int walking_ = 0;                                    // the sequence the constructor is walking
+  std::vector<Occurrence> vertex_first_, edge_first_;  // first occurrence, parallel to kmers_ / edges_
 };
 
 }  // namespace dv

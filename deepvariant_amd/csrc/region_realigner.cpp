@@ -21,7 +21,10 @@
 //   2b, once: the pairs of all windows go through one kernel launch; the CIGARs of the pairs that
 //       aligned (LocalAligner::complete) are spread over the worker pool;
 //   2c, one task per window: FastPassAligner::finish_alignments.
-// Phase 1, the read assignment and the result arrays are the same code for both routes.
+// With DV_REALIGN_DEVICE_ASSEMBLY=1 the device route's phase 1 becomes 1a, the batch's window list; 1b, once, the
+// graph of every window in one kernel launch (debruijn.hip), choice of k and cycle test included; 1c, one task per
+// window: DeBruijnGraph::from_compact (which prunes), candidate_haplotypes and the comparison with the reference.
+// The read assignment and the result arrays are the same code for both routes.
 //
 // Tasks are independent (each builds its own graph / aligner; the aligner's scratch buffers are
 // thread_local), so a phase is a parallel loop over a task list ordered longest first.
@@ -40,6 +43,7 @@
 
 #include <unistd.h>
 
+#include "debruijn_device.h"
 #include "debruijn_graph.h"
 #include "dv_internal.h"
 #include "fast_pass_aligner.h"
@@ -213,6 +217,7 @@ int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_region
     if (stats) *stats = dv_realign_device_stats{0, 0, 0, 0};
     dv::last_traceback_stats() = dv::TracebackStats();
     dv::last_fast_pass_stats() = dv::FastPassStats();
+    dv::last_assembly_stats() = dv::AssemblyStats();
     const DeviceRoute device{stream, stats};
     return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
   } catch (const std::bad_alloc&) {
@@ -283,25 +288,54 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
   dbg.disable_graph_pruning = o->dbg.disable_graph_pruning != 0;
 
   // ---- phase 1: assembly
-  parallel_tasks(longest_first(cost), n_threads, [&](int t) {
-    Window& win = windows[t];
+  // a window's reference and the reads that overlap it, in row order
+  auto assembly_window = [&](const Window& win) {
     const dv_realign_region& r = regions[win.region];
     const int64_t a = r.window_start[win.index], b = r.window_end[win.index];
-    const std::string_view ref(r.ref + (a - r.ref_start), static_cast<size_t>(b - a));
-    std::vector<dv::AssemblyRead> reads;
+    dv::AssemblyWindow aw;
+    aw.ref = std::string_view(r.ref + (a - r.ref_start), static_cast<size_t>(b - a));
     for (int32_t i = 0; i < r.n_reads; ++i) {
       if (r.read_end[i] > a && b > r.read_start[i]) {
         const uint32_t s0 = r.read_seq_off[i], s1 = r.read_seq_off[i + 1];
-        reads.push_back(dv::AssemblyRead{std::string_view(reinterpret_cast<const char*>(r.bases) + s0, s1 - s0),
-                                         r.quals + s0, r.read_mapq[i]});
+        aw.reads.push_back(dv::AssemblyRead{std::string_view(reinterpret_cast<const char*>(r.bases) + s0, s1 - s0),
+                                            r.quals + s0, r.read_mapq[i]});
       }
     }
-    auto graph = dv::DeBruijnGraph::build(ref, reads, dbg);
+    return aw;
+  };
+  auto keep_haplotypes = [](Window& win, const dv::DeBruijnGraph* graph, std::string_view ref) {
     if (!graph) return;                                   // haplotypes == [ref]: dropped
     std::vector<std::string> haps = graph->candidate_haplotypes();
     if (haps.empty() || (haps.size() == 1 && haps[0] == ref)) return;
     win.haplotypes = std::move(haps);
-  });
+  };
+  if (!device || !dv::device_assembly_enabled()) {
+    parallel_tasks(longest_first(cost), n_threads, [&](int t) {
+      const dv::AssemblyWindow aw = assembly_window(windows[t]);
+      keep_haplotypes(windows[t], dv::DeBruijnGraph::build(aw.ref, aw.reads, dbg).get(), aw.ref);
+    });
+  } else {
+    // 1a: the batch's window list
+    const std::vector<int> by_cost = longest_first(cost);
+    std::vector<dv::AssemblyWindow> assembly(windows.size());
+    parallel_tasks(by_cost, n_threads, [&](int t) { assembly[t] = assembly_window(windows[t]); });
+    // 1b: the graphs of all windows of all regions in one device call
+    std::vector<dv::CompactGraph> graphs;
+    if (int rc = dv::compact_on_device(assembly, dbg, device->stream, &graphs, &dv::last_assembly_stats())) return rc;
+    // 1c: pruning and the haplotypes from the compact graphs
+    std::atomic<int64_t> rejected{0};
+    parallel_tasks(by_cost, n_threads, [&](int t) {
+      const dv::AssemblyWindow& aw = assembly[t];
+      std::unique_ptr<dv::DeBruijnGraph> graph;
+      std::string why;
+      if (!dv::DeBruijnGraph::from_compact(aw.ref, aw.reads, dbg, graphs[t], &graph, &why)) {
+        rejected.fetch_add(1, std::memory_order_relaxed);      // never expected: the host's own graph instead
+        graph = dv::DeBruijnGraph::build(aw.ref, aw.reads, dbg);
+      }
+      keep_haplotypes(windows[t], graph.get(), aw.ref);
+    });
+    dv::last_assembly_stats().windows_rejected += rejected.load();
+  }
 
   // ---- reads -> assembled windows (per region; windows of a region are consecutive in `windows`)
   auto res = std::make_unique<dv_realign_result>();

@@ -47,6 +47,8 @@ _NATIVE_THREADS = max(0, int(os.environ.get('DV_REALIGN_THREADS', '0')))
 # library at each call) moves the CIGARs' banded trace-back into the same kernel launch; off by default too.
 # DV_REALIGN_DEVICE_FASTPASS=1 (read by the library at each call as well) moves the fast pass of every window there,
 # one more launch per call and no k-mer index on the host; off by default, same results.
+# DV_REALIGN_DEVICE_ASSEMBLY=1 (read by the library at each call too) builds every window's de Bruijn graph there, one
+# launch per call; the host threads prune and enumerate from the compact graphs; off by default, same results.
 _DEVICE_ALIGN = os.environ.get('DV_REALIGN_DEVICE', '0') == '1'
 _pool: Optional[concurrent.futures.ThreadPoolExecutor] = None
 
@@ -316,6 +318,8 @@ class RealignJob:
     self.traceback_stats = None    # _lib.DvRealignTracebackStats of the call, device route only
     self.fast_pass_stats = None    # _lib.DvFastPassStats of the call, device route only (all zero unless
                                    # DV_REALIGN_DEVICE_FASTPASS=1 moved the fast pass to the device)
+    self.assembly_stats = None     # _lib.DvDebruijnDeviceStats of the call, device route only (all zero unless
+                                   # DV_REALIGN_DEVICE_ASSEMBLY=1 moved phase 1's graphs to the device)
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -365,6 +369,9 @@ class RealignJob:
       fast_pass = _lib.DvFastPassStats()
       _lib.check(_lib.lib().dv_fast_pass_device_last_stats(C.byref(fast_pass)))
       self.fast_pass_stats = fast_pass
+      assembly = _lib.DvDebruijnDeviceStats()
+      _lib.check(_lib.lib().dv_debruijn_device_last_stats(C.byref(assembly)))
+      self.assembly_stats = assembly
     else:
       _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
                                                C.byref(out)))

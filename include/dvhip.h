@@ -644,7 +644,7 @@ typedef struct dv_fast_pass_stats {
  * pass (all zero when the latter ran it on the host: DV_REALIGN_DEVICE_FASTPASS unset). */
 int dv_fast_pass_device_last_stats(dv_fast_pass_stats* out);
 
-/* ---- local assembly for the window realigner (host only) -----------------------
+/* ---- local assembly for the window realigner ------------------------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
  * CandidateHaplotypes, GraphViz; python binding deepvariant/realigner/python/
  * debruijn_graph_pybind.cc).  Options are DeBruijnGraphOptions (deepvariant/protos/
@@ -669,6 +669,79 @@ int dv_debruijn_kmer_size(const dv_debruijn_graph* g);                          
 /* candidate_haplotypes(): sorted; strings owned by the graph until its next call. */
 int dv_debruijn_haplotypes(dv_debruijn_graph* g, int32_t* n, const char* const** haplotypes);
 int dv_debruijn_graphviz(dv_debruijn_graph* g, const char** text);                     /* graphviz */
+
+/* The graph of the winning k BEFORE pruning, as integers ("compact form"), for many windows in one call.  An
+ * occurrence is (seq, pos): seq 0 is the window's reference, seq 1 + j the j-th read of its list (a read below
+ * min_mapq keeps its number and never occurs), pos the offset of the k-mer's first byte.  Vertices and edges are
+ * in insertion order, which is ascending first occurrence (the constructor walks the reference, then the reads in
+ * order, each left to right), so the form is canonical; an edge's occurrence is that of its `from` k-mer in the
+ * walk that created the edge.  Sequence s is bases / quals [seq_off[s], seq_off[s + 1]); mapq has one entry per
+ * sequence (a reference's is not read).  k[w] = 0: dv_debruijn_build returns NULL for the window.  k_tries[w] is
+ * the number of k values of the schedule visited, the reference-repeat test's included. */
+typedef struct dv_debruijn_window {
+  int32_t reference;               /* the sequence holding the window's reference */
+  int32_t first_read, n_reads;     /* its reads: sequences [first_read, first_read + n_reads) */
+  int32_t reserved;
+} dv_debruijn_window;
+typedef struct dv_debruijn_compact {   /* views into the result; valid until dv_debruijn_compact_free */
+  const int32_t* k;                /* [n_windows] */
+  const int32_t* k_tries;          /* [n_windows] */
+  const int64_t* vertex_off;       /* [n_windows + 1] into the vertex arrays */
+  const int32_t* vertex_seq;
+  const int32_t* vertex_pos;
+  const int64_t* edge_off;         /* [n_windows + 1] into the edge arrays */
+  const int32_t* edge_from;        /* vertex numbers within the window */
+  const int32_t* edge_to;
+  const int32_t* edge_weight;
+  const int32_t* edge_is_ref;
+  const int32_t* edge_seq;
+  const int32_t* edge_pos;
+} dv_debruijn_compact;
+typedef struct dv_debruijn_compact_result dv_debruijn_compact_result;
+/* Host code (DeBruijnGraph's own constructor and cycle test). */
+int dv_debruijn_compact_batch(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                              const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                              const dv_debruijn_options* options, dv_debruijn_compact_result** out,
+                              dv_debruijn_compact* arrays);
+void dv_debruijn_compact_free(dv_debruijn_compact_result* r);
+/* The same on the device (csrc/debruijn.hip has the contract without the maps): one upload, ONE kernel launch with
+ * a workgroup per window -- the choice of k and the cycle test included --, one download and one synchronisation on
+ * `stream` (NULL = a non-blocking stream the library owns); identical arrays.  A window whose reference plus reads
+ * pass DV_DEBRUIJN_DEVICE_MAX_BASES, or whose graph at some k passes DV_DEBRUIJN_DEVICE_MAX_VERTICES /
+ * DV_DEBRUIJN_DEVICE_MAX_EDGES (found at run time), is not an error: the host code builds it inside the same call.
+ * No device is DV_ERR_NO_DEVICE (there is no CPU fallback). */
+#define DV_DEBRUIJN_DEVICE_MAX_VERTICES 8192
+#define DV_DEBRUIJN_DEVICE_MAX_EDGES 8192
+#define DV_DEBRUIJN_DEVICE_MAX_BASES 131072
+int dv_debruijn_compact_batch_device(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                                     const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                                     const dv_debruijn_options* options, void* stream,
+                                     dv_debruijn_compact_result** out, dv_debruijn_compact* arrays);
+typedef struct dv_debruijn_device_stats {
+  int64_t windows;           /* windows asked for */
+  int64_t windows_on_host;   /* of them over a limit, or overflowing at run time: built by the host code */
+  int64_t kmers;             /* k-mer occurrences hashed on the device, summed over the k values tried */
+  int64_t k_tries;           /* k values visited, summed over windows */
+  int64_t launches;          /* kernel launches */
+  int64_t windows_rejected;  /* dv_realign_regions_device only: device graphs dv_debruijn_from_compact's checks
+                                refused (rebuilt on the host); must stay 0 */
+} dv_debruijn_device_stats;
+/* What the calling thread's last dv_debruijn_compact_batch_device or dv_realign_regions_device did with the
+ * assembly (all zero when the latter ran it on the host: DV_REALIGN_DEVICE_ASSEMBLY unset). */
+int dv_debruijn_device_last_stats(dv_debruijn_device_stats* out);
+/* The graph dv_debruijn_build returns, rebuilt from one window's compact form (n_vertices / n_edges entries of the
+ * arrays above) and pruned as dv_debruijn_build prunes; the reads as for dv_debruijn_build.  *out = NULL for k = 0.
+ * The compact form is validated before anything is indexed by it -- occurrences inside their sequences, edge
+ * endpoints in range, the reference's vertices 0 .. |ref| - k in order, both lists sorted by occurrence -- and a
+ * malformed one is DV_ERR_BAD_INPUT. */
+int dv_debruijn_from_compact(const char* ref, int64_t ref_len, const uint8_t* bases, const uint8_t* quals,
+                             int64_t n_bases, const uint32_t* read_seq_off, const uint8_t* read_mapq,
+                             int32_t n_table_reads, const int32_t* reads, int32_t n_reads,
+                             const dv_debruijn_options* options, int32_t k, int32_t n_vertices,
+                             const int32_t* vertex_seq, const int32_t* vertex_pos, int32_t n_edges,
+                             const int32_t* edge_from, const int32_t* edge_to, const int32_t* edge_weight,
+                             const int32_t* edge_is_ref, const int32_t* edge_seq, const int32_t* edge_pos,
+                             dv_debruijn_graph** out);
 
 /* ---- the window realigner over many regions in one call (host only, threaded) -----
  * Replaces the body of Realigner.realign_reads (deepvariant/realigner/realigner.py:795-855) for a
@@ -736,7 +809,11 @@ void dv_realign_result_free(dv_realign_result* r);
  * DV_REALIGN_DEVICE_FASTPASS=1 in the environment, read at each call, also moves the fast pass of every
  * window there (dv_fast_pass_batch_device's kernel: one more launch per call, no k-mer index on the host);
  * unset or 0 it runs on the host threads.  Results are identical either way; `stats` keeps counting the
- * sweep kernel only, dv_fast_pass_device_last_stats reports the fast pass. */
+ * sweep kernel only, dv_fast_pass_device_last_stats reports the fast pass.
+ * DV_REALIGN_DEVICE_ASSEMBLY=1, read at each call as well, moves phase 1's graph building there: the windows of all
+ * regions go through one dv_debruijn_compact_batch_device-style launch, and the host threads prune and enumerate
+ * from the compact graphs (dv_debruijn_from_compact's code); unset or 0 each window is built on a host thread.
+ * dv_debruijn_device_last_stats reports it. */
 int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
                               void* stream, dv_realign_result** out, dv_realign_output* arrays,
                               dv_realign_device_stats* stats);

@@ -1,0 +1,173 @@
+"""Windows for the tests of the realigner's compact graphs (tests/test_debruijn_compact_cpu.py, tests/test_hip_debruijn.py):
+the seeded random windows and the option sampler of tests/test_reference_graphs_cpu.py (copied: that file is kept as it
+is), and hand-made windows for the corners of DeBruijnGraph::build's contract (csrc/debruijn.hip restates it).  A case
+is (name, ref, reads, options).  Not a test module."""
+import dataclasses
+
+import numpy as np
+
+from deepvariant_amd import dv_types as T
+from deepvariant_amd.realigner import debruijn_graph
+
+K = 10          # min_k of the hand-made windows
+
+
+def options(**changes):
+  base = debruijn_graph.DeBruijnGraphOptions(min_k=K, max_k=30, step_k=1, min_mapq=14, min_base_quality=15,
+                                             min_edge_weight=2, max_num_paths=256, disable_graph_pruning=False)
+  return dataclasses.replace(base, **changes)
+
+
+def read(seq, quals=None, mapq=60, name='r'):
+  quals = np.full(len(seq), 30, np.uint8) if quals is None else np.asarray(quals, np.uint8)
+  assert len(quals) == len(seq)
+  return T.Read(fragment_name=name, read_number=0, number_reads=1, aligned_sequence=seq, aligned_quality=bytes(quals),
+                alignment=T.LinearAlignment(position=T.Position('chr', 1000, False), mapping_quality=mapq,
+                                            cigar=[T.CigarUnit(1, max(1, len(seq)))]))
+
+
+def random_bases(seed, n):
+  rng = np.random.default_rng(seed)
+  return ''.join('ACGT'[int(i)] for i in rng.integers(0, 4, size=n))
+
+
+def _low(n, *positions):
+  q = np.full(n, 30, np.uint8)
+  for p in positions:
+    q[p] = 5
+  return q
+
+
+def _snp(seq, p):
+  return seq[:p] + 'ACGT'[('ACGT'.index(seq[p]) + 1) % 4] + seq[p + 1:]
+
+
+def hand_made():
+  """[(name, ref, reads, options)]"""
+  ref = random_bases(11, 90)
+  alt = _snp(ref, 45)
+  cases = []
+  span = alt[20:70]                                   # 50 bases over the SNP
+  for p in (0, 1, K - 1, K, K + 1):
+    cases.append(('bad base at %d' % p, ref, [read(span, _low(50, p)), read(span, _low(50, p)), read(span)], options()))
+  cases.append(('two adjacent bad bases', ref, [read(span, _low(50, 24, 25)), read(span, _low(50, 24, 25)), read(span)],
+                options()))
+  # bad at 19 and 28: the segment from 20 is shorter than k, and its first k-mer -- over the SNP at 25 and over the bad
+  # base at 28 -- stays behind as a vertex without edges
+  cases.append(('short segment after a bad base', ref, [read(span, _low(50, 19, 28)), read(span, _low(50, 19, 28))],
+                options()))
+  cases.append(('low quality base', ref, [read(span, _low(50, 30)), read(span, _low(50, 30))], options()))
+  cases.append(('N at the same place', ref, [read(span[:30] + 'N' + span[31:])] * 2, options()))
+  cases.append(('lower-case read', ref, [read(span.lower()), read(span), read(span[:25].lower() + span[25:])], options()))
+  cases.append(('read below min_mapq', ref, [read(span), read(_snp(span, 10), mapq=13), read(span, mapq=14),
+                                             read(_snp(span, 40), mapq=0)], options()))
+  cases.append(('reads of length k - 1, k, k + 1', ref,
+                [read(alt[40:40 + n]) for n in (K - 1, K, K + 1)] * 2, options()))
+  short = random_bases(12, K + 1)
+  cases.append(('reference of length min_k', short[:K], [read(short), read(short)], options()))
+  cases.append(('reference of length min_k + 1', short, [read(short), read(short[:K] + 'A'), read(short)], options()))
+  tandem = ref[:30] + 'ACG' * 6 + ref[30:]
+  cases.append(('tandem repeat in the reference', tandem, [read(tandem[15:75]), read(_snp(tandem, 60)[20:80])] * 2,
+                options()))
+  cases.append(('homopolymer reference', 'A' * 40, [read('A' * 30), read('A' * 12 + 'C' + 'A' * 12)], options()))
+  unit = random_bases(13, 12)
+  looped = ref[10:30] + unit + unit + ref[30:50]
+  cases.append(('read-only cycle', ref, [read(looped), read(looped), read(ref[5:60])], options()))
+  cases.append(('step_k = 2', tandem, [read(tandem[15:75]), read(_snp(tandem, 60)[20:80])] * 2, options(step_k=2)))
+  cases.append(('no reads', ref, [], options()))
+  long_ref = random_bases(14, 330)
+  long_alt = _snp(_snp(long_ref, 100), 200)
+  strides = []
+  for i, n in enumerate((63, 64, 65, 255, 256, 257)):
+    s = long_alt[5 * i:5 * i + n]
+    strides += [read(s), read(s, _low(n, n // 2)), read(s.lower())]
+  cases.append(('reads across wave and workgroup strides', long_ref, strides, options()))
+  sites = (25, 45, 65)
+  bubbles = []
+  for p in sites:                                     # three independent SNP bubbles: 8 paths
+    bubbles += [read(_snp(ref, p)[p - 14:p + 15])] * 2 + [read(ref[p - 14:p + 15])] * 2
+  cases.append(('max_num_paths exceeded', ref, bubbles, options(max_num_paths=4)))
+  noisy = [read(span), read(_snp(span, 5)), read(_snp(span, 33)), read(span, _low(50, 20))]
+  cases.append(('disable_graph_pruning', ref, noisy, options(disable_graph_pruning=True)))
+  return cases
+
+
+def assembly_window(rng):
+  """tests/test_reference_graphs_cpu.py::_assembly_window."""
+  n = int(rng.integers(120, 320))
+  ref = ''.join('ACGT'[int(i)] for i in rng.integers(0, 4, size=n))
+  if rng.random() < 0.4:      # a tandem repeat: forces larger k
+    p = int(rng.integers(30, n - 60))
+    unit = ''.join('ACGT'[int(i)] for i in rng.integers(0, 4, size=int(rng.integers(1, 5))))
+    ref = ref[:p] + unit * int(rng.integers(5, 14)) + ref[p:]
+  haps = [ref]
+  for _ in range(int(rng.integers(0, 3))):
+    s = list(ref)
+    for _e in range(int(rng.integers(1, 3))):
+      p = int(rng.integers(25, len(s) - 25))
+      u = rng.random()
+      if u < 0.4:
+        s[p] = 'ACGT'[('ACGT'.index(s[p]) + 1 + int(rng.integers(0, 3))) % 4]
+      elif u < 0.7:
+        s[p:p] = ['ACGT'[int(i)] for i in rng.integers(0, 4, size=int(rng.integers(1, 10)))]
+      else:
+        del s[p:p + int(rng.integers(1, 10))]
+    haps.append(''.join(s))
+  reads = []
+  for i in range(int(rng.integers(40, 140))):
+    hap = haps[int(rng.integers(0, len(haps)))]
+    L = int(rng.integers(60, min(150, len(hap))))
+    s0 = int(rng.integers(0, len(hap) - L + 1))
+    seq = list(hap[s0:s0 + L])
+    quals = rng.integers(16, 45, size=L).astype(np.uint8)
+    if rng.random() < 0.08:
+      quals[int(rng.integers(0, L))] = 5      # a low-quality base cuts the read's k-mers there
+    if rng.random() < 0.15:
+      seq[int(rng.integers(0, L))] = 'ACGTN'[int(rng.integers(0, 5))]
+    if rng.random() < 0.1:
+      seq = [c.lower() for c in seq]
+    reads.append(T.Read(fragment_name='w%d' % i, read_number=0, number_reads=1, aligned_sequence=''.join(seq),
+                        aligned_quality=bytes(quals),
+                        alignment=T.LinearAlignment(position=T.Position('chr', 1000 + s0, False),
+                                                    mapping_quality=int(rng.integers(8, 61)),
+                                                    cigar=[T.CigarUnit(1, L)])))
+  return ref, reads
+
+
+def sample_options(rng):
+  """The option sampler of test_local_assembly_equals_the_reference, in its order of draws."""
+  return debruijn_graph.DeBruijnGraphOptions(
+      min_k=int(rng.choice([10, 12, 15])), max_k=int(rng.choice([31, 51, 101])), step_k=int(rng.choice([1, 2])),
+      min_mapq=14, min_base_quality=15, min_edge_weight=int(rng.choice([1, 2, 3])),
+      max_num_paths=int(rng.choice([4, 256])), disable_graph_pruning=bool(rng.random() < 0.15))
+
+
+def generated(seed, n=40):
+  """[(name, ref, reads, options)]: the windows test_local_assembly_equals_the_reference draws for `seed`."""
+  rng = np.random.default_rng(seed)
+  cases = []
+  for i in range(n):
+    ref, reads = assembly_window(rng)
+    cases.append(('seed %d window %d' % (seed, i), ref, reads, sample_options(rng)))
+  return cases
+
+
+SEEDS = (1, 2, 3, 4)
+
+
+def graph_key(o):
+  """The options that decide the graph before pruning: windows with the same key can share a batch."""
+  return (o.min_k, o.max_k, o.step_k, o.min_mapq, o.min_base_quality)
+
+
+def batches(cases):
+  """cases grouped by graph_key, in first-seen order: [(options, [case])]."""
+  groups = {}
+  for case in cases:
+    groups.setdefault(graph_key(case[3]), (case[3], []))[1].append(case)
+  return list(groups.values())
+
+
+def same_graph(a, b):
+  return a.k == b.k and a.k_tries == b.k_tries and all(
+      np.array_equal(getattr(a, name), getattr(b, name)) for name in debruijn_graph.CompactGraph.ARRAYS)

@@ -10,11 +10,14 @@ host route: `device` with DV_REALIGN_DEVICE_TRACEBACK=0 (every CIGAR's banded tr
 `device_traceback` with =1 (in the kernel); the split of the trace-backs and the widest band are in `stats`.
 Where it has the device fast pass, `device_fast_pass` is one more alternating arm: DV_REALIGN_DEVICE_FASTPASS=1 with the
 trace-back on the host, against `device` with both switches 0; its (haplotype, read) pairs and diagonal cells are in
-`stats`.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
+`stats`.  Where it has the device assembly, `device_assembly` (DV_REALIGN_DEVICE_ASSEMBLY=1, the other two switches 0:
+phase 1's graphs in one launch of csrc/debruijn.hip) and `device_all` (all three switches 1) alternate with them too;
+windows, k-mer occurrences hashed and k values tried are in `stats`.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
 measures an older checkout.  Kernel time is not measured here: run this under
 `rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
 `cells` by local_align_sweeps' time per call (fast_pass_kernel: `fast_pass_cells`, with DV_REALIGN_DEVICE_FASTPASS=1
--- the tool sets the switches per arm itself, so profile with `--arms device_fast_pass`).
+-- the tool sets the switches per arm itself, so profile with `--arms device_fast_pass`; debruijn_kernel:
+`assembly_kmers`, with `--arms device_assembly`).
 
   python tools/realign_bench.py [--regions 100] [--repeats 7] [--threads 16,4] [--arms a,b] [--out result.json]
 """
@@ -90,7 +93,9 @@ def main(argv=None):
   has_device = hasattr(_lib, 'DvRealignDeviceStats')
   has_traceback = hasattr(_lib, 'DvRealignTracebackStats')
   has_fast_pass = hasattr(_lib, 'DvFastPassStats')
+  has_assembly = hasattr(_lib, 'DvDebruijnDeviceStats')
   switch, fast_pass_switch = 'DV_REALIGN_DEVICE_TRACEBACK', 'DV_REALIGN_DEVICE_FASTPASS'
+  assembly_switch = 'DV_REALIGN_DEVICE_ASSEMBLY'
   if has_device:
     routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
               'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
@@ -98,14 +103,19 @@ def main(argv=None):
       routes['device_traceback'] = routes['device']
     if has_fast_pass:
       routes['device_fast_pass'] = routes['device']
+    if has_assembly:
+      routes['device_assembly'] = routes['device']
+      routes['device_all'] = routes['device']
   else:
     routes = {'host': R.Realigner(R.realigner_config(), ref)}
 
   def run(route):
     if has_traceback:
-      os.environ[switch] = '1' if route == 'device_traceback' else '0'      # read by the library at each call
+      os.environ[switch] = '1' if route in ('device_traceback', 'device_all') else '0'   # read by the library at each call
     if has_fast_pass:
-      os.environ[fast_pass_switch] = '1' if route == 'device_fast_pass' else '0'
+      os.environ[fast_pass_switch] = '1' if route in ('device_fast_pass', 'device_all') else '0'
+    if has_assembly:
+      os.environ[assembly_switch] = '1' if route in ('device_assembly', 'device_all') else '0'
     gc.collect()
     t0 = time.perf_counter()
     job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
@@ -140,6 +150,17 @@ def main(argv=None):
     assert job.device_stats.launches == 1 and fp.launches == 1 and fp.haplotypes > 0
     result['stats'].update({'fast_pass_haplotypes': fp.haplotypes, 'fast_pass_haplotypes_on_host': fp.haplotypes_on_host,
                             'fast_pass_pairs': fp.pairs, 'fast_pass_cells': fp.cells, 'fast_pass_launches': fp.launches})
+  if has_assembly:
+    for route in ('device_assembly', 'device_all'):
+      _, _, got, job = run(route)
+      assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device assembly differs'
+      asm = job.assembly_stats
+      assert job.device_stats.launches == 1 and asm.launches == 1 and asm.windows > 0
+      assert asm.windows_on_host == 0 and asm.windows_rejected == 0
+      assert (job.fast_pass_stats.launches == 1) == (route == 'device_all')
+    result['stats'].update({'assembly_windows': asm.windows, 'assembly_windows_on_host': asm.windows_on_host,
+                            'assembly_kmers': asm.kmers, 'assembly_k_tries': asm.k_tries,
+                            'assembly_launches': asm.launches, 'assembly_windows_rejected': asm.windows_rejected})
   for threads in [int(t) for t in args.threads.split(',')]:
     R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
     runs = {route: [] for route in routes if not args.arms or route in args.arms.split(',')}
@@ -165,6 +186,11 @@ def main(argv=None):
                                                     entry['device']['native_call_ms'], 4)
       entry['fast_pass_median_below_device_min'] = (entry['device_fast_pass']['native_call_ms'] <
                                                     min(entry['device']['native_call_runs_ms']))
+    for arm in ('device_assembly', 'device_all'):
+      if arm in entry and 'device' in entry:
+        entry[arm + '_over_device_native'] = round(entry[arm]['native_call_ms'] / entry['device']['native_call_ms'], 4)
+        entry[arm + '_median_below_device_min'] = (entry[arm]['native_call_ms'] <
+                                                   min(entry['device']['native_call_runs_ms']))
     result['threads'][str(threads)] = entry
   line = json.dumps(result)
   print(line)
