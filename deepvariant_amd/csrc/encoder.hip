@@ -50,6 +50,7 @@ constexpr int kCigCacheHardMax = 64;   // (DV_CIG_CACHE: measured on ont50, 13,6
                                        // the LDS the larger tables take costs more occupancy than the cached words save)
 constexpr int kPixDw = DV_MAX_CHANNELS / 4;  // dwords of one pixel's channel bytes
 constexpr int kInsertLutSize = 1008;
+constexpr size_t kMaxLdsBytes = 64 * 1024;   // dynamic LDS a launch may ask for without raising the kernel's attribute
 
 enum ChannelKind : uint8_t {
   kZero = 0,      // blank / mean_coverage (painted afterwards)
@@ -224,7 +225,13 @@ __device__ __forceinline__ void store_pixel(uint8_t* dst, const uint32_t (&o)[kP
     const uint16_t m = static_cast<uint16_t>(o[1]);
     __builtin_memcpy(dst + 4, &m, 2);
   } else {
-    for (int ch = 0; ch < CO; ++ch) dst[ch] = static_cast<uint8_t>(o[ch >> 2] >> ((ch & 3) * 8));
+    // o[] holds DV_MAX_CHANNELS bytes; out_channels may pad the pixel up to 64: the channels past o[] are zero.
+    // (One loop with a select: a second loop for the tail costs 6 VGPRs, and with them the kernel's fifth wave per SIMD.)
+    for (int ch = 0; ch < CO; ++ch) {
+      const int d = ch >> 2;
+      const uint32_t w = d < kPixDw ? o[d & (kPixDw - 1)] : 0u;
+      dst[ch] = static_cast<uint8_t>(w >> ((ch & 3) * 8));
+    }
   }
 }
 
@@ -1207,6 +1214,57 @@ int dv_encode_batch(dv_encoder* enc, const dv_batch* b, int out_channels,
   if (b->n_items < 0 || b->n_reads < 0) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, "negative counts");
   }
+  // Validate what the reference would LOG(FATAL)/CHECK on (host batches), before anything is sized, staged or launched.
+  if (b->memory == DV_MEM_HOST) {
+    if (int rc = dv_validate_batch(b, enc->opt.reference_band_height)) return rc;
+  }
+  const int W = enc->opt.width;
+  const size_t row_bytes = static_cast<size_t>(W) * out_channels;
+  EncArgs a{};
+  a.n_items = b->n_items;
+  a.out_channels = out_channels;
+  a.n_channels = enc->konst.n_channels;
+  a.row_buf_bytes = static_cast<int>((row_bytes + 16 + 15) & ~size_t(15));
+
+  // CIGAR cache geometry (EncArgs::cig_cache, kept_cap): from the batch itself when it is host memory, from its
+  // ABI v7 hints when it is not; without either the round-4 shape (8 words x kMaxKept reads).  The cache may
+  // take up to 24 KB (64 words x 96 reads: the ONT shape), which still leaves three workgroups per CU.
+  {
+    uint32_t ops = b->max_cigar_ops, height = b->max_item_height;
+    if (b->memory == DV_MEM_HOST) {
+      ops = 0;
+      height = 0;
+      for (int r = 0; r < b->n_reads; ++r) ops = std::max(ops, b->read_cigar_off[r + 1] - b->read_cigar_off[r]);
+      for (int i = 0; i < b->n_items; ++i) height = std::max<uint32_t>(height, b->item_height[i]);
+    }
+    const int band = enc->opt.reference_band_height;
+    a.kept_cap = height > static_cast<uint32_t>(band) ? std::min<int>(kMaxKept, static_cast<int>(height) - band) : kMaxKept;
+    a.kept_cap = (a.kept_cap + 3) & ~3;
+    int cache = kCigCache;
+    while (cache < kCigCacheMax && static_cast<uint32_t>(cache) < ops) cache *= 2;
+    while (cache > kCigCache && static_cast<size_t>(cache) * a.kept_cap * 4 > 24 * 1024) cache /= 2;
+    a.cig_cache = ops == 0 ? kCigCache : cache;
+    static const int force_cache = getenv("DV_CIG_CACHE") ? atoi(getenv("DV_CIG_CACHE")) : 0;   // tuning knob: 8..64
+    if (force_cache >= kCigCache && force_cache <= kCigCacheHardMax && (force_cache & (force_cache - 1)) == 0) {
+      a.cig_cache = force_cache;
+      if (getenv("DV_CIG_KEPT_MAX") != nullptr) a.kept_cap = kMaxKept;
+    }
+  }
+  // The kernel is launched with the default dynamic LDS limit (it never raises
+  // hipFuncAttributeMaxDynamicSharedMemorySize): a shape that asks for more is refused here, before anything is
+  // staged or launched, instead of surfacing as whatever the failed launch reports.
+  const size_t lds = sizeof(EncConst) + 6 * kMaxKept * 4 + 8 * 4 +
+                     3 * static_cast<size_t>(a.kept_cap) * ((a.n_channels + 3) / 4) * 4 +
+                     static_cast<size_t>(a.kept_cap) * a.cig_cache * 4 +
+                     static_cast<size_t>(kWaves) * a.row_buf_bytes;
+  if (lds > kMaxLdsBytes) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT,
+                    "dv_encode_batch: width " + std::to_string(W) + " with out_channels " + std::to_string(out_channels) +
+                        " needs " + std::to_string(lds) + " bytes of LDS per workgroup (CIGAR cache " +
+                        std::to_string(a.cig_cache) + " words x " + std::to_string(a.kept_cap) + " reads); the limit is " +
+                        std::to_string(kMaxLdsBytes));
+  }
+
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   DV_HIP_CHECK(hipSetDevice(enc->device));
   {
@@ -1214,22 +1272,12 @@ int dv_encode_batch(dv_encoder* enc, const dv_batch* b, int out_channels,
     if (int rc = deep_list_lengths(enc, b, stream, &deep)) return rc;
     if (int rc = ensure_perm_table(enc, static_cast<int>(b->max_list_len), deep)) return rc;
   }
-
-  const int W = enc->opt.width;
-  const size_t row_bytes = static_cast<size_t>(W) * out_channels;
-  EncArgs a{};
   a.konst = static_cast<const EncConst*>(enc->d_konst.ptr);
   a.perm_off = static_cast<const uint32_t*>(enc->d_perm_off.ptr);
   a.perm = static_cast<const uint16_t*>(enc->d_perm.ptr);
-  a.n_items = b->n_items;
-  a.out_channels = out_channels;
-  a.n_channels = enc->konst.n_channels;
-  a.row_buf_bytes = static_cast<int>((row_bytes + 16 + 15) & ~size_t(15));
 
   size_t out_bytes = 0, covered_bytes = 0;
   if (b->memory == DV_MEM_HOST) {
-    // Validate what the reference would LOG(FATAL)/CHECK on, then stage.
-    if (int rc = dv_validate_batch(b, enc->opt.reference_band_height)) return rc;
     for (int i = 0; i < b->n_items; ++i) {
       out_bytes = std::max<size_t>(out_bytes, b->item_out_off[i] + b->item_height[i] * row_bytes);
       covered_bytes += b->item_height[i] * row_bytes;
@@ -1312,34 +1360,6 @@ int dv_encode_batch(dv_encoder* enc, const dv_batch* b, int out_channels,
   a.out = d_out;
   a.out_rows = d_rows;
 
-  // CIGAR cache geometry (EncArgs::cig_cache, kept_cap): from the batch itself when it is host memory, from its
-  // ABI v7 hints when it is not; without either the round-4 shape (8 words x kMaxKept reads).  The cache may
-  // take up to 24 KB (64 words x 96 reads: the ONT shape), which still leaves three workgroups per CU.
-  {
-    uint32_t ops = b->max_cigar_ops, height = b->max_item_height;
-    if (b->memory == DV_MEM_HOST) {
-      ops = 0;
-      height = 0;
-      for (int r = 0; r < b->n_reads; ++r) ops = std::max(ops, b->read_cigar_off[r + 1] - b->read_cigar_off[r]);
-      for (int i = 0; i < b->n_items; ++i) height = std::max<uint32_t>(height, b->item_height[i]);
-    }
-    const int band = enc->opt.reference_band_height;
-    a.kept_cap = height > static_cast<uint32_t>(band) ? std::min<int>(kMaxKept, static_cast<int>(height) - band) : kMaxKept;
-    a.kept_cap = (a.kept_cap + 3) & ~3;
-    int cache = kCigCache;
-    while (cache < kCigCacheMax && static_cast<uint32_t>(cache) < ops) cache *= 2;
-    while (cache > kCigCache && static_cast<size_t>(cache) * a.kept_cap * 4 > 24 * 1024) cache /= 2;
-    a.cig_cache = ops == 0 ? kCigCache : cache;
-    static const int force_cache = getenv("DV_CIG_CACHE") ? atoi(getenv("DV_CIG_CACHE")) : 0;   // tuning knob: 8..64
-    if (force_cache >= kCigCache && force_cache <= kCigCacheHardMax && (force_cache & (force_cache - 1)) == 0) {
-      a.cig_cache = force_cache;
-      if (getenv("DV_CIG_KEPT_MAX") != nullptr) a.kept_cap = kMaxKept;
-    }
-  }
-  const size_t lds = sizeof(EncConst) + 6 * kMaxKept * 4 + 8 * 4 +
-                     3 * static_cast<size_t>(a.kept_cap) * ((a.n_channels + 3) / 4) * 4 +
-                     static_cast<size_t>(a.kept_cap) * a.cig_cache * 4 +
-                     static_cast<size_t>(kWaves) * a.row_buf_bytes;
   {
     dv::ProfileScope prof(dv::kProfEncoder, stream);
     hipLaunchKernelGGL(encode_items_kernel, dim3(b->n_items), dim3(kBlock), lds,

@@ -105,10 +105,12 @@ class PileupImageEncoderNative:
     return packing.allele_frequency_pixels(self._options, dv_call, alt_alleles,
                                            table, idx)
 
-  def _one_item(self, dv_call, ref_bases: str, reads: Sequence,
-                image_start_pos: int, alt_alleles: Sequence[str], height: int,
-                mean_coverage: float = 0.0, alignment_positions=None,
-                channels_to_blank=None, non_uniform_threshold=None):
+  def pack_one_item(self, dv_call, ref_bases: str, reads: Sequence,
+                    image_start_pos: int, alt_alleles: Sequence[str], height: int,
+                    mean_coverage: float = 0.0, alignment_positions=None,
+                    channels_to_blank=None, non_uniform_threshold=None) -> packing.PackedBatch:
+    """The one-item batch a pileup is encoded from: the read table with what this channel list needs, one reference
+    window, one item at out_off 0."""
     width = len(ref_bases)
     table = packing.ReadTable.from_reads(
         reads, alignment_positions=alignment_positions,
@@ -132,6 +134,12 @@ class PileupImageEncoderNative:
                                           channels_to_blank),
         mean_coverage=mean_coverage, groups=groups,
         list_aux=self._list_aux(dv_call, alt_alleles, table, idx))
+    return batch
+
+  def _one_item(self, dv_call, ref_bases: str, reads: Sequence,
+                image_start_pos: int, alt_alleles: Sequence[str], height: int, **kwargs):
+    width = len(ref_bases)
+    batch = self.pack_one_item(dv_call, ref_bases, reads, image_start_pos, alt_alleles, height, **kwargs)
     c = self.num_channels
     out, rows = self._encoder(width).encode(batch, c)
     return out.reshape(height, width, c), int(rows[0])

@@ -281,8 +281,11 @@ void dv_encoder_destroy(dv_encoder* enc);
  *  deepvariant/pileup_image_native.h:214-275), one workgroup per item.
  *   out           uint8, item i row r at out + item_out_off[i] + r*width*out_channels,
  *                 pixels HWC with `out_channels` >= n_channels bytes each
- *                 (extra trailing channels are zero-filled)
- *   out_rows      int32[n_items] read rows kept per item, may be NULL
+ *                 (extra trailing channels are zero-filled; at most 64)
+ *                 A workgroup stages four rows of width*out_channels bytes in LDS next to its read tables: a
+ *                 shape whose request exceeds 64 KiB is DV_ERR_INVALID_ARGUMENT (dv_last_error names the width
+ *                 and out_channels) before anything is copied or launched.
+ *   out_rows     int32[n_items] read rows kept per item, may be NULL
  *   out_memory    dv_memory of out / out_rows */
 int dv_encode_batch(dv_encoder* enc, const dv_batch* batch, int out_channels,
                     uint8_t* out, int32_t* out_rows, int out_memory,
