@@ -54,6 +54,8 @@ ABI_SYMBOLS = [
     'dv_local_align_pairs_device', 'dv_local_align_device_last_stats', 'dv_realign_regions_device',
     'dv_local_align_device_last_traceback_stats', 'dv_local_align_band',
     'dv_fast_pass_batch', 'dv_fast_pass_batch_device', 'dv_fast_pass_device_last_stats',
+    'dv_trim_reads_batch', 'dv_trim_reads_batch_device', 'dv_trimmed_reads_arrays', 'dv_trimmed_reads_free',
+    'dv_trim_device_last_stats',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
     'dv_debruijn_device_last_stats', 'dv_debruijn_from_compact', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
@@ -215,6 +217,22 @@ class DvFastPassWindow(C.Structure):
 class DvFastPassStats(C.Structure):
   _fields_ = [('haplotypes', C.c_int64), ('haplotypes_on_host', C.c_int64), ('pairs', C.c_int64),
               ('cells', C.c_int64), ('launches', C.c_int64)]
+
+
+class DvTrimWindow(C.Structure):
+  _fields_ = [('q0', C.c_int64), ('q1', C.c_int64), ('r0', C.c_int64), ('r1', C.c_int64),
+              ('min_overlap', C.c_int32), ('reserved', C.c_int32)]
+
+
+class DvTrimmedReadsView(C.Structure):
+  _fields_ = [('n_windows', C.c_int32), ('n_rows', C.c_int32), ('n_words', C.c_int64),
+              ('window_row_off', C.c_void_p), ('src_row', C.c_void_p), ('pos', C.c_void_p), ('end', C.c_void_p),
+              ('read_trim', C.c_void_p), ('new_len', C.c_void_p), ('cigar_off', C.c_void_p), ('cigar', C.c_void_p)]
+
+
+class DvTrimStats(C.Structure):
+  _fields_ = [('pairs_tested', C.c_int64), ('pairs_kept', C.c_int64), ('words_read', C.c_int64),
+              ('words_written', C.c_int64), ('launches', C.c_int64)]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -457,6 +475,12 @@ def lib():
     for fn in (l.dv_fast_pass_batch, l.dv_fast_pass_batch_device):
       fn.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
     l.dv_fast_pass_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_trim_reads_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    l.dv_trim_reads_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.dv_trimmed_reads_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_trimmed_reads_free.argtypes = [C.c_void_p]
+    l.dv_trimmed_reads_free.restype = None
+    l.dv_trim_device_last_stats.argtypes = [C.c_void_p]
     l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

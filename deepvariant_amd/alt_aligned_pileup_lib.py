@@ -223,3 +223,92 @@ def fill_pileup_array_by_sample(images: Sequence[np.ndarray],
         get_sample_alt_aligned_pileup(mode, so.alt_aligned_pileup), alt_combination)
     parts.append(fill_pileup_array(images[s], alt_images[s], mode, rows))
   return np.concatenate(parts, axis=0)
+
+
+# ------------------------------------------------------------------ trimming on a packed table
+def trim_arrays(table, windows: Sequence, device: bool = True, stream: int = 0) -> dict:
+  """TrimReads for many windows over one packed read table, in libdvhip (include/dvhip.h
+  dv_trim_reads_batch_device: one wave per (window, read) pair; device=False: the host code).
+  `windows`: (q0, q1, r0, r1, min_overlap) each -- the read query, the pileup window, the least
+  reference overlap.  -> the arrays of dv_trimmed_reads_view, copied, and `stats` (device only).
+  What trim_read refuses with ValueError is a ValueError here too, naming window and row."""
+  import ctypes as C
+  from deepvariant_amd import _lib
+  lib = _lib.lib()
+  n = int(table.n_reads)
+  keep = [np.ascontiguousarray(table.read_pos, np.int32), np.ascontiguousarray(table.read_seq_off, np.uint32),
+          np.ascontiguousarray(table.read_cigar_off, np.uint32), np.ascontiguousarray(table.cigar, np.uint32),
+          np.ascontiguousarray(table.read_end, np.int64)]
+  b = _lib.DvBatch()
+  b.memory, b.n_reads = _lib.DV_MEM_HOST, n
+  b.read_pos, b.read_seq_off, b.read_cigar_off, b.cigar = (a.ctypes.data for a in keep[:4])
+  b.n_bases, b.n_cigar = int(keep[1][-1]), int(keep[2][-1])
+  wins = (_lib.DvTrimWindow * max(len(windows), 1))()
+  for k, (q0, q1, r0, r1, min_overlap) in enumerate(windows):
+    wins[k] = _lib.DvTrimWindow(int(q0), int(q1), int(r0), int(r1), int(min_overlap), 0)
+  handle = C.c_void_p()
+  if device:
+    rc = lib.dv_trim_reads_batch_device(C.byref(b), keep[4].ctypes.data, len(windows), wins, C.byref(handle),
+                                        C.c_void_p(stream or None))
+  else:
+    rc = lib.dv_trim_reads_batch(C.byref(b), keep[4].ctypes.data, len(windows), wins, C.byref(handle))
+  if rc == _lib.DV_ERR_BAD_INPUT:
+    raise ValueError(_lib.last_error())
+  _lib.check(rc)
+  try:
+    view = _lib.DvTrimmedReadsView()
+    _lib.check(lib.dv_trimmed_reads_arrays(handle, C.byref(view)))
+
+    def arr(ptr, dtype, count):
+      if not count:
+        return np.zeros(0, dtype)
+      buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+      return np.frombuffer(buf, dtype=dtype, count=count).copy()
+
+    rows = view.n_rows
+    out = dict(window_row_off=arr(view.window_row_off, np.int32, view.n_windows + 1),
+               cigar_off=arr(view.cigar_off, np.uint32, rows + 1), cigar=arr(view.cigar, np.uint32, view.n_words))
+    for name in ('src_row', 'pos', 'end', 'read_trim', 'new_len'):
+      out[name] = arr(getattr(view, name), np.int32, rows)
+  finally:
+    lib.dv_trimmed_reads_free(handle)
+  if device:
+    st = _lib.DvTrimStats()
+    _lib.check(lib.dv_trim_device_last_stats(C.byref(st)))
+    out['stats'] = {name: int(getattr(st, name)) for name, _ in st._fields_}   # pylint: disable=protected-access
+  return out
+
+
+def trim_table(table, windows: Sequence, device: bool = True, stream: int = 0, with_stats: bool = False):
+  """-> (the ReadTable of every window's trimmed reads, [(lo, hi) rows per window][, stats]): field for field
+  what ReadTable.from_reads(trim_reads objects, alignment_positions=untrimmed starts) gives for the same reads
+  window after window, built from trim_arrays' descriptors with array operations only.  A table with per-read
+  aux pixels or per-base aux planes is refused: those channels are computed on the TRIMMED sequence, which only
+  the object path does."""
+  from deepvariant_amd import packing
+  if table.read_aux is not None or any(getattr(table, 'base_aux%d' % k) is not None for k in range(3)):
+    raise ValueError('trim_table: the table carries per-read aux pixels or per-base aux planes; those channels are '
+                     'computed on the trimmed sequence, which only the Read-object path does')
+  d = trim_arrays(table, windows, device=device, stream=stream)
+  src = d['src_row'].astype(np.int64)
+  n = len(src)
+  new_len = d['new_len'].astype(np.int64)
+  seq_off = np.zeros(n + 1, np.int64)
+  np.cumsum(new_len, out=seq_off[1:])
+  starts = table.read_seq_off.astype(np.int64)[src] + d['read_trim']
+  seq_idx = np.arange(int(seq_off[-1]), dtype=np.int64) + np.repeat(starts - seq_off[:-1], new_len)
+  flags = table.read_flags[src]
+  per_base = lambda a, bit: a[seq_idx] if a is not None and (flags & bit).any() else None     # noqa: E731
+  ranks = np.unique(table.read_name_rank[src], return_inverse=True)[1].astype(np.uint32).reshape(n) if n else \
+      np.zeros(0, np.uint32)
+  keys = table.keys
+  trimmed = packing.ReadTable(
+      n_reads=n, read_pos=d['pos'], read_sort_pos=table.read_pos[src].astype(np.int32) if n else None,
+      read_seq_off=seq_off.astype(np.uint32), read_cigar_off=d['cigar_off'], read_mapq=table.read_mapq[src],
+      read_flags=flags, read_frag_len=table.read_frag_len[src], read_hp=table.read_hp[src], read_name_rank=ranks,
+      read_aux=None, bases=table.bases[seq_idx], quals=table.quals[seq_idx],
+      mod_5mc=per_base(table.mod_5mc, packing.DV_READ_HAS_5MC), mod_6ma=per_base(table.mod_6ma, packing.DV_READ_HAS_6MA),
+      cigar=d['cigar'], keys=[keys[i] for i in src.tolist()], read_end=d['end'].astype(np.int64))
+  off = d['window_row_off'].tolist()
+  ranges = list(zip(off[:-1], off[1:]))
+  return (trimmed, ranges, d.get('stats')) if with_stats else (trimmed, ranges)

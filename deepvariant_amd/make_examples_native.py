@@ -216,6 +216,9 @@ class ExamplesGenerator:
     trimmed = [[] for _ in reads_per_sample]
     starts = [[] for _ in reads_per_sample]
     ranges = {}
+    # a sample whose reads are a packed table: its windows are gathered here and trimmed in one call below
+    packed = [isinstance(reads, packing.ReadTable) for reads in reads_per_sample]
+    packed_windows = [[] for _ in reads_per_sample]
     for ci, cand in enumerate(candidates):
       variant = cand.variant
       if wanted is not None and not wanted[ci]:
@@ -228,17 +231,35 @@ class ExamplesGenerator:
                                               self._ref.n_bases(variant.reference_name))
       for s in sample_order:
         so = self._options.sample_options[s]
-        if isinstance(reads_per_sample[s], packing.ReadTable):
-          raise NotImplementedError('trim_reads_for_pileup needs Read objects, not a packed table')
         min_overlap = pic.width if so.keep_only_window_spanning_reads \
             else aap.K_DEFAULT_MINIMUM_READ_OVERLAP
+        if packed[s]:
+          packed_windows[s].append((ci, (q0, q1, r0, r1, min_overlap)))
+          continue
         overlapping = [reads_per_sample[s][int(k)] for k in tables[s].query(q0, q1)]
         kept, original = aap.trim_reads(overlapping, r0, r1, min_overlap)
         lo = len(trimmed[s])
         trimmed[s].extend(kept)
         starts[s].extend(original)
         ranges[(ci, s)] = (lo, lo + len(kept))
-    new_tables = [self._table_of(trimmed[s], starts[s]) for s in range(len(reads_per_sample))]
+    new_tables = []
+    for s, reads in enumerate(reads_per_sample):
+      if not packed[s]:
+        new_tables.append(self._table_of(trimmed[s], starts[s]))
+        continue
+      if self._encoder_api._need_aux or any(self._encoder_api._need_seq_aux):
+        raise NotImplementedError(
+            'trim_reads_for_pileup on a packed table: this channel set needs per-read aux pixels or per-base aux '
+            'planes, which are computed on the trimmed sequence; pass Read objects')
+      # the table route (alt_aligned_pileup_lib.trim_table, csrc/trim_reads.hip): one call per sample over every
+      # wanted candidate; there is no host fallback
+      table, rows = aap.trim_table(reads, [w for _, w in packed_windows[s]], device=True)
+      for (ci, _), span in zip(packed_windows[s], rows):
+        ranges[(ci, s)] = span
+      if table.read_sort_pos is None:
+        table.read_sort_pos = table.read_pos.copy()
+      new_tables.append(table)
+      trimmed[s] = starts[s] = None      # no Read objects: _realign_for_alt_images cannot take this sample
     self._trimmed_reads, self._trimmed_starts = trimmed, starts
     return new_tables, ranges
 
@@ -281,6 +302,9 @@ class ExamplesGenerator:
       for s in sample_order:
         if (ci, s) not in trim_ranges or not self._sample_needs_alt(self._options.sample_options[s]):
           continue
+        if self._trimmed_reads[s] is None:
+          raise NotImplementedError('alt-aligned pileups realign the trimmed reads as Read objects '
+                                    '(RealignReadsToHaplotype), not a packed table')
         lo, hi = trim_ranges[(ci, s)]
         trimmed = self._trimmed_reads[s][lo:hi]
         starts = self._trimmed_starts[s][lo:hi]

@@ -647,6 +647,60 @@ typedef struct dv_fast_pass_stats {
  * pass (all zero when the latter ran it on the host: DV_REALIGN_DEVICE_FASTPASS unset). */
 int dv_fast_pass_device_last_stats(dv_fast_pass_stats* out);
 
+/* ---- window trimming of reads on a packed table -------------------------------------
+ * TrimReads (deepvariant/alt_aligned_pileup_lib.cc:231-248) for many pileup windows over one region's read
+ * table: per window, the rows with q1 > read_pos && q0 < read_end, in row order (InMemoryReader::Query), each
+ * cut to [r0, r1) (TrimRead / TrimCigar, :91-216) and kept when its trimmed CIGAR spans >= min_overlap
+ * reference bases and holds at least one read base.  The closed form is written out in csrc/trim_reads.hip;
+ * the Python restatement is alt_aligned_pileup_lib.trim_cigar / trim_read / trim_reads.
+ * `reads` is a DV_MEM_HOST dv_batch of which read_pos, read_seq_off, read_cigar_off and cigar are read;
+ * read_end (alignment ends, [n_reads]) is not part of dv_batch and comes beside it.  The table may be unsorted.
+ * A pair with r1 <= max(r0, read_pos) (the reference's CHECK_GT) or whose trimmed CIGAR needs more bases than the
+ * read's sequence has is DV_ERR_BAD_INPUT for the whole call; dv_last_error names the smallest such (window, row).
+ * Null pointers, negative counts, a table not in host memory, descending offsets, ends or window bounds outside
+ * int32: DV_ERR_INVALID_ARGUMENT before any device work.  On any error *out is NULL and nothing stays allocated. */
+typedef struct dv_trim_window {
+  int64_t q0, q1;        /* the read query: variant start / end -/+ read_overlap_buffer_bp */
+  int64_t r0, r1;        /* the pileup window (CalculateAlignmentRegion) */
+  int32_t min_overlap;   /* kDefaultMinimumReadOverlap (15), or the image width for window-spanning reads only */
+  int32_t reserved;
+} dv_trim_window;
+typedef struct dv_trimmed_reads dv_trimmed_reads;   /* owns the host arrays of one call's result */
+typedef struct dv_trimmed_reads_view {              /* views into the result; valid until dv_trimmed_reads_free */
+  int32_t n_windows;
+  int32_t n_rows;                  /* kept (window, read) pairs: the same read once per window that keeps it */
+  int64_t n_words;
+  const int32_t* window_row_off;   /* [n_windows + 1]: window w's rows are [off[w], off[w + 1]) */
+  const int32_t* src_row;          /* [n_rows] the row of `reads` */
+  const int32_t* pos;              /* r0 where the window cut the read's start, else read_pos */
+  const int32_t* end;              /* pos + the reference span of the trimmed CIGAR */
+  const int32_t* read_trim;        /* the kept bases are [read_trim, read_trim + new_len) of the read's */
+  const int32_t* new_len;
+  const uint32_t* cigar_off;       /* [n_rows + 1] into cigar */
+  const uint32_t* cigar;           /* [n_words] dv_batch's encoding; a CIGAR the window ends inside an operation
+                                      of closes with that operation at its remaining length, which may be 0 */
+} dv_trimmed_reads_view;
+/* Host code (csrc/trim_reads.hip, TrimCigar operation by operation); for tests and tools. */
+int dv_trim_reads_batch(const dv_batch* reads, const int64_t* read_end, int32_t n_windows,
+                        const dv_trim_window* windows, dv_trimmed_reads** out);
+/* The same on the device: one wave per (window, read) pair; one upload, three launches (count, scan, emit), one
+ * download and one synchronisation on `stream` (NULL = a non-blocking stream the library owns); identical arrays.
+ * CIGAR length is unbounded.  No pair at all is DV_OK without a device; no device is DV_ERR_NO_DEVICE (there is
+ * no CPU fallback). */
+int dv_trim_reads_batch_device(const dv_batch* reads, const int64_t* read_end, int32_t n_windows,
+                               const dv_trim_window* windows, dv_trimmed_reads** out, void* stream);
+int dv_trimmed_reads_arrays(const dv_trimmed_reads* t, dv_trimmed_reads_view* out);
+void dv_trimmed_reads_free(dv_trimmed_reads* t);
+typedef struct dv_trim_stats {
+  int64_t pairs_tested;    /* (window, read) pairs that passed the overlap test: one wave each */
+  int64_t pairs_kept;
+  int64_t words_read;      /* CIGAR operations of the tested pairs (the kernel stops at the window's end) */
+  int64_t words_written;
+  int64_t launches;
+} dv_trim_stats;
+/* What the calling thread's last dv_trim_reads_batch_device did. */
+int dv_trim_device_last_stats(dv_trim_stats* out);
+
 /* ---- local assembly for the window realigner ------------------------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
  * CandidateHaplotypes, GraphViz; python binding deepvariant/realigner/python/
