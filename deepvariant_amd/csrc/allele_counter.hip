@@ -22,8 +22,10 @@
 #include <vector>
 
 #include "candidates.h"
-#include "dv_internal.h"
+#include "device_round_trip.h"
 #include "gvcf.h"
+
+using dv::align16;
 
 // Large results live in pinned host memory (the count array of a 7.7 Mb interval is 31 MB: 1.3 ms
 // over PCIe from pinned memory, 5 ms into pageable); small ones -- a 1 kb calling region's 4 KB of
@@ -464,7 +466,6 @@ int gvcf_from_counts(const dv_allele_counts* c, const dv_allele_counter_options*
                      const int32_t* keys, const dv_gvcf_options* gv, const dv_gvcf_site* d_table, hipStream_t stream,
                      dv_gvcf_blocks** out) {
   static thread_local dv::DeviceBuffer d_img;
-  auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   const int64_t len = c->length;
   const uint32_t n_ev = static_cast<uint32_t>(c->events.size());
   const size_t n_keys = keys ? static_cast<size_t>(b->n_reads) : 0;
@@ -539,7 +540,6 @@ int candidates_from_counts(const dv_allele_counts* c, const dv_allele_counter_op
                            const int32_t* keys, const dv_candidate_options* co, hipStream_t stream,
                            dv_candidates** out) {
   static thread_local dv::DeviceBuffer d_img;
-  auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   auto res = std::make_unique<dv_candidates>();
   const int64_t len = c->length;
   if (len == 0) {
@@ -828,7 +828,6 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     size_t cscr_off = 0;
   };
   std::vector<Plan> plan(static_cast<size_t>(n));
-  auto align16 = [](size_t x) { return (x + 15) & ~static_cast<size_t>(15); };
   size_t up_bytes = 0, cnt_ints = 0, ev_total = 0;
   int n_batched = 0;
   int n_gv = 0;                                  // gVCF: batched regions, their scratch and record totals

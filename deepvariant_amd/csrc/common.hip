@@ -1,12 +1,15 @@
-// common.hip -- error handling, device buffers, profiling hooks and the small
-// host-side helpers of the C ABI (CRC32C, DownsampleReadIndices, Query).
+// common.hip -- error handling, device buffers, the round trip of the realigner's device calls
+// (device_round_trip.h), profiling hooks and the small host-side helpers of the C ABI (CRC32C,
+// DownsampleReadIndices, Query).
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <random>
 
+#include "device_round_trip.h"
 #include "dv_internal.h"
 
 namespace dv {
@@ -48,6 +51,61 @@ void DeviceBuffer::release() {
   if (ptr) (void)hipFree(ptr);
   ptr = nullptr;
   cap = 0;
+}
+
+int RoundTrip::begin(const std::string& no_device_message, void* caller_stream, size_t up_bytes, size_t down_bytes,
+                     size_t scratch_bytes) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(DV_ERR_NO_DEVICE, no_device_message);
+  // the call may come from a thread that has not used the device yet (RealignJob.start on an executor)
+  int device = 0;
+  DV_HIP_CHECK(hipGetDevice(&device));
+  DV_HIP_CHECK(hipSetDevice(device));
+  stream_ = static_cast<hipStream_t>(caller_stream);
+  if (!stream_) {
+    if (own_stream_ && own_stream_device_ != device) {
+      (void)hipStreamDestroy(own_stream_);
+      own_stream_ = nullptr;
+    }
+    if (!own_stream_) {
+      DV_HIP_CHECK(hipStreamCreateWithFlags(&own_stream_, hipStreamNonBlocking));
+      own_stream_device_ = device;
+    }
+    stream_ = own_stream_;
+  }
+  if (int rc = up.reserve(up_bytes)) return rc;
+  if (int rc = down.reserve(down_bytes)) return rc;
+  if (int rc = d_up.reserve_on_current_device(up_bytes)) return rc;
+  if (int rc = d_down.reserve_on_current_device(down_bytes)) return rc;
+  if (scratch_bytes > 0) {
+    if (int rc = d_scratch.reserve_on_current_device(scratch_bytes)) return rc;
+  }
+  return DV_OK;
+}
+
+int RoundTrip::upload(size_t up_bytes) {
+  DV_HIP_CHECK(hipMemcpyAsync(d_up.ptr, up.ptr, up_bytes, hipMemcpyHostToDevice, stream_));
+  return DV_OK;
+}
+
+int RoundTrip::finish(size_t down_bytes) {
+  DV_HIP_CHECK(hipMemcpyAsync(down.ptr, d_down.ptr, down_bytes, hipMemcpyDeviceToHost, stream_));
+  DV_HIP_CHECK(hipStreamSynchronize(stream_));
+  return DV_OK;
+}
+
+int check_sequence_table(const std::string& who, int32_t n_seqs, const int64_t* seq_off) {
+  for (int32_t s = 0; s < n_seqs; ++s) {
+    if (seq_off[s] < 0 || seq_off[s + 1] < seq_off[s]) {
+      return fail(DV_ERR_INVALID_ARGUMENT, who + ": sequence offsets must ascend from >= 0");
+    }
+  }
+  return DV_OK;
+}
+
+bool env_switch(const char* name, bool otherwise) {
+  const char* v = getenv(name);
+  return v && *v ? std::atoi(v) != 0 : otherwise;
 }
 
 // ---- profiling: event pairs around launches, summed per kind -------------

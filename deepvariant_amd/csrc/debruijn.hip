@@ -38,7 +38,8 @@
 // round; the graph is acyclic iff every vertex was removed.  At the winning k the used slots are stored as
 // occurrence keys; the host sorts them by first occurrence and renumbers, so the races that decide slot order never
 // reach the caller.  The tables are sized by the window (at most twice the limits of include/dvhip.h) and live in
-// the window's slice of a device scratch buffer the calling thread reuses: at the measured sizes they do not fit
+// the window's slice of a device scratch buffer the calling thread reuses (RoundTrip::d_scratch; the upload and
+// download images and the thread's stream are device_round_trip.h's too): at the measured sizes they do not fit
 // LDS.  Every loop is bounded: a probe sequence by the table's size (then the window's
 // overflow flag is set and the host builds it), the peel by vertices + 1 rounds, a chain by the vertex count, an
 // edge list by the edge count, the k loop by the schedule; no workgroup waits for another.
@@ -49,7 +50,7 @@
 #include <string>
 
 #include "debruijn_device.h"
-#include "dv_internal.h"
+#include "device_round_trip.h"
 
 static_assert(sizeof(dv_debruijn_device_stats) == 48, "dv_debruijn_device_stats layout");
 static_assert(sizeof(dv_debruijn_window) == 16, "dv_debruijn_window layout");
@@ -83,11 +84,9 @@ struct Params {
   int min_k, max_k, step_k, min_mapq, min_base_quality, max_vertices, max_edges;
 };
 
-size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
-
 // a window's slice: P | ekey | nb | sid | slot_of | vkey | indeg | head | work | ew | eocc | enext
 size_t slice_bytes(size_t n, size_t vcap, size_t ecap) {
-  return align16(8 * (n + 1) + 8 * ecap + 4 * (3 * n + 4 * vcap + 3 * ecap));
+  return dv::align16(8 * (n + 1) + 8 * ecap + 4 * (3 * n + 4 * vcap + 3 * ecap));
 }
 
 __device__ inline uint32_t ld(const uint32_t* p) {
@@ -386,13 +385,6 @@ __global__ __launch_bounds__(kThreads) void debruijn_kernel(const uint8_t* __res
   }
 }
 
-struct ThreadState {
-  dv::PinnedStage up, down;
-  dv::DeviceBuffer d_up, d_down, d_scratch;
-  hipStream_t stream = nullptr;   // the library's own, for callers that pass none
-  int stream_device = -1;
-};
-
 uint32_t pow2_at_least(uint32_t x) {
   uint32_t p = 64;
   while (p < x) p <<= 1;
@@ -458,10 +450,7 @@ AssemblyStats& last_assembly_stats() {
   return stats;
 }
 
-bool device_assembly_enabled() {
-  const char* v = getenv("DV_REALIGN_DEVICE_ASSEMBLY");
-  return v && *v && std::atoi(v) != 0;
-}
+bool device_assembly_enabled() { return env_switch("DV_REALIGN_DEVICE_ASSEMBLY", false); }
 
 void compact_on_host(const std::vector<AssemblyWindow>& windows, const DeBruijnOptions& options,
                      std::vector<CompactGraph>* out) {
@@ -518,56 +507,36 @@ int compact_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijn
     stats->windows_on_host += static_cast<int64_t>(on_host.size());
   }
   if (!items.empty()) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-      return fail(DV_ERR_NO_DEVICE, "de Bruijn assembly: no HIP device (the device route has no CPU fallback)");
-    }
-    // the call may come from a thread that has not used the device yet
-    int device = 0;
-    DV_HIP_CHECK(hipGetDevice(&device));
-    DV_HIP_CHECK(hipSetDevice(device));
-    static thread_local ThreadState ts;
-    hipStream_t stream = static_cast<hipStream_t>(stream_in);
-    if (!stream) {
-      if (ts.stream && ts.stream_device != device) {
-        (void)hipStreamDestroy(ts.stream);
-        ts.stream = nullptr;
-      }
-      if (!ts.stream) {
-        DV_HIP_CHECK(hipStreamCreateWithFlags(&ts.stream, hipStreamNonBlocking));
-        ts.stream_device = device;
-      }
-      stream = ts.stream;
-    }
     // the heaviest windows first: early workgroups start first
     std::vector<size_t> order(items.size());
     for (size_t x = 0; x < order.size(); ++x) order[x] = x;
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return items[a].n_bytes > items[b].n_bytes; });
     const size_t n_items = items.size();
+    Layout up, down;
     // upload image: items | offsets | mapq | bases | quals
-    const size_t o_off = align16(n_items * sizeof(Item));
-    const size_t o_mapq = o_off + align16(static_cast<size_t>(n_entries) * sizeof(int32_t));
-    const size_t o_bases = o_mapq + align16(static_cast<size_t>(n_entries));
-    const size_t o_quals = o_bases + align16(static_cast<size_t>(n_bytes));
-    const size_t up_bytes = o_quals + align16(static_cast<size_t>(n_bytes));
+    const size_t o_items = up.add(n_items * sizeof(Item));
+    const size_t o_off = up.add(static_cast<size_t>(n_entries) * sizeof(int32_t));
+    const size_t o_mapq = up.add(static_cast<size_t>(n_entries));
+    const size_t o_bases = up.add(static_cast<size_t>(n_bytes));
+    const size_t o_quals = up.add(static_cast<size_t>(n_bytes));
     // download image: headers | vertex keys | edges
-    const size_t o_vout = align16(n_items * sizeof(Header));
-    const size_t o_eout = o_vout + align16(static_cast<size_t>(vout) * sizeof(uint32_t));
-    const size_t down_bytes = o_eout + static_cast<size_t>(eout) * sizeof(uint4);
-    if (int rc = ts.up.reserve(up_bytes)) return rc;
-    if (int rc = ts.down.reserve(down_bytes)) return rc;
-    if (int rc = ts.d_up.reserve_on_current_device(up_bytes)) return rc;
-    if (int rc = ts.d_down.reserve_on_current_device(down_bytes)) return rc;
-    if (int rc = ts.d_scratch.reserve_on_current_device(static_cast<size_t>(scratch_bytes))) return rc;
-    Item* up_items = reinterpret_cast<Item*>(ts.up.ptr);
-    int32_t* up_off = reinterpret_cast<int32_t*>(ts.up.ptr + o_off);
-    uint8_t* up_mapq = ts.up.ptr + o_mapq;
+    const size_t o_headers = down.add(n_items * sizeof(Header));
+    const size_t o_vout = down.add(static_cast<size_t>(vout) * sizeof(uint32_t));
+    const size_t o_eout = down.add_last(static_cast<size_t>(eout) * sizeof(uint4));
+    static thread_local RoundTrip rt;     // its scratch: the windows' tables
+    if (int rc = rt.begin("de Bruijn assembly: no HIP device (the device route has no CPU fallback)", stream_in,
+                          up.bytes(), down.bytes(), static_cast<size_t>(scratch_bytes))) {
+      return rc;
+    }
+    Item* up_items = rt.host_up<Item>(o_items);
+    int32_t* up_off = rt.host_up<int32_t>(o_off);
+    uint8_t* up_mapq = rt.host_up<uint8_t>(o_mapq);
     for (size_t x = 0; x < n_items; ++x) {
       const Item& it = items[order[x]];
       up_items[x] = it;
       const AssemblyWindow& w = windows[item_window[order[x]]];
-      uint8_t* b = ts.up.ptr + o_bases + it.bytes_off;
-      uint8_t* q = ts.up.ptr + o_quals + it.bytes_off;
+      uint8_t* b = rt.host_up<uint8_t>(o_bases) + it.bytes_off;
+      uint8_t* q = rt.host_up<uint8_t>(o_quals) + it.bytes_off;
       int32_t* offs = up_off + it.seq_table;
       uint8_t* mq = up_mapq + it.seq_table;
       std::memcpy(b, w.ref.data(), w.ref.size());
@@ -590,26 +559,23 @@ int compact_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijn
       }
       mq[w.reads.size() + 1] = 0;
     }
-    uint8_t* d_up = static_cast<uint8_t*>(ts.d_up.ptr);
-    uint8_t* d_down = static_cast<uint8_t*>(ts.d_down.ptr);
-    DV_HIP_CHECK(hipMemcpyAsync(d_up, ts.up.ptr, up_bytes, hipMemcpyHostToDevice, stream));
+    if (int rc = rt.upload(up.bytes())) return rc;
     {
-      ProfileScope prof(kProfOther, stream);
+      ProfileScope prof(kProfOther, rt.stream());
       const Params prm{options.min_k, options.max_k, options.step_k, options.min_mapq, options.min_base_quality,
                        kDebruijnMaxVertices, kDebruijnMaxEdges};
-      hipLaunchKernelGGL(debruijn_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, stream,
-                         d_up + o_bases, d_up + o_quals, reinterpret_cast<const int32_t*>(d_up + o_off), d_up + o_mapq,
-                         reinterpret_cast<const Item*>(d_up), prm, static_cast<uint8_t*>(ts.d_scratch.ptr),
-                         reinterpret_cast<uint32_t*>(d_down + o_vout), reinterpret_cast<uint4*>(d_down + o_eout),
-                         reinterpret_cast<Header*>(d_down));
+      hipLaunchKernelGGL(debruijn_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, rt.stream(),
+                         rt.dev_up<const uint8_t>(o_bases), rt.dev_up<const uint8_t>(o_quals),
+                         rt.dev_up<const int32_t>(o_off), rt.dev_up<const uint8_t>(o_mapq),
+                         rt.dev_up<const Item>(o_items), prm, static_cast<uint8_t*>(rt.d_scratch.ptr),
+                         rt.dev_down<uint32_t>(o_vout), rt.dev_down<uint4>(o_eout), rt.dev_down<Header>(o_headers));
       DV_HIP_CHECK(hipGetLastError());
     }
-    DV_HIP_CHECK(hipMemcpyAsync(ts.down.ptr, d_down, down_bytes, hipMemcpyDeviceToHost, stream));
-    DV_HIP_CHECK(hipStreamSynchronize(stream));
+    if (int rc = rt.finish(down.bytes())) return rc;
     if (stats) stats->launches += 1;
-    const Header* headers = reinterpret_cast<const Header*>(ts.down.ptr);
-    const uint32_t* vkeys = reinterpret_cast<const uint32_t*>(ts.down.ptr + o_vout);
-    const uint4* edges = reinterpret_cast<const uint4*>(ts.down.ptr + o_eout);
+    const Header* headers = rt.host_down<Header>(o_headers);
+    const uint32_t* vkeys = rt.host_down<uint32_t>(o_vout);
+    const uint4* edges = rt.host_down<uint4>(o_eout);
     for (size_t x = 0; x < n_items; ++x) {
       const Item& it = items[order[x]];
       const size_t wi = item_window[order[x]];
@@ -665,11 +631,7 @@ int parse(const char* who, int32_t n_seqs, const char* bases, const uint8_t* qua
   if (o->step_k <= 0 || o->min_k <= 0) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": min_k and step_k must be positive");
   }
-  for (int32_t s = 0; s < n_seqs; ++s) {
-    if (seq_off[s] < 0 || seq_off[s + 1] < seq_off[s]) {
-      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": sequence offsets must ascend from >= 0");
-    }
-  }
+  if (int rc = dv::check_sequence_table(name, n_seqs, seq_off)) return rc;
   if (n_seqs > 0 && seq_off[n_seqs] > seq_off[0] && (!bases || !quals)) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null bases or qualities");
   }
@@ -748,7 +710,7 @@ int dv_debruijn_compact_batch(int32_t n_seqs, const char* bases, const uint8_t* 
                               const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
                               const dv_debruijn_options* options, dv_debruijn_compact_result** out,
                               dv_debruijn_compact* arrays) {
-  try {
+  return dv::guarded("dv_debruijn_compact_batch", [&]() -> int {
     Batch b;
     if (int rc = parse("dv_debruijn_compact_batch", n_seqs, bases, quals, seq_off, mapq, n_windows, windows, options,
                        out, arrays, &b)) {
@@ -758,18 +720,14 @@ int dv_debruijn_compact_batch(int32_t n_seqs, const char* bases, const uint8_t* 
     dv::compact_on_host(b.windows, b.options, &graphs);
     publish(graphs, out, arrays);
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_debruijn_compact_batch: out of host memory");
-  } catch (const std::exception& e) {
-    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_debruijn_compact_batch: ") + e.what());
-  }
+  });
 }
 
 int dv_debruijn_compact_batch_device(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
                                      const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
                                      const dv_debruijn_options* options, void* stream,
                                      dv_debruijn_compact_result** out, dv_debruijn_compact* arrays) {
-  try {
+  return dv::guarded("dv_debruijn_compact_batch_device", [&]() -> int {
     dv::last_assembly_stats() = dv::AssemblyStats();
     Batch b;
     if (int rc = parse("dv_debruijn_compact_batch_device", n_seqs, bases, quals, seq_off, mapq, n_windows, windows,
@@ -785,11 +743,7 @@ int dv_debruijn_compact_batch_device(int32_t n_seqs, const char* bases, const ui
     if (int rc = dv::compact_on_device(b.windows, b.options, stream, &graphs, &dv::last_assembly_stats())) return rc;
     publish(graphs, out, arrays);
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_debruijn_compact_batch_device: out of host memory");
-  } catch (const std::exception& e) {
-    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_debruijn_compact_batch_device: ") + e.what());
-  }
+  });
 }
 
 void dv_debruijn_compact_free(dv_debruijn_compact_result* r) { delete r; }

@@ -6,6 +6,8 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -24,6 +26,25 @@ int fail(int status, const std::string& msg);
                                         hipGetErrorString(_e));               \
     }                                                                         \
   } while (0)
+
+// ---- shared pieces of the C entry points
+// A sequence table's offsets seq_off[0 .. n_seqs] must ascend from >= 0 ("<who>: sequence offsets must ascend ...").
+int check_sequence_table(const std::string& who, int32_t n_seqs, const int64_t* seq_off);
+
+// An on/off environment switch, read on every call: unset or empty gives `otherwise`, anything else atoi != 0.
+bool env_switch(const char* name, bool otherwise);
+
+// Runs an entry point's body; no exception leaves the C ABI.
+template <class F>
+int guarded(const char* who, F&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail(DV_ERR_OUT_OF_MEMORY, std::string(who) + ": out of host memory");
+  } catch (const std::exception& e) {
+    return fail(DV_ERR_BAD_INPUT, std::string(who) + ": " + e.what());
+  }
+}
 
 // Grow-only device buffer.
 struct DeviceBuffer {

@@ -25,6 +25,9 @@
 // position only where the haplotype's k-mer is in its index, so the uncovered positions of the tested range -- usually
 // none -- are compared against every k-mer of every read longer than k, 64 positions per wave at a time, until one is
 // found.  Thread 0 stores the haplotype's score and discarded flag.
+//
+// Host side: one upload image, one launch, one download image per call; their layouts and the calling thread's
+// buffers and stream are device_round_trip.h's (Layout, RoundTrip).
 #include <algorithm>
 #include <cctype>
 #include <climits>
@@ -32,7 +35,7 @@
 #include <cstring>
 #include <string>
 
-#include "dv_internal.h"
+#include "device_round_trip.h"
 #include "fast_pass_aligner.h"
 #include "fast_pass_device.h"
 
@@ -210,15 +213,6 @@ __global__ __launch_bounds__(kThreads) void fast_pass_kernel(const uint8_t* __re
   if (tid == 0) hap_out[blockIdx.x] = make_int2(hole ? 0 : total, hole);
 }
 
-struct ThreadState {
-  dv::PinnedStage up, down;
-  dv::DeviceBuffer d_up, d_down;
-  hipStream_t stream = nullptr;   // the library's own, for callers that pass none
-  int stream_device = -1;
-};
-
-size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
-
 // the positions [lo, hi) the hole rule tests, with the host's unsigned arithmetic: a suffix longer than the
 // haplotype wraps and excludes nothing
 void hole_range(int n, int k, int prefix, int suffix, int* lo, int* hi) {
@@ -289,10 +283,7 @@ FastPassStats& last_fast_pass_stats() {
   return stats;
 }
 
-bool device_fast_pass_enabled() {
-  const char* v = getenv("DV_REALIGN_DEVICE_FASTPASS");
-  return v && *v && std::atoi(v) != 0;
-}
+bool device_fast_pass_enabled() { return env_switch("DV_REALIGN_DEVICE_FASTPASS", false); }
 
 void fast_pass_on_host(const std::vector<FastPassWindow>& windows, const FastPassScoring& sc, FastPassResults* out) {
   size_results(windows, out);
@@ -379,27 +370,6 @@ int fast_pass_on_device(const std::vector<FastPassWindow>& windows, const FastPa
     stats->cells += cells;
   }
   if (!items.empty()) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-      return fail(DV_ERR_NO_DEVICE, "fast pass: no HIP device (the device route has no CPU fallback)");
-    }
-    // the call may come from a thread that has not used the device yet
-    int device = 0;
-    DV_HIP_CHECK(hipGetDevice(&device));
-    DV_HIP_CHECK(hipSetDevice(device));
-    static thread_local ThreadState ts;
-    hipStream_t stream = static_cast<hipStream_t>(stream_in);
-    if (!stream) {
-      if (ts.stream && ts.stream_device != device) {
-        (void)hipStreamDestroy(ts.stream);
-        ts.stream = nullptr;
-      }
-      if (!ts.stream) {
-        DV_HIP_CHECK(hipStreamCreateWithFlags(&ts.stream, hipStreamNonBlocking));
-        ts.stream_device = device;
-      }
-      stream = ts.stream;
-    }
     // the heaviest haplotypes first: early workgroups start first
     std::vector<size_t> order(items.size());
     for (size_t x = 0; x < order.size(); ++x) order[x] = x;
@@ -407,40 +377,39 @@ int fast_pass_on_device(const std::vector<FastPassWindow>& windows, const FastPa
       return static_cast<int64_t>(items[a].n) * items[a].n_reads > static_cast<int64_t>(items[b].n) * items[b].n_reads;
     });
     const size_t n_items = items.size();
-    const size_t o_off = align16(n_items * sizeof(Item));
-    const size_t o_bytes = o_off + align16(read_off.size() * sizeof(int32_t));
-    const size_t up_bytes = o_bytes + align16(static_cast<size_t>(n_bytes));
-    const size_t o_haps = align16(static_cast<size_t>(n_rows) * sizeof(int2));
-    const size_t down_bytes = o_haps + n_items * sizeof(int2);
-    if (int rc = ts.up.reserve(up_bytes)) return rc;
-    if (int rc = ts.down.reserve(down_bytes)) return rc;
-    if (int rc = ts.d_up.reserve_on_current_device(up_bytes)) return rc;
-    if (int rc = ts.d_down.reserve_on_current_device(down_bytes)) return rc;
-    Item* up_items = reinterpret_cast<Item*>(ts.up.ptr);
+    Layout up, down;
+    const size_t o_items = up.add(n_items * sizeof(Item));
+    const size_t o_off = up.add(read_off.size() * sizeof(int32_t));
+    const size_t o_bytes = up.add(static_cast<size_t>(n_bytes));
+    // download image: a row per (item, read) | a (score, discarded) per item
+    const size_t o_rows = down.add(static_cast<size_t>(n_rows) * sizeof(int2));
+    const size_t o_haps = down.add_last(n_items * sizeof(int2));
+    static thread_local RoundTrip rt;
+    if (int rc = rt.begin("fast pass: no HIP device (the device route has no CPU fallback)", stream_in, up.bytes(),
+                          down.bytes(), 0)) {
+      return rc;
+    }
+    Item* up_items = rt.host_up<Item>(o_items);
     for (size_t x = 0; x < n_items; ++x) up_items[x] = items[order[x]];
-    std::memcpy(ts.up.ptr + o_off, read_off.data(), read_off.size() * sizeof(int32_t));
-    uint8_t* at = ts.up.ptr + o_bytes;
+    std::memcpy(rt.host_up<int32_t>(o_off), read_off.data(), read_off.size() * sizeof(int32_t));
+    uint8_t* at = rt.host_up<uint8_t>(o_bytes);
     for (std::string_view p : pieces) {
       std::memcpy(at, p.data(), p.size());
       at += p.size();
     }
-    uint8_t* d_up = static_cast<uint8_t*>(ts.d_up.ptr);
-    uint8_t* d_down = static_cast<uint8_t*>(ts.d_down.ptr);
-    DV_HIP_CHECK(hipMemcpyAsync(d_up, ts.up.ptr, up_bytes, hipMemcpyHostToDevice, stream));
+    if (int rc = rt.upload(up.bytes())) return rc;
     {
-      ProfileScope prof(kProfOther, stream);
+      ProfileScope prof(kProfOther, rt.stream());
       const Params prm{sc.kmer_size, sc.max_num_of_mismatches, sc.match, sc.mismatch};
-      hipLaunchKernelGGL(fast_pass_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, stream,
-                         d_up + o_bytes, reinterpret_cast<const int32_t*>(d_up + o_off),
-                         reinterpret_cast<const Item*>(d_up), prm, reinterpret_cast<int2*>(d_down),
-                         reinterpret_cast<int2*>(d_down + o_haps));
+      hipLaunchKernelGGL(fast_pass_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, rt.stream(),
+                         rt.dev_up<const uint8_t>(o_bytes), rt.dev_up<const int32_t>(o_off),
+                         rt.dev_up<const Item>(o_items), prm, rt.dev_down<int2>(o_rows), rt.dev_down<int2>(o_haps));
       DV_HIP_CHECK(hipGetLastError());
     }
-    DV_HIP_CHECK(hipMemcpyAsync(ts.down.ptr, d_down, down_bytes, hipMemcpyDeviceToHost, stream));
-    DV_HIP_CHECK(hipStreamSynchronize(stream));
+    if (int rc = rt.finish(down.bytes())) return rc;
     if (stats) stats->launches += 1;
-    const int2* rows = reinterpret_cast<const int2*>(ts.down.ptr);
-    const int2* haps = reinterpret_cast<const int2*>(ts.down.ptr + o_haps);
+    const int2* rows = rt.host_down<int2>(o_rows);
+    const int2* haps = rt.host_down<int2>(o_haps);
     for (size_t x = 0; x < n_items; ++x) {
       const Item& it = items[order[x]];
       const size_t g = item_haplotype[order[x]];
@@ -483,11 +452,7 @@ int parse(const char* who, int32_t n_seqs, const char* bytes, const int64_t* seq
   if (n_seqs < 0 || n_windows < 0 || (n_seqs > 0 && !seq_off) || (n_windows > 0 && !windows)) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null pointer or negative count");
   }
-  for (int32_t s = 0; s < n_seqs; ++s) {
-    if (seq_off[s] < 0 || seq_off[s + 1] < seq_off[s]) {
-      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": sequence offsets must ascend from >= 0");
-    }
-  }
+  if (int rc = dv::check_sequence_table(name, n_seqs, seq_off)) return rc;
   if (n_seqs > 0 && seq_off[n_seqs] > seq_off[0] && !bytes) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null bytes");
   dv::AlignerOptions ao;
   if (o) {
@@ -564,7 +529,7 @@ int dv_fast_pass_batch(int32_t n_seqs, const char* bytes, const int64_t* seq_off
                        const dv_fast_pass_window* windows, const dv_aligner_options* options, void* /*stream*/,
                        int32_t* haplotype_score, int32_t* haplotype_discarded, int32_t* read_position,
                        int32_t* read_score) {
-  try {
+  return dv::guarded("dv_fast_pass_batch", [&]() -> int {
     Batch b;
     if (int rc = parse("dv_fast_pass_batch", n_seqs, bytes, seq_off, n_windows, windows, options, haplotype_score,
                        haplotype_discarded, read_position, read_score, &b)) {
@@ -575,18 +540,14 @@ int dv_fast_pass_batch(int32_t n_seqs, const char* bytes, const int64_t* seq_off
     dv::fast_pass_on_host(b.windows, b.scoring, &res);
     copy_out(res, haplotype_score, haplotype_discarded, read_position, read_score);
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_fast_pass_batch: out of host memory");
-  } catch (const std::exception& e) {
-    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_fast_pass_batch: ") + e.what());
-  }
+  });
 }
 
 int dv_fast_pass_batch_device(int32_t n_seqs, const char* bytes, const int64_t* seq_off, int32_t n_windows,
                               const dv_fast_pass_window* windows, const dv_aligner_options* options, void* stream,
                               int32_t* haplotype_score, int32_t* haplotype_discarded, int32_t* read_position,
                               int32_t* read_score) {
-  try {
+  return dv::guarded("dv_fast_pass_batch_device", [&]() -> int {
     dv::last_fast_pass_stats() = dv::FastPassStats();
     Batch b;
     if (int rc = parse("dv_fast_pass_batch_device", n_seqs, bytes, seq_off, n_windows, windows, options,
@@ -602,11 +563,7 @@ int dv_fast_pass_batch_device(int32_t n_seqs, const char* bytes, const int64_t* 
     if (int rc = dv::fast_pass_on_device(b.windows, b.scoring, stream, &res, &dv::last_fast_pass_stats())) return rc;
     copy_out(res, haplotype_score, haplotype_discarded, read_position, read_score);
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_fast_pass_batch_device: out of host memory");
-  } catch (const std::exception& e) {
-    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_fast_pass_batch_device: ") + e.what());
-  }
+  });
 }
 
 int dv_fast_pass_device_last_stats(dv_fast_pass_stats* out) {

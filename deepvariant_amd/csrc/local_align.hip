@@ -54,12 +54,15 @@
 // Lane 0 writes the runs as they close, last run first.  A pair that cannot be finished here
 // (band > 31, more than 64 runs, no scratch area, or where banded_cigar itself gives up) is
 // flagged not traced and the host's banded_cigar does it: the host never reads a partial list.
+//
+// Host side: one upload image, one launch, one download per call; the image's layout and the calling
+// thread's buffers, scratch (the direction bytes) and stream are device_round_trip.h's (Layout, RoundTrip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
 
-#include "dv_internal.h"
+#include "device_round_trip.h"
 #include "local_align_device.h"
 
 static_assert(sizeof(dv_realign_device_stats) == 32, "dv_realign_device_stats layout");
@@ -380,15 +383,6 @@ __global__ __launch_bounds__(64 * kWavesPerGroup) void local_align_sweeps(
   }
 }
 
-struct ThreadState {
-  dv::PinnedStage up, down;
-  dv::DeviceBuffer d_up, d_down, d_scratch;   // d_scratch: the trace-back's direction bytes
-  hipStream_t stream = nullptr;   // the library's own, for callers that pass none
-  int stream_device = -1;
-};
-
-size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
-
 int rows_bucket(size_t query_len) {
   const int need = static_cast<int>((query_len + 63) / 64);
   for (int b : kRowBuckets) {
@@ -475,46 +469,23 @@ int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, co
     }
   }
 
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-    return fail(DV_ERR_NO_DEVICE, "local aligner: no HIP device (the device route has no CPU fallback)");
-  }
-  // the call may come from a thread that has not used the device yet (RealignJob.start on an executor)
-  int device = 0;
-  DV_HIP_CHECK(hipGetDevice(&device));
-  DV_HIP_CHECK(hipSetDevice(device));
-  static thread_local ThreadState ts;
-  hipStream_t stream = static_cast<hipStream_t>(stream_in);
-  if (!stream) {
-    if (ts.stream && ts.stream_device != device) {
-      (void)hipStreamDestroy(ts.stream);
-      ts.stream = nullptr;
-    }
-    if (!ts.stream) {
-      DV_HIP_CHECK(hipStreamCreateWithFlags(&ts.stream, hipStreamNonBlocking));
-      ts.stream_device = device;
-    }
-    stream = ts.stream;
-  }
-
   // upload image: items | sequence offsets | codes
   const size_t n_items = items.size();
-  const size_t o_items = 0;
-  const size_t o_off = align16(n_items * sizeof(SweepItem));
-  const size_t o_codes = o_off + align16((used.size() + 1) * sizeof(int32_t));
-  const size_t up_bytes = o_codes + align16(n_codes);
+  Layout up;
+  const size_t o_items = up.add(n_items * sizeof(SweepItem));
+  const size_t o_off = up.add((used.size() + 1) * sizeof(int32_t));
+  const size_t o_codes = up.add(n_codes);
+  // download image: out_words per pair
   const size_t out_words = trace ? kTraceWords : kCornerWords;
   const size_t down_bytes = n_items * out_words * sizeof(int32_t);
-  if (int rc = ts.up.reserve(up_bytes)) return rc;
-  if (int rc = ts.down.reserve(down_bytes)) return rc;
-  if (int rc = ts.d_up.reserve_on_current_device(up_bytes)) return rc;
-  if (int rc = ts.d_down.reserve_on_current_device(down_bytes)) return rc;
-  if (scratch_units > 0) {
-    if (int rc = ts.d_scratch.reserve_on_current_device(scratch_units * kAreaUnit)) return rc;
+  static thread_local RoundTrip rt;     // its scratch: the trace-back's direction bytes
+  if (int rc = rt.begin("local aligner: no HIP device (the device route has no CPU fallback)", stream_in, up.bytes(),
+                        down_bytes, scratch_units * kAreaUnit)) {
+    return rc;
   }
-  std::memcpy(ts.up.ptr + o_items, items.data(), n_items * sizeof(SweepItem));
-  int32_t* off = reinterpret_cast<int32_t*>(ts.up.ptr + o_off);
-  uint8_t* codes = ts.up.ptr + o_codes;
+  std::memcpy(rt.host_up<SweepItem>(o_items), items.data(), n_items * sizeof(SweepItem));
+  int32_t* off = rt.host_up<int32_t>(o_off);
+  uint8_t* codes = rt.host_up<uint8_t>(o_codes);
   int32_t at = 0;
   for (size_t u = 0; u < used.size(); ++u) {
     const CodedSequence& s = *sequences[used[u]];
@@ -524,23 +495,20 @@ int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, co
   }
   off[used.size()] = at;
 
-  uint8_t* d_up = static_cast<uint8_t*>(ts.d_up.ptr);
-  DV_HIP_CHECK(hipMemcpyAsync(d_up, ts.up.ptr, up_bytes, hipMemcpyHostToDevice, stream));
+  if (int rc = rt.upload(up.bytes())) return rc;
   {
-    ProfileScope prof(kProfOther, stream);
+    ProfileScope prof(kProfOther, rt.stream());
     const Scoring sc{match, mismatch, gap_open, gap_extend};
     const unsigned groups = static_cast<unsigned>((n_items + kWavesPerGroup - 1) / kWavesPerGroup);
-    hipLaunchKernelGGL(local_align_sweeps, dim3(groups), dim3(64 * kWavesPerGroup), 0, stream, d_up + o_codes,
-                       reinterpret_cast<const int32_t*>(d_up + o_off),
-                       reinterpret_cast<const SweepItem*>(d_up + o_items), static_cast<int>(n_items), sc,
-                       static_cast<int32_t*>(ts.d_down.ptr), static_cast<int>(out_words),
-                       static_cast<uint8_t*>(ts.d_scratch.ptr));
+    hipLaunchKernelGGL(local_align_sweeps, dim3(groups), dim3(64 * kWavesPerGroup), 0, rt.stream(),
+                       rt.dev_up<const uint8_t>(o_codes), rt.dev_up<const int32_t>(o_off),
+                       rt.dev_up<const SweepItem>(o_items), static_cast<int>(n_items), sc, rt.dev_down<int32_t>(0),
+                       static_cast<int>(out_words), static_cast<uint8_t*>(rt.d_scratch.ptr));
     DV_HIP_CHECK(hipGetLastError());
   }
-  DV_HIP_CHECK(hipMemcpyAsync(ts.down.ptr, ts.d_down.ptr, down_bytes, hipMemcpyDeviceToHost, stream));
-  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int rc = rt.finish(down_bytes)) return rc;
   if (stats) stats->launches += 1;
-  const int32_t* res = reinterpret_cast<const int32_t*>(ts.down.ptr);
+  const int32_t* res = rt.host_down<int32_t>(0);
   for (size_t w = 0; w < n_items; ++w) {
     const int32_t* r = res + w * out_words;
     const size_t k = static_cast<size_t>(items[w].pair);
@@ -574,10 +542,7 @@ TracebackStats& last_traceback_stats() {
   return stats;
 }
 
-bool device_traceback_enabled() {
-  const char* v = getenv("DV_REALIGN_DEVICE_TRACEBACK");
-  return v && *v ? std::atoi(v) != 0 : kTracebackByDefault;
-}
+bool device_traceback_enabled() { return env_switch("DV_REALIGN_DEVICE_TRACEBACK", kTracebackByDefault); }
 
 bool complete_on_device_route(const LocalAligner& aligner, const CodedSequence& ref, const CodedSequence& q,
                               const SweepCorners& corners, const DeviceRuns* traced, size_t k, LocalAlignment* out) {
@@ -614,7 +579,7 @@ extern "C" {
 int dv_local_align_pairs_device(int32_t n_seqs, const char* bases, const int64_t* seq_off, int32_t n_pairs,
                                 const int32_t* pair_ref, const int32_t* pair_query, int32_t match, int32_t mismatch,
                                 int32_t gap_open, int32_t gap_extend, dv_local_alignment* out, void* stream) {
-  try {
+  return dv::guarded("dv_local_align_pairs_device", [&]() -> int {
     g_last_stats = dv::DeviceAlignStats();
     dv::last_traceback_stats() = dv::TracebackStats();
     if (n_seqs < 0 || n_pairs < 0 || (n_seqs > 0 && !seq_off) || (n_pairs > 0 && (!pair_ref || !pair_query || !out))) {
@@ -626,11 +591,7 @@ int dv_local_align_pairs_device(int32_t n_seqs, const char* bases, const int64_t
       return dv::fail(DV_ERR_INVALID_ARGUMENT,
                       "dv_local_align_pairs_device: match must be in [1, 127], the penalties in [0, 127]");
     }
-    for (int32_t s = 0; s < n_seqs; ++s) {
-      if (seq_off[s] < 0 || seq_off[s + 1] < seq_off[s]) {
-        return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_local_align_pairs_device: sequence offsets must ascend from >= 0");
-      }
-    }
+    if (int rc = dv::check_sequence_table("dv_local_align_pairs_device", n_seqs, seq_off)) return rc;
     if (n_seqs > 0 && seq_off[n_seqs] > seq_off[0] && !bases) {
       return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_local_align_pairs_device: null bases");
     }
@@ -682,11 +643,7 @@ int dv_local_align_pairs_device(int32_t n_seqs, const char* bases, const int64_t
       }
     }
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, "dv_local_align_pairs_device: out of host memory");
-  } catch (const std::exception& e) {
-    return dv::fail(DV_ERR_BAD_INPUT, std::string("dv_local_align_pairs_device: ") + e.what());
-  }
+  });
 }
 
 int dv_local_align_device_last_stats(dv_realign_device_stats* out) {

@@ -35,14 +35,18 @@
 // pairs in order; pass 3 (emit) writes each kept pair's row and copies its operations, lane 0 and the last lane
 // patching the two cut lengths.  Placement is a pure function of the input (no atomics decide it); the one atomic
 // is the minimum over the offending pairs for the error report.
+//
+// Host side: one upload image, the three launches, one download image per call; the layouts of the images and of
+// the device-only work space, and the calling thread's buffers and stream, are device_round_trip.h's (Layout,
+// RoundTrip).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "dv_internal.h"
+#include "device_round_trip.h"
 #include "trim_reads.h"
 
 namespace {
@@ -271,15 +275,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void trim_emit_kernel(Tables
   }
 }
 
-struct ThreadState {
-  dv::PinnedStage up, down;
-  dv::DeviceBuffer d_up, d_down, d_work;
-  hipStream_t stream = nullptr;   // the library's own, for callers that pass none
-  int stream_device = -1;
-};
-
-size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
-
 dv_trim_stats& last_stats() {
   static thread_local dv_trim_stats stats;
   return stats;
@@ -408,92 +403,70 @@ int trim_on_device(const Call& c, int32_t n_windows, const dv_trim_window* windo
   const dv_batch& b = *c.reads;
   const size_t n_reads = static_cast<size_t>(b.n_reads), n_pairs = c.pairs.size(), n_win = static_cast<size_t>(n_windows);
   const size_t n_cigar = b.read_cigar_off[n_reads], bound = static_cast<size_t>(c.words);
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-    return dv::fail(DV_ERR_NO_DEVICE, "dv_trim_reads_batch_device: no HIP device (dv_trim_reads_batch is the host code)");
-  }
-  // the call may come from a thread that has not used the device yet
-  int device = 0;
-  DV_HIP_CHECK(hipGetDevice(&device));
-  DV_HIP_CHECK(hipSetDevice(device));
-  static thread_local ThreadState ts;
-  hipStream_t stream = static_cast<hipStream_t>(stream_in);
-  if (!stream) {
-    if (ts.stream && ts.stream_device != device) {
-      (void)hipStreamDestroy(ts.stream);
-      ts.stream = nullptr;
-    }
-    if (!ts.stream) {
-      DV_HIP_CHECK(hipStreamCreateWithFlags(&ts.stream, hipStreamNonBlocking));
-      ts.stream_device = device;
-    }
-    stream = ts.stream;
-  }
+  dv::Layout up, down, work;
   // upload image: error word | windows | window pair offsets | pairs | read_pos | seq_len | cigar_off | cigar
-  const size_t u_windows = 16;
-  const size_t u_wpo = u_windows + align16(n_win * sizeof(dv_trim_window));
-  const size_t u_pairs = u_wpo + align16((n_win + 1) * sizeof(int32_t));
-  const size_t u_pos = u_pairs + align16(n_pairs * sizeof(Pair));
-  const size_t u_len = u_pos + align16(n_reads * sizeof(int32_t));
-  const size_t u_coff = u_len + align16(n_reads * sizeof(uint32_t));
-  const size_t u_cigar = u_coff + align16((n_reads + 1) * sizeof(uint32_t));
-  const size_t up_bytes = u_cigar + align16(n_cigar * sizeof(uint32_t));
+  const size_t u_error = up.add(sizeof(unsigned long long));
+  const size_t u_windows = up.add(n_win * sizeof(dv_trim_window));
+  const size_t u_wpo = up.add((n_win + 1) * sizeof(int32_t));
+  const size_t u_pairs = up.add(n_pairs * sizeof(Pair));
+  const size_t u_pos = up.add(n_reads * sizeof(int32_t));
+  const size_t u_len = up.add(n_reads * sizeof(uint32_t));
+  const size_t u_coff = up.add((n_reads + 1) * sizeof(uint32_t));
+  const size_t u_cigar = up.add(n_cigar * sizeof(uint32_t));
   // download image: header | window row offsets | five row arrays | cigar_off | words, each for the most there can be
-  const size_t rows4 = align16(n_pairs * sizeof(int32_t));
-  const size_t d_wro = 16;
-  const size_t d_rows = d_wro + align16((n_win + 1) * sizeof(int32_t));
-  const size_t d_coff = d_rows + 5 * rows4;
-  const size_t d_words = d_coff + align16((n_pairs + 1) * sizeof(uint32_t));
-  const size_t down_bytes = d_words + align16(bound * sizeof(uint32_t));
+  const size_t d_header = down.add(sizeof(Header));
+  const size_t d_wro = down.add((n_win + 1) * sizeof(int32_t));
+  size_t d_rows[5];     // src_row, pos, end, read_trim, new_len
+  for (size_t& at : d_rows) at = down.add(n_pairs * sizeof(int32_t));
+  const size_t d_coff = down.add((n_pairs + 1) * sizeof(uint32_t));
+  const size_t d_words = down.add(bound * sizeof(uint32_t));
   // device-only work space: PairResult per pair | row_of | word_of
-  const size_t k_row = align16(n_pairs * sizeof(PairResult));
-  const size_t k_word = k_row + align16((n_pairs + 1) * sizeof(int32_t));
-  const size_t work_bytes = k_word + align16((n_pairs + 1) * sizeof(uint32_t));
-  static_assert(sizeof(Header) <= 16, "the header has 16 bytes of the download");
-  if (int rc = ts.up.reserve(up_bytes)) return rc;
-  if (int rc = ts.down.reserve(down_bytes)) return rc;
-  if (int rc = ts.d_up.reserve_on_current_device(up_bytes)) return rc;
-  if (int rc = ts.d_down.reserve_on_current_device(down_bytes)) return rc;
-  if (int rc = ts.d_work.reserve_on_current_device(work_bytes)) return rc;
-  uint8_t* up = ts.up.ptr;
-  *reinterpret_cast<unsigned long long*>(up) = dv::trim::kNoError;
-  if (n_win) std::memcpy(up + u_windows, windows, n_win * sizeof(dv_trim_window));
-  std::memcpy(up + u_wpo, c.window_pair_off.data(), (n_win + 1) * sizeof(int32_t));
-  std::memcpy(up + u_pairs, c.pairs.data(), n_pairs * sizeof(Pair));
-  std::memcpy(up + u_pos, b.read_pos, n_reads * sizeof(int32_t));
-  uint32_t* seq_len = reinterpret_cast<uint32_t*>(up + u_len);
+  const size_t k_results = work.add(n_pairs * sizeof(PairResult));
+  const size_t k_row = work.add((n_pairs + 1) * sizeof(int32_t));
+  const size_t k_word = work.add((n_pairs + 1) * sizeof(uint32_t));
+  static_assert(sizeof(Header) <= 16 && sizeof(unsigned long long) <= 16, "the two first sections take 16 bytes each");
+  static thread_local dv::RoundTrip rt;     // its scratch: the work space
+  if (int rc = rt.begin("dv_trim_reads_batch_device: no HIP device (dv_trim_reads_batch is the host code)", stream_in,
+                        up.bytes(), down.bytes(), work.bytes())) {
+    return rc;
+  }
+  *rt.host_up<unsigned long long>(u_error) = dv::trim::kNoError;
+  if (n_win) std::memcpy(rt.host_up<dv_trim_window>(u_windows), windows, n_win * sizeof(dv_trim_window));
+  std::memcpy(rt.host_up<int32_t>(u_wpo), c.window_pair_off.data(), (n_win + 1) * sizeof(int32_t));
+  std::memcpy(rt.host_up<Pair>(u_pairs), c.pairs.data(), n_pairs * sizeof(Pair));
+  std::memcpy(rt.host_up<int32_t>(u_pos), b.read_pos, n_reads * sizeof(int32_t));
+  uint32_t* seq_len = rt.host_up<uint32_t>(u_len);
   for (size_t r = 0; r < n_reads; ++r) seq_len[r] = b.read_seq_off[r + 1] - b.read_seq_off[r];
-  std::memcpy(up + u_coff, b.read_cigar_off, (n_reads + 1) * sizeof(uint32_t));
-  if (n_cigar) std::memcpy(up + u_cigar, b.cigar, n_cigar * sizeof(uint32_t));
-  uint8_t* d_up = static_cast<uint8_t*>(ts.d_up.ptr);
-  uint8_t* d_down = static_cast<uint8_t*>(ts.d_down.ptr);
-  uint8_t* d_work = static_cast<uint8_t*>(ts.d_work.ptr);
+  std::memcpy(rt.host_up<uint32_t>(u_coff), b.read_cigar_off, (n_reads + 1) * sizeof(uint32_t));
+  if (n_cigar) std::memcpy(rt.host_up<uint32_t>(u_cigar), b.cigar, n_cigar * sizeof(uint32_t));
   Tables t;
-  t.read_pos = reinterpret_cast<const int32_t*>(d_up + u_pos);
-  t.seq_len = reinterpret_cast<const uint32_t*>(d_up + u_len);
-  t.cigar_off = reinterpret_cast<const uint32_t*>(d_up + u_coff);
-  t.cigar = reinterpret_cast<const uint32_t*>(d_up + u_cigar);
-  t.windows = reinterpret_cast<const dv_trim_window*>(d_up + u_windows);
-  t.pairs = reinterpret_cast<const Pair*>(d_up + u_pairs);
-  t.window_pair_off = reinterpret_cast<const int32_t*>(d_up + u_wpo);
+  t.read_pos = rt.dev_up<const int32_t>(u_pos);
+  t.seq_len = rt.dev_up<const uint32_t>(u_len);
+  t.cigar_off = rt.dev_up<const uint32_t>(u_coff);
+  t.cigar = rt.dev_up<const uint32_t>(u_cigar);
+  t.windows = rt.dev_up<const dv_trim_window>(u_windows);
+  t.pairs = rt.dev_up<const Pair>(u_pairs);
+  t.window_pair_off = rt.dev_up<const int32_t>(u_wpo);
   t.n_pairs = static_cast<int32_t>(n_pairs);
   t.n_windows = n_windows;
   Outputs o;
-  o.header = reinterpret_cast<Header*>(d_down);
-  o.window_row_off = reinterpret_cast<int32_t*>(d_down + d_wro);
-  o.src_row = reinterpret_cast<int32_t*>(d_down + d_rows);
-  o.pos = reinterpret_cast<int32_t*>(d_down + d_rows + rows4);
-  o.end = reinterpret_cast<int32_t*>(d_down + d_rows + 2 * rows4);
-  o.read_trim = reinterpret_cast<int32_t*>(d_down + d_rows + 3 * rows4);
-  o.new_len = reinterpret_cast<int32_t*>(d_down + d_rows + 4 * rows4);
-  o.cigar_off = reinterpret_cast<uint32_t*>(d_down + d_coff);
-  o.cigar = reinterpret_cast<uint32_t*>(d_down + d_words);
-  unsigned long long* d_error = reinterpret_cast<unsigned long long*>(d_up);
-  PairResult* d_results = reinterpret_cast<PairResult*>(d_work);
+  o.header = rt.dev_down<Header>(d_header);
+  o.window_row_off = rt.dev_down<int32_t>(d_wro);
+  o.src_row = rt.dev_down<int32_t>(d_rows[0]);
+  o.pos = rt.dev_down<int32_t>(d_rows[1]);
+  o.end = rt.dev_down<int32_t>(d_rows[2]);
+  o.read_trim = rt.dev_down<int32_t>(d_rows[3]);
+  o.new_len = rt.dev_down<int32_t>(d_rows[4]);
+  o.cigar_off = rt.dev_down<uint32_t>(d_coff);
+  o.cigar = rt.dev_down<uint32_t>(d_words);
+  unsigned long long* d_error = rt.dev_up<unsigned long long>(u_error);
+  uint8_t* d_work = static_cast<uint8_t*>(rt.d_scratch.ptr);
+  PairResult* d_results = reinterpret_cast<PairResult*>(d_work + k_results);
   int32_t* d_row_of = reinterpret_cast<int32_t*>(d_work + k_row);
   uint32_t* d_word_of = reinterpret_cast<uint32_t*>(d_work + k_word);
   const unsigned blocks = static_cast<unsigned>((n_pairs + kWavesPerBlock - 1) / kWavesPerBlock);
-  DV_HIP_CHECK(hipMemcpyAsync(d_up, up, up_bytes, hipMemcpyHostToDevice, stream));
+  hipStream_t stream = rt.stream();
+  if (int rc = rt.upload(up.bytes())) return rc;
   {
     dv::ProfileScope prof(dv::kProfOther, stream);
     hipLaunchKernelGGL(trim_count_kernel, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, stream, t, d_results, d_error);
@@ -505,25 +478,23 @@ int trim_on_device(const Call& c, int32_t n_windows, const dv_trim_window* windo
                        d_word_of, o);
     DV_HIP_CHECK(hipGetLastError());
   }
-  DV_HIP_CHECK(hipMemcpyAsync(ts.down.ptr, d_down, down_bytes, hipMemcpyDeviceToHost, stream));
-  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int rc = rt.finish(down.bytes())) return rc;
   stats->launches += 3;
-  const uint8_t* down = ts.down.ptr;
-  const Header header = *reinterpret_cast<const Header*>(down);
+  const Header header = *rt.host_down<Header>(d_header);
   if (header.error != dv::trim::kNoError) return pair_error("dv_trim_reads_batch_device", c, windows, header.error);
   const size_t n_rows = static_cast<size_t>(header.n_rows), n_words = static_cast<size_t>(header.n_words);
   if (n_rows > n_pairs || n_words > bound) return dv::fail(DV_ERR_HIP, "dv_trim_reads_batch_device: totals past their bounds");
-  auto rows_of = [&](size_t k) { return reinterpret_cast<const int32_t*>(down + d_rows + k * rows4); };
-  const int32_t* wro = reinterpret_cast<const int32_t*>(down + d_wro);
+  auto rows_of = [&](size_t k) { return rt.host_down<int32_t>(d_rows[k]); };
+  const int32_t* wro = rt.host_down<int32_t>(d_wro);
   res->window_row_off.assign(wro, wro + n_win + 1);
   res->src_row.assign(rows_of(0), rows_of(0) + n_rows);
   res->pos.assign(rows_of(1), rows_of(1) + n_rows);
   res->end.assign(rows_of(2), rows_of(2) + n_rows);
   res->read_trim.assign(rows_of(3), rows_of(3) + n_rows);
   res->new_len.assign(rows_of(4), rows_of(4) + n_rows);
-  const uint32_t* coff = reinterpret_cast<const uint32_t*>(down + d_coff);
+  const uint32_t* coff = rt.host_down<uint32_t>(d_coff);
   res->cigar_off.assign(coff, coff + n_rows + 1);
-  const uint32_t* words = reinterpret_cast<const uint32_t*>(down + d_words);
+  const uint32_t* words = rt.host_down<uint32_t>(d_words);
   res->cigar.assign(words, words + n_words);
   stats->pairs_kept += static_cast<int64_t>(n_rows);
   stats->words_written += static_cast<int64_t>(n_words);
@@ -532,36 +503,26 @@ int trim_on_device(const Call& c, int32_t n_windows, const dv_trim_window* windo
 
 int run(const char* who, bool on_device, const dv_batch* reads, const int64_t* read_end, int32_t n_windows,
         const dv_trim_window* windows, dv_trimmed_reads** out, void* stream) {
-  dv_trimmed_reads* res = nullptr;
-  try {
+  return dv::guarded(who, [&]() -> int {
     if (on_device) last_stats() = dv_trim_stats{0, 0, 0, 0, 0};
     Call c;
     if (int rc = parse(who, reads, read_end, n_windows, windows, out, &c)) return rc;
-    res = new dv_trimmed_reads();
+    auto res = std::make_unique<dv_trimmed_reads>();
     int rc = DV_OK;
     if (!on_device) {
-      rc = trim_on_host(c, n_windows, windows, res);
+      rc = trim_on_host(c, n_windows, windows, res.get());
     } else if (c.pairs.empty()) {          // nothing to launch
       res->window_row_off.assign(static_cast<size_t>(n_windows) + 1, 0);
       res->cigar_off.assign(1, 0);
     } else {
       last_stats().pairs_tested = static_cast<int64_t>(c.pairs.size());
       last_stats().words_read = c.words;
-      rc = trim_on_device(c, n_windows, windows, stream, res, &last_stats());
+      rc = trim_on_device(c, n_windows, windows, stream, res.get(), &last_stats());
     }
-    if (rc) {
-      delete res;
-      return rc;
-    }
-    *out = res;
+    if (rc) return rc;
+    *out = res.release();
     return DV_OK;
-  } catch (const std::bad_alloc&) {
-    delete res;
-    return dv::fail(DV_ERR_OUT_OF_MEMORY, std::string(who) + ": out of host memory");
-  } catch (const std::exception& e) {
-    delete res;
-    return dv::fail(DV_ERR_BAD_INPUT, std::string(who) + ": " + e.what());
-  }
+  });
 }
 
 }  // namespace
