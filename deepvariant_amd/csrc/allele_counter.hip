@@ -21,11 +21,7 @@
 #include <memory>
 #include <vector>
 
-#include "candidates.h"
-#include "device_round_trip.h"
-#include "gvcf.h"
-
-using dv::align16;
+#include "allele_counter_plan.h"
 
 // Large results live in pinned host memory (the count array of a 7.7 Mb interval is 31 MB: 1.3 ms
 // over PCIe from pinned memory, 5 ms into pageable); small ones -- a 1 kb calling region's 4 KB of
@@ -66,25 +62,6 @@ struct PinnedArray {
     n = 0;
   }
   ~PinnedArray() { release(); }
-};
-
-// Grow-only pinned staging for the batch entry point (one per host thread and direction).
-struct PinnedBytes {
-  uint8_t* ptr = nullptr;
-  size_t cap = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return DV_OK;
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 20);
-    if (hipHostMalloc(reinterpret_cast<void**>(&ptr), want, hipHostMallocDefault) != hipSuccess) {
-      ptr = nullptr;
-      return dv::fail(DV_ERR_OUT_OF_MEMORY, "hipHostMalloc (allele counter staging)");
-    }
-    cap = want;
-    return DV_OK;
-  }
 };
 
 struct dv_allele_counts {
@@ -447,9 +424,7 @@ int check_request(const dv_batch* b, const dv_allele_counter_options* o, dv_alle
       }
     }
   }
-  const int64_t reads_start = std::min(o->interval_start, o->reads_interval_start);
-  const int64_t reads_end = std::max(o->interval_end, o->reads_interval_end);
-  if (o->ref_start > reads_start || o->ref_start + o->n_ref_bases < reads_end) {
+  if (o->ref_start > dv::reads_start(o) || o->ref_start + o->n_ref_bases < dv::reads_end(o)) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": the reference window must cover the reads interval");
   }
   int count = 0;
@@ -459,69 +434,161 @@ int check_request(const dv_batch* b, const dv_allele_counter_options* o, dv_alle
   return DV_OK;
 }
 
-// The gVCF pass over counts that are already on the host (a region that took the one-region path:
-// a device-resident read table, no reads, or events beyond the batch's first guess): the counts go
-// back up and through the same kernels.  One synchronisation; the rare path.
+// ---- one of each piece the one-region entry, the batch entry and the passes behind them share
+
+// Everything of CountArgs but the seven table pointers, `ref`, `candidate_mask` and the outputs.
+CountArgs fill_count_args(const dv_batch* b, const dv_allele_counter_options* o, int64_t len) {
+  CountArgs a{};
+  a.n_reads = b->n_reads;
+  a.ref_start = o->ref_start;
+  a.n_ref = o->n_ref_bases;
+  a.reads_start = dv::reads_start(o);
+  a.reads_end = dv::reads_end(o);
+  a.interval_start = o->interval_start;
+  a.interval_len = len;
+  a.contig_len = o->contig_n_bases > 0 ? o->contig_n_bases : o->ref_start + o->n_ref_bases;
+  a.min_mapq = o->min_mapping_quality;
+  a.min_bq = o->min_base_quality;
+  a.legacy = o->keep_legacy_behavior ? 1 : 0;
+  return a;
+}
+
+// track_ref_reads: one bit per position of the interval, set at the candidate positions; dv::mask_words(len) words.
+void build_candidate_mask(const dv_allele_counter_options* o, int64_t len, uint32_t* words) {
+  std::memset(words, 0, dv::mask_words(len) * sizeof(uint32_t));
+  for (int32_t k = 0; k < o->n_candidate_positions; ++k) {
+    const int64_t p = o->candidate_positions[k] - o->interval_start;
+    if (p >= 0 && p < len) words[static_cast<size_t>(p >> 5)] |= 1u << (p & 31);
+  }
+}
+
+void launch_count(const CountArgs& a, int32_t n_reads, hipStream_t stream) {
+  dv::ProfileScope prof(dv::kProfOther, stream);
+  hipLaunchKernelGGL(count_alleles_kernel, dim3((n_reads + 4 * kReadsPerWave - 1) / (4 * kReadsPerWave)), dim3(256), 0,
+                     stream, a);
+}
+
+int window_too_small() {           // counters[2] of a launch is not zero
+  return dv::fail(DV_ERR_BAD_INPUT, "dv_count_alleles: an indel reaches outside the reference window (pass more margin)");
+}
+
+// A region's counts where a pass behind the counter finds them on the device: what GvcfRegion and CandRegion share.
+struct CountsOnDevice {
+  const int32_t* ref_count;
+  const dv_allele_event* events;
+  const uint32_t* n_events;
+  uint32_t event_cap;
+  const int32_t* read_key;         // null: every read is its own key
+  const uint8_t* ref;              // of the interval
+  int64_t interval_start, len;
+};
+
+dv::GvcfRegion gvcf_region(const CountsOnDevice& c, const dv_gvcf_options* gv, int32_t* scratch, dv_gvcf_block* blocks,
+                           int32_t* n_blocks) {
+  return dv::GvcfRegion{c.ref_count, c.events, c.n_events, c.event_cap, c.read_key, c.ref, c.interval_start,
+                        static_cast<int32_t>(c.len), gv->left_padding, static_cast<int32_t>(c.len - gv->right_padding),
+                        scratch, blocks, n_blocks};      // in the order of gvcf.h
+}
+
+// bases, seq_off: the read table's, which the events point into
+dv::CandRegion cand_region(const CountsOnDevice& c, const uint8_t* bases, const uint32_t* seq_off, int32_t* scratch,
+                           dv_candidate_site* sites, dv_candidate_allele* alleles, int32_t* words, int32_t* n_out) {
+  return dv::CandRegion{c.ref_count, c.events, c.n_events, c.event_cap, c.read_key, c.ref, bases, seq_off,
+                        static_cast<int32_t>(c.len), scratch, sites, alleles, words, n_out};   // in the order of candidates.h
+}
+
+template <class T>
+T* at(void* base, size_t bytes) { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + bytes); }
+
+// ---- a pass over counts that are already on the host (a region that took the one-region path: a device-resident
+// read table, no reads, or events beyond the batch's first guess): the counts and sorted events go back up and
+// through the same kernels.  The rare path.  One device image per pass:
+//   descriptor | n_events and the pass' record counts | ref_count | events | ref | keys   -- the same for both passes
+//   | what else the pass uploads | scratch | the pass' records
+struct CountsImage {
+  dv::Layout lay;
+  size_t desc = 0, words = 0, counts = 0, events = 0, ref = 0, keys = 0;
+  int64_t len = 0;
+  uint32_t n_ev = 0;
+  size_t n_keys = 0;
+};
+
+CountsImage lay_counts_image(size_t descriptor_bytes, const dv_allele_counts* c, const dv_batch* b, const int32_t* keys) {
+  CountsImage im;
+  im.len = c->length;
+  im.n_ev = static_cast<uint32_t>(c->events.size());
+  im.n_keys = keys ? static_cast<size_t>(b->n_reads) : 0;
+  im.desc = im.lay.add(descriptor_bytes);
+  im.words = im.lay.add(16);
+  im.counts = im.lay.add(static_cast<size_t>(im.len) * sizeof(int32_t));
+  im.events = im.lay.add(static_cast<size_t>(im.n_ev) * sizeof(dv_allele_event));
+  im.ref = im.lay.add(static_cast<size_t>(im.len));
+  im.keys = im.lay.add(im.n_keys * sizeof(int32_t));
+  return im;
+}
+
+// One thread's buffers for one such pass: the upload is staged in pinned memory, so the asynchronous copy reads
+// nothing of the caller's; the stage is free again when the pass returns, because it ends on a synchronisation.
+struct CountsBuffers {
+  dv::PinnedStage stage;
+  dv::DeviceBuffer d_img;
+};
+
+// Fills the shared sections of the staged image -> where the pass finds them on the device.
+CountsOnDevice stage_counts(const CountsImage& im, const dv_allele_counts* c, const dv_allele_counter_options* o,
+                            const int32_t* keys, uint8_t* host, uint8_t* dev) {
+  std::memset(host + im.words, 0, 16);
+  std::memcpy(host + im.words, &im.n_ev, 4);
+  const int32_t* cnt = c->ref_count.ptr ? c->ref_count.ptr : c->empty_counts.data();
+  if (im.len) std::memcpy(host + im.counts, cnt, static_cast<size_t>(im.len) * sizeof(int32_t));
+  if (im.n_ev) std::memcpy(host + im.events, c->events.data(), static_cast<size_t>(im.n_ev) * sizeof(dv_allele_event));
+  std::memcpy(host + im.ref, o->ref_bases + (o->interval_start - o->ref_start), static_cast<size_t>(im.len));
+  if (im.n_keys) std::memcpy(host + im.keys, keys, im.n_keys * sizeof(int32_t));
+  return CountsOnDevice{at<const int32_t>(dev, im.counts), at<const dv_allele_event>(dev, im.events),
+                        at<const uint32_t>(dev, im.words), im.n_ev, keys ? at<const int32_t>(dev, im.keys) : nullptr,
+                        dev + im.ref, o->interval_start, im.len};
+}
+
+// The image's first up_bytes go up and its scratch section is zeroed; no synchronisation.
+int upload_counts_image(const CountsBuffers& buf, size_t up_bytes, size_t scratch_at, size_t scratch_bytes,
+                        hipStream_t stream) {
+  DV_HIP_CHECK(hipMemcpyAsync(buf.d_img.ptr, buf.stage.ptr, up_bytes, hipMemcpyHostToDevice, stream));
+  DV_HIP_CHECK(hipMemsetAsync(at<uint8_t>(buf.d_img.ptr, scratch_at), 0, scratch_bytes, stream));
+  return DV_OK;
+}
+
+// The first step of the download: the pass' record counts, which lie behind n_events.  Waits for the stream.
+int download_record_counts(const CountsBuffers& buf, const CountsImage& im, int32_t* n_records, int count,
+                           hipStream_t stream) {
+  DV_HIP_CHECK(hipMemcpyAsync(n_records, at<uint8_t>(buf.d_img.ptr, im.words + 4), count * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, stream));
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  return DV_OK;
+}
+
+// The gVCF pass over a region's host counts.  The records land in the result's pageable vector: the copy is
+// followed by a synchronisation before the function returns.
 int gvcf_from_counts(const dv_allele_counts* c, const dv_allele_counter_options* o, const dv_batch* b,
                      const int32_t* keys, const dv_gvcf_options* gv, const dv_gvcf_site* d_table, hipStream_t stream,
                      dv_gvcf_blocks** out) {
-  static thread_local dv::DeviceBuffer d_img;
-  const int64_t len = c->length;
-  const uint32_t n_ev = static_cast<uint32_t>(c->events.size());
-  const size_t n_keys = keys ? static_cast<size_t>(b->n_reads) : 0;
-  // image: descriptor | n_events, n_blocks | ref_count | events | ref | keys | scratch | blocks
-  size_t at = 0;
-  const size_t o_desc = at;
-  at += align16(sizeof(dv::GvcfRegion));
-  const size_t o_words = at;
-  at += 16;
-  const size_t o_cnt = at;
-  at += align16(static_cast<size_t>(len) * 4);
-  const size_t o_ev = at;
-  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
-  const size_t o_ref = at;
-  at += align16(static_cast<size_t>(len));
-  const size_t o_keys = at;
-  at += align16(n_keys * 4);
-  const size_t up_bytes = at;
-  const size_t o_scr = at;
-  at += align16(dv::gvcf_scratch_ints(len, n_ev) * 4);
-  const size_t o_blk = at;
-  const int64_t n_sites = len - gv->left_padding - gv->right_padding;
-  at += static_cast<size_t>(n_sites) * sizeof(dv_gvcf_block);
-  if (int rc = d_img.reserve_on_current_device(at)) return rc;
-  uint8_t* dev = static_cast<uint8_t*>(d_img.ptr);
-  std::vector<uint8_t> img(up_bytes, 0);
-  dv::GvcfRegion g{};
-  g.ref_count = reinterpret_cast<const int32_t*>(dev + o_cnt);
-  g.events = reinterpret_cast<const dv_allele_event*>(dev + o_ev);
-  g.n_events = reinterpret_cast<const uint32_t*>(dev + o_words);
-  g.event_cap = n_ev;
-  g.read_key = keys ? reinterpret_cast<const int32_t*>(dev + o_keys) : nullptr;
-  g.ref = dev + o_ref;
-  g.interval_start = o->interval_start;
-  g.len = static_cast<int32_t>(len);
-  g.lo = gv->left_padding;
-  g.hi = static_cast<int32_t>(len - gv->right_padding);
-  g.scratch = reinterpret_cast<int32_t*>(dev + o_scr);
-  g.blocks = reinterpret_cast<dv_gvcf_block*>(dev + o_blk);
-  g.n_blocks = reinterpret_cast<int32_t*>(dev + o_words + 4);
-  std::memcpy(img.data() + o_desc, &g, sizeof(g));
-  std::memcpy(img.data() + o_words, &n_ev, 4);
-  const int32_t* cnt = c->ref_count.ptr ? c->ref_count.ptr : c->empty_counts.data();
-  if (len) std::memcpy(img.data() + o_cnt, cnt, static_cast<size_t>(len) * 4);
-  if (n_ev) std::memcpy(img.data() + o_ev, c->events.data(), static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
-  std::memcpy(img.data() + o_ref, o->ref_bases + (o->interval_start - o->ref_start), static_cast<size_t>(len));
-  if (n_keys) std::memcpy(img.data() + o_keys, keys, n_keys * 4);
-  DV_HIP_CHECK(hipMemcpyAsync(dev, img.data(), up_bytes, hipMemcpyHostToDevice, stream));
-  DV_HIP_CHECK(hipMemsetAsync(dev + o_scr, 0, o_blk - o_scr, stream));
-  if (int rc = dv::gvcf_launch(reinterpret_cast<const dv::GvcfRegion*>(dev + o_desc), 1, len, n_ev, gv, d_table, nullptr,
-                               stream)) {
+  static thread_local CountsBuffers buf;
+  CountsImage im = lay_counts_image(sizeof(dv::GvcfRegion), c, b, keys);
+  const size_t up_bytes = im.lay.bytes();
+  const size_t o_scr = im.lay.add(dv::gvcf_scratch_ints(im.len, im.n_ev) * sizeof(int32_t));
+  const size_t o_blk = im.lay.add_last(static_cast<size_t>(im.len - gv->left_padding - gv->right_padding) * sizeof(dv_gvcf_block));
+  if (int rc = buf.stage.reserve(up_bytes)) return rc;
+  if (int rc = buf.d_img.reserve_on_current_device(im.lay.bytes())) return rc;
+  uint8_t* dev = static_cast<uint8_t*>(buf.d_img.ptr);
+  const CountsOnDevice counts = stage_counts(im, c, o, keys, buf.stage.ptr, dev);
+  const dv::GvcfRegion g = gvcf_region(counts, gv, at<int32_t>(dev, o_scr), at<dv_gvcf_block>(dev, o_blk),
+                                       at<int32_t>(dev, im.words + 4));
+  std::memcpy(buf.stage.ptr + im.desc, &g, sizeof(g));
+  if (int rc = upload_counts_image(buf, up_bytes, o_scr, o_blk - o_scr, stream)) return rc;
+  if (int rc = dv::gvcf_launch(at<const dv::GvcfRegion>(dev, im.desc), 1, im.len, im.n_ev, gv, d_table, nullptr, stream)) {
     return rc;
   }
   int32_t n_blocks = 0;
-  DV_HIP_CHECK(hipMemcpyAsync(&n_blocks, dev + o_words + 4, 4, hipMemcpyDeviceToHost, stream));
-  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int rc = download_record_counts(buf, im, &n_blocks, 1, stream)) return rc;
   auto res = std::make_unique<dv_gvcf_blocks>();
   res->blocks.resize(static_cast<size_t>(n_blocks));
   if (n_blocks) {
@@ -533,90 +600,48 @@ int gvcf_from_counts(const dv_allele_counts* c, const dv_allele_counter_options*
   return DV_OK;
 }
 
-// The candidate pass over counts that are already on the host (a region that took the one-region path),
-// as gvcf_from_counts: the counts and sorted events go back up and through the same kernels, so the
-// event words come back in the order of dv_allele_counts_arrays.  Two synchronisations; the rare path.
+// The candidate pass over a region's host counts, so that the event words come back in the order of
+// dv_allele_counts_arrays.  A host-resident read table's offsets and bases go up with the image; a device-resident
+// one is read where it lies.  The records land in the result's pageable vectors: the synchronisation at the end
+// follows the copies.
 int candidates_from_counts(const dv_allele_counts* c, const dv_allele_counter_options* o, const dv_batch* b,
                            const int32_t* keys, const dv_candidate_options* co, hipStream_t stream,
                            dv_candidates** out) {
-  static thread_local dv::DeviceBuffer d_img;
+  static thread_local CountsBuffers buf;
   auto res = std::make_unique<dv_candidates>();
-  const int64_t len = c->length;
-  if (len == 0) {
+  if (c->length == 0) {
     *out = res.release();
     return DV_OK;
   }
-  if (len > 0x7fffffff - 2) return dv::fail(DV_ERR_INVALID_ARGUMENT, "interval too long for the candidate pass");
-  const uint32_t n_ev = static_cast<uint32_t>(c->events.size());
+  if (c->length > 0x7fffffff - 2) return dv::fail(DV_ERR_INVALID_ARGUMENT, "interval too long for the candidate pass");
+  CountsImage im = lay_counts_image(sizeof(dv::CandRegion), c, b, keys);
   const size_t n_reads = static_cast<size_t>(b->n_reads);
-  const size_t n_keys = keys ? n_reads : 0;
   const bool table_on_host = b->memory == DV_MEM_HOST && n_reads > 0;
-  // image: descriptor | n_events, n_sites, n_alleles | ref_count | events | ref | keys | seq_off | bases |
-  //        scratch | sites | alleles | words
-  size_t at = 0;
-  const size_t o_desc = at;
-  at += align16(sizeof(dv::CandRegion));
-  const size_t o_words = at;
-  at += 16;
-  const size_t o_cnt = at;
-  at += align16(static_cast<size_t>(len) * 4);
-  const size_t o_ev = at;
-  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
-  const size_t o_ref = at;
-  at += align16(static_cast<size_t>(len));
-  const size_t o_keys = at;
-  at += align16(n_keys * 4);
-  const size_t o_seq = at;
-  if (table_on_host) at += align16((n_reads + 1) * 4);
-  const size_t o_bases = at;
-  if (table_on_host) at += align16(b->n_bases);
-  const size_t up_bytes = at;
-  const size_t o_scr = at;
-  at += align16(dv::cand_scratch_ints(len, n_ev) * 4);
-  const size_t o_site = at;
-  at += align16(static_cast<size_t>(len) * sizeof(dv_candidate_site));
-  const size_t o_all = at;
-  at += align16(static_cast<size_t>(n_ev) * sizeof(dv_candidate_allele));
-  const size_t o_evw = at;
-  at += align16(static_cast<size_t>(n_ev) * 4);
-  if (int rc = d_img.reserve_on_current_device(at)) return rc;
-  uint8_t* dev = static_cast<uint8_t*>(d_img.ptr);
-  std::vector<uint8_t> img(up_bytes, 0);
-  dv::CandRegion g{};
-  g.ref_count = reinterpret_cast<const int32_t*>(dev + o_cnt);
-  g.events = reinterpret_cast<const dv_allele_event*>(dev + o_ev);
-  g.n_events = reinterpret_cast<const uint32_t*>(dev + o_words);
-  g.event_cap = n_ev;
-  g.read_key = keys ? reinterpret_cast<const int32_t*>(dev + o_keys) : nullptr;
-  g.ref = dev + o_ref;
-  g.bases = table_on_host ? dev + o_bases : b->bases;
-  g.seq_off = table_on_host ? reinterpret_cast<const uint32_t*>(dev + o_seq) : b->read_seq_off;
-  g.len = static_cast<int32_t>(len);
-  g.scratch = reinterpret_cast<int32_t*>(dev + o_scr);
-  g.sites = reinterpret_cast<dv_candidate_site*>(dev + o_site);
-  g.alleles = reinterpret_cast<dv_candidate_allele*>(dev + o_all);
-  g.words = reinterpret_cast<int32_t*>(dev + o_evw);
-  g.n_out = reinterpret_cast<int32_t*>(dev + o_words + 4);
-  std::memcpy(img.data() + o_desc, &g, sizeof(g));
-  std::memcpy(img.data() + o_words, &n_ev, 4);
-  const int32_t* cnt = c->ref_count.ptr ? c->ref_count.ptr : c->empty_counts.data();
-  std::memcpy(img.data() + o_cnt, cnt, static_cast<size_t>(len) * 4);
-  if (n_ev) std::memcpy(img.data() + o_ev, c->events.data(), static_cast<size_t>(n_ev) * sizeof(dv_allele_event));
-  std::memcpy(img.data() + o_ref, o->ref_bases + (o->interval_start - o->ref_start), static_cast<size_t>(len));
-  if (n_keys) std::memcpy(img.data() + o_keys, keys, n_keys * 4);
+  const size_t o_seq = table_on_host ? im.lay.add((n_reads + 1) * sizeof(uint32_t)) : 0;
+  const size_t o_bases = table_on_host ? im.lay.add(b->n_bases) : 0;
+  const size_t up_bytes = im.lay.bytes();
+  const size_t o_scr = im.lay.add(dv::cand_scratch_ints(im.len, im.n_ev) * sizeof(int32_t));
+  const size_t o_site = im.lay.add(static_cast<size_t>(im.len) * sizeof(dv_candidate_site));
+  const size_t o_all = im.lay.add(static_cast<size_t>(im.n_ev) * sizeof(dv_candidate_allele));
+  const size_t o_evw = im.lay.add(static_cast<size_t>(im.n_ev) * sizeof(int32_t));
+  if (int rc = buf.stage.reserve(up_bytes)) return rc;
+  if (int rc = buf.d_img.reserve_on_current_device(im.lay.bytes())) return rc;
+  uint8_t* dev = static_cast<uint8_t*>(buf.d_img.ptr);
+  const CountsOnDevice counts = stage_counts(im, c, o, keys, buf.stage.ptr, dev);
   if (table_on_host) {
-    std::memcpy(img.data() + o_seq, b->read_seq_off, (n_reads + 1) * 4);
-    std::memcpy(img.data() + o_bases, b->bases, b->n_bases);
+    std::memcpy(buf.stage.ptr + o_seq, b->read_seq_off, (n_reads + 1) * sizeof(uint32_t));
+    std::memcpy(buf.stage.ptr + o_bases, b->bases, b->n_bases);
   }
-  DV_HIP_CHECK(hipMemcpyAsync(dev, img.data(), up_bytes, hipMemcpyHostToDevice, stream));
-  DV_HIP_CHECK(hipMemsetAsync(dev + o_scr, 0, o_site - o_scr, stream));
-  if (int rc = dv::cand_launch(reinterpret_cast<const dv::CandRegion*>(dev + o_desc), 1, n_ev, co, nullptr, nullptr,
-                               stream)) {
-    return rc;
-  }
+  const dv::CandRegion g = cand_region(counts, table_on_host ? dev + o_bases : b->bases,
+                                       table_on_host ? at<const uint32_t>(dev, o_seq) : b->read_seq_off,
+                                       at<int32_t>(dev, o_scr), at<dv_candidate_site>(dev, o_site),
+                                       at<dv_candidate_allele>(dev, o_all), at<int32_t>(dev, o_evw),
+                                       at<int32_t>(dev, im.words + 4));
+  std::memcpy(buf.stage.ptr + im.desc, &g, sizeof(g));
+  if (int rc = upload_counts_image(buf, up_bytes, o_scr, o_site - o_scr, stream)) return rc;
+  if (int rc = dv::cand_launch(at<const dv::CandRegion>(dev, im.desc), 1, im.n_ev, co, nullptr, nullptr, stream)) return rc;
   int32_t n_out[2] = {0, 0};
-  DV_HIP_CHECK(hipMemcpyAsync(n_out, dev + o_words + 4, 8, hipMemcpyDeviceToHost, stream));
-  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  if (int rc = download_record_counts(buf, im, n_out, 2, stream)) return rc;
   res->sites.resize(static_cast<size_t>(n_out[0]));
   if (n_out[0]) {
     DV_HIP_CHECK(hipMemcpyAsync(res->sites.data(), dev + o_site, res->sites.size() * sizeof(dv_candidate_site),
@@ -624,15 +649,364 @@ int candidates_from_counts(const dv_allele_counts* c, const dv_allele_counter_op
   }
   if (!co->positions_only) {
     res->alleles.resize(static_cast<size_t>(n_out[1]));
-    res->words.resize(n_ev);
+    res->words.resize(im.n_ev);
     if (n_out[1]) {
       DV_HIP_CHECK(hipMemcpyAsync(res->alleles.data(), dev + o_all, res->alleles.size() * sizeof(dv_candidate_allele),
                                   hipMemcpyDeviceToHost, stream));
     }
-    if (n_ev) DV_HIP_CHECK(hipMemcpyAsync(res->words.data(), dev + o_evw, static_cast<size_t>(n_ev) * 4, hipMemcpyDeviceToHost, stream));
+    if (im.n_ev) {
+      DV_HIP_CHECK(hipMemcpyAsync(res->words.data(), dev + o_evw, static_cast<size_t>(im.n_ev) * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, stream));
+    }
   }
   DV_HIP_CHECK(hipStreamSynchronize(stream));
   *out = res.release();
+  return DV_OK;
+}
+
+// ---- the batch entry point's steps, in the order count_batch takes them
+
+// What one call asked for.
+struct BatchRequest {
+  int32_t n;
+  const dv_batch* const* reads;
+  const dv_allele_counter_options* const* options;
+  const int32_t* const* read_keys;
+  const dv_gvcf_options* gv;           // null: no gVCF pass
+  const dv_candidate_options* co;      // null: no candidate pass
+  bool pos_only;                       // positions only: neither counts nor events come back
+  hipStream_t stream;
+  const char* who;
+  const int32_t* keys_of(int32_t k) const { return read_keys ? read_keys[k] : nullptr; }
+};
+
+// The caller's result arrays.  Until release() every result in them is this guard's: on an error exit -- the
+// DV_HIP_CHECK returns included -- none is left allocated and every entry is null.  With positions_only the
+// counts of a region that went alone live in own_out and never reach the caller.
+struct BatchResults {
+  int32_t n = 0;
+  dv_allele_counts** out = nullptr;
+  dv_gvcf_blocks** gout = nullptr;     // null without the pass
+  dv_candidates** cout = nullptr;
+  std::vector<dv_allele_counts*> own_out;
+  bool released = false;
+
+  void take(int32_t count, dv_allele_counts** counts, dv_gvcf_blocks** blocks, dv_candidates** candidates) {
+    n = count, out = counts, gout = blocks, cout = candidates;
+    for (int32_t k = 0; k < n; ++k) {
+      out[k] = nullptr;
+      if (gout) gout[k] = nullptr;
+      if (cout) cout[k] = nullptr;
+    }
+  }
+  void release() { released = true; }
+  template <class T> static void drop(T*& p) {
+    delete p;
+    p = nullptr;
+  }
+  ~BatchResults() {
+    for (int32_t k = 0; k < n; ++k) {
+      if (!released || !own_out.empty()) drop(out[k]);
+      if (!released && gout) drop(gout[k]);
+      if (!released && cout) drop(cout[k]);
+    }
+  }
+};
+
+// Everything that can be refused before any device work; hands the result arrays to `results`.
+int check_batch(const BatchRequest& rq, dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout,
+                BatchResults* results) {
+  const std::string name(rq.who);
+  const int32_t n = rq.n;
+  if (rq.pos_only && n > 0) {
+    results->own_out.assign(static_cast<size_t>(n), nullptr);
+    out = results->own_out.data();
+  }
+  if (n < 0 || (n > 0 && (!rq.reads || !rq.options || !out || (rq.gv && !gout) || (rq.co && !cout)))) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
+  }
+  results->take(n, out, rq.gv ? gout : nullptr, rq.co ? cout : nullptr);
+  if (rq.gv) {
+    if (int rc = dv::gvcf_check_options(rq.gv, rq.who)) return rc;
+  }
+  if (rq.co) {
+    if (int rc = dv::cand_check_options(rq.co, rq.who)) return rc;
+    if (rq.pos_only && rq.gv) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": positions_only excludes the gVCF pass");
+  }
+  for (int32_t k = 0; k < n; ++k) {
+    const dv_allele_counter_options* o = rq.options[k];
+    if (rq.gv) {   // before check_request: bad input is reported as such with or without a device
+      if (int rc = dv::gvcf_check_region(o, rq.gv, rq.who)) return rc;
+    }
+    if (int rc = check_request(rq.reads[k], o, &out[k], rq.who)) return rc;
+    if (o->track_ref_reads && o->n_candidate_positions > 0 && !o->candidate_positions) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": candidate_positions is null");
+    }
+    if (rq.co && o->interval_end - o->interval_start > 0x7fffffff - 2) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": interval too long for the candidate pass");
+    }
+  }
+  return DV_OK;
+}
+
+// One host thread's grow-only buffers: pinned staging both ways and the device images.
+struct BatchBuffers {
+  dv::PinnedStage h_up, h_down, h_second;
+  dv::DeviceBuffer d_up, d_res, d_ev;
+  dv::DeviceBuffer d_gscr, d_gblk, d_gpack;                              // gVCF: scratch, records, packed records
+  dv::DeviceBuffer d_cscr, d_csite, d_call, d_cword, d_cpsite, d_cpall;  // candidates: scratch, sites, alleles, words, packed
+
+  // everything but h_second, whose size the first download tells
+  int reserve(const dv::BatchPlan& p) {
+    const size_t sites = std::max<size_t>(p.cnt_ints, 1), evs = std::max<size_t>(p.ev_total, 1);
+    if (int rc = h_up.reserve(p.up_bytes)) return rc;
+    if (int rc = h_down.reserve(p.res_bytes)) return rc;
+    if (int rc = d_up.reserve_on_current_device(p.up_bytes)) return rc;
+    if (int rc = d_res.reserve_on_current_device(p.res_bytes)) return rc;
+    if (int rc = d_ev.reserve_on_current_device(evs * sizeof(dv_allele_event))) return rc;
+    if (p.gv.n) {
+      const size_t blocks = std::max<size_t>(p.gv.blocks, 1);
+      if (int rc = d_gscr.reserve_on_current_device(p.gv.scratch_ints * sizeof(int32_t))) return rc;
+      if (int rc = d_gblk.reserve_on_current_device(blocks * sizeof(dv_gvcf_block))) return rc;
+      if (int rc = d_gpack.reserve_on_current_device(blocks * sizeof(dv_gvcf_block))) return rc;
+    }
+    if (p.cd.n) {
+      if (int rc = d_cscr.reserve_on_current_device(std::max<size_t>(p.cd.scratch_ints, 1) * sizeof(int32_t))) return rc;
+      if (int rc = d_csite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
+      if (int rc = d_cpsite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
+      if (int rc = d_call.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
+      if (int rc = d_cpall.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
+      if (int rc = d_cword.reserve_on_current_device(evs * sizeof(int32_t))) return rc;
+    }
+    return DV_OK;
+  }
+};
+
+// Region k's arrays into the staging image, and its descriptors for the passes it is in: they point into the
+// device images, at the counts, events and reference the counter uses.
+void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, const BatchBuffers& buf) {
+  const dv::RegionPlan& p = plan.regions[k];
+  const dv_batch* b = rq.reads[k];
+  const dv_allele_counter_options* o = rq.options[k];
+  const size_t nr = static_cast<size_t>(b->n_reads);
+  uint8_t* host = buf.h_up.ptr;
+  std::memcpy(host + p.up.read_pos, b->read_pos, nr * 4);
+  std::memcpy(host + p.up.seq_off, b->read_seq_off, (nr + 1) * 4);
+  std::memcpy(host + p.up.cigar_off, b->read_cigar_off, (nr + 1) * 4);
+  std::memcpy(host + p.up.mapq, b->read_mapq, nr);
+  std::memcpy(host + p.up.bases, b->bases, b->n_bases);
+  std::memcpy(host + p.up.quals, b->quals, b->n_bases);
+  std::memcpy(host + p.up.cigar, b->cigar, static_cast<size_t>(b->n_cigar) * 4);
+  std::memcpy(host + p.up.ref, o->ref_bases, static_cast<size_t>(o->n_ref_bases));
+  if (p.mask_words) build_candidate_mask(o, p.len, at<uint32_t>(host, p.up.mask));
+  if (p.has_keys) std::memcpy(host + p.up.keys, rq.keys_of(k), nr * 4);
+  if (p.gv.slot < 0 && p.cd.slot < 0) return;
+  void* dup = buf.d_up.ptr;
+  const CountsOnDevice c{at<const int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off,
+                         static_cast<const dv_allele_event*>(buf.d_ev.ptr) + p.ev_off,
+                         at<const uint32_t>(buf.d_res.ptr, plan.counters_at) + static_cast<size_t>(k) * 4, p.cap,
+                         p.has_keys ? at<const int32_t>(dup, p.up.keys) : nullptr,
+                         at<const uint8_t>(dup, p.up.ref) + (o->interval_start - o->ref_start), o->interval_start, p.len};
+  if (p.cd.slot >= 0) {
+    const dv::CandRegion g = cand_region(
+        c, at<const uint8_t>(dup, p.up.bases), at<const uint32_t>(dup, p.up.seq_off),
+        static_cast<int32_t*>(buf.d_cscr.ptr) + p.cd.scratch_off, static_cast<dv_candidate_site*>(buf.d_csite.ptr) + p.cnt_off,
+        static_cast<dv_candidate_allele*>(buf.d_call.ptr) + p.ev_off, static_cast<int32_t*>(buf.d_cword.ptr) + p.ev_off,
+        at<int32_t>(buf.d_res.ptr, plan.n_cand_at) + static_cast<size_t>(k) * 2);
+    std::memcpy(host + plan.cd.desc_up + static_cast<size_t>(p.cd.slot) * sizeof(g), &g, sizeof(g));
+  }
+  if (p.gv.slot >= 0) {
+    const dv::GvcfRegion g = gvcf_region(c, rq.gv, static_cast<int32_t*>(buf.d_gscr.ptr) + p.gv.scratch_off,
+                                         static_cast<dv_gvcf_block*>(buf.d_gblk.ptr) + p.gv.block_off,
+                                         at<int32_t>(buf.d_res.ptr, plan.n_blocks_at) + k);
+    std::memcpy(host + plan.gv.desc_up + static_cast<size_t>(p.gv.slot) * sizeof(g), &g, sizeof(g));
+  }
+}
+
+// The counting kernel's arguments for region k of the batch.
+CountArgs batch_count_args(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, const BatchBuffers& buf) {
+  const dv::RegionPlan& p = plan.regions[k];
+  void* dup = buf.d_up.ptr;
+  CountArgs a = fill_count_args(rq.reads[k], rq.options[k], p.len);
+  a.read_pos = at<const int32_t>(dup, p.up.read_pos);
+  a.seq_off = at<const uint32_t>(dup, p.up.seq_off);
+  a.cigar_off = at<const uint32_t>(dup, p.up.cigar_off);
+  a.mapq = at<const uint8_t>(dup, p.up.mapq);
+  a.bases = at<const uint8_t>(dup, p.up.bases);
+  a.quals = at<const uint8_t>(dup, p.up.quals);
+  a.cigar = at<const uint32_t>(dup, p.up.cigar);
+  a.ref = at<const uint8_t>(dup, p.up.ref);
+  a.candidate_mask = p.mask_words ? at<const uint32_t>(dup, p.up.mask) : nullptr;
+  a.counters = at<uint32_t>(buf.d_res.ptr, plan.counters_at) + static_cast<size_t>(k) * 4;
+  a.ref_count = at<int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off;
+  a.events = static_cast<dv_allele_event*>(buf.d_ev.ptr) + p.ev_off;
+  a.event_cap = p.cap;
+  return a;
+}
+
+// One upload, the counting kernels back to back, the passes behind them; no synchronisation.
+int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const BatchBuffers& buf,
+                     const dv_gvcf_site** d_table) {
+  hipStream_t stream = rq.stream;
+  for (int32_t k = 0; k < rq.n; ++k) {
+    if (plan.regions[k].batched) stage_region(rq, plan, k, buf);
+  }
+  DV_HIP_CHECK(hipMemcpyAsync(buf.d_up.ptr, buf.h_up.ptr, plan.up_bytes, hipMemcpyHostToDevice, stream));
+  DV_HIP_CHECK(hipMemsetAsync(buf.d_res.ptr, 0, plan.res_bytes, stream));
+  if (plan.gv.n) {
+    DV_HIP_CHECK(hipMemsetAsync(buf.d_gscr.ptr, 0, plan.gv.scratch_ints * sizeof(int32_t), stream));
+    if (int rc = dv::gvcf_table_on_device(rq.gv, d_table, stream)) return rc;
+  }
+  if (plan.cd.n) DV_HIP_CHECK(hipMemsetAsync(buf.d_cscr.ptr, 0, plan.cd.scratch_ints * sizeof(int32_t), stream));
+  for (int32_t k = 0; k < rq.n; ++k) {
+    if (plan.regions[k].batched) launch_count(batch_count_args(rq, plan, k, buf), rq.reads[k]->n_reads, stream);
+  }
+  DV_HIP_CHECK(hipGetLastError());
+  if (plan.gv.n) {
+    // the reference-confidence pass reads the counts where the kernels above leave them
+    if (int rc = dv::gvcf_launch(at<const dv::GvcfRegion>(buf.d_up.ptr, plan.gv.desc_up), plan.gv.n, plan.gv.max_len,
+                                 plan.max_cap, rq.gv, *d_table, static_cast<dv_gvcf_block*>(buf.d_gpack.ptr), stream)) {
+      return rc;
+    }
+  }
+  if (plan.cd.n) {
+    // the candidate caller reads the same counts and events, and the read bases the events point into
+    if (int rc = dv::cand_launch(at<const dv::CandRegion>(buf.d_up.ptr, plan.cd.desc_up), plan.cd.n, plan.max_cap, rq.co,
+                                 static_cast<dv_candidate_site*>(buf.d_cpsite.ptr),
+                                 static_cast<dv_candidate_allele*>(buf.d_cpall.ptr), stream)) {
+      return rc;
+    }
+  }
+  return DV_OK;
+}
+
+// The result image comes home -- with positions_only its counters and record counts only -- and the stream is waited
+// for: the events follow once their numbers are known.
+int download_first(const BatchRequest& rq, const dv::BatchPlan& plan, const BatchBuffers& buf) {
+  if (rq.pos_only) {
+    DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr, buf.d_res.ptr, plan.counts_at, hipMemcpyDeviceToHost, rq.stream));
+    DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr + plan.n_cand_at, at<uint8_t>(buf.d_res.ptr, plan.n_cand_at),
+                                plan.res_bytes - plan.n_cand_at, hipMemcpyDeviceToHost, rq.stream));
+  } else {
+    DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr, buf.d_res.ptr, plan.res_bytes, hipMemcpyDeviceToHost, rq.stream));
+  }
+  DV_HIP_CHECK(hipStreamSynchronize(rq.stream));
+  return DV_OK;
+}
+
+// The results of the regions the batch answers, sized from the first download.
+int allocate_results(const BatchRequest& rq, const dv::BatchPlan& plan, const dv::SecondImage& second,
+                     const BatchBuffers& buf, BatchResults* results) {
+  const uint32_t* counters = at<const uint32_t>(buf.h_down.ptr, plan.counters_at);
+  const int32_t* counts = at<const int32_t>(buf.h_down.ptr, plan.counts_at);
+  for (int32_t k = 0; k < rq.n; ++k) {
+    const dv::RegionPlan& p = plan.regions[k];
+    const dv::SecondImage::Region& r = second.regions[k];
+    if (p.batched && counters[4 * k + 2] != 0) return window_too_small();
+    if (!r.kept) continue;           // the first guess was too small: this region goes alone (two passes there)
+    if (rq.co) {
+      results->cout[k] = new dv_candidates();
+      results->cout[k]->sites.resize(r.n_sites);
+      if (!rq.pos_only) results->cout[k]->alleles.resize(r.n_alleles);
+    }
+    if (rq.pos_only) continue;
+    auto res = std::make_unique<dv_allele_counts>();
+    res->length = p.len;
+    res->n_reads_counted = static_cast<int32_t>(counters[4 * k + 1]);
+    if (int rc = res->ref_count.reserve(static_cast<size_t>(p.len))) return rc;
+    std::memcpy(res->ref_count.ptr, counts + p.cnt_off, static_cast<size_t>(p.len) * sizeof(int32_t));
+    if (int rc = res->raw.reserve(r.n_events)) return rc;
+    results->out[k] = res.release();
+    if (rq.gv) {
+      results->gout[k] = new dv_gvcf_blocks();
+      results->gout[k]->blocks.resize(r.n_blocks);
+    }
+  }
+  return DV_OK;
+}
+
+// The events and event words of every kept region and the packed records of every region into one pinned image,
+// one synchronisation.
+int download_second(const BatchRequest& rq, const dv::BatchPlan& plan, const dv::SecondImage& second, BatchBuffers* buf) {
+  if (int rc = buf->h_second.reserve(second.bytes)) return rc;
+  uint8_t* host = buf->h_second.ptr;
+  hipStream_t stream = rq.stream;
+  for (int32_t k = 0; k < rq.n; ++k) {
+    const dv::SecondImage::Region& r = second.regions[k];
+    if (!r.kept || r.n_events == 0) continue;
+    const size_t ev_off = plan.regions[k].ev_off;
+    DV_HIP_CHECK(hipMemcpyAsync(host + r.events_at, static_cast<const dv_allele_event*>(buf->d_ev.ptr) + ev_off,
+                                r.n_events * sizeof(dv_allele_event), hipMemcpyDeviceToHost, stream));
+    if (rq.co) {
+      DV_HIP_CHECK(hipMemcpyAsync(host + r.words_at, static_cast<const int32_t*>(buf->d_cword.ptr) + ev_off,
+                                  r.n_events * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    }
+  }
+  if (second.packed_sites) {
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.sites_at, buf->d_cpsite.ptr, second.packed_sites * sizeof(dv_candidate_site),
+                                hipMemcpyDeviceToHost, stream));
+  }
+  if (second.packed_alleles && !rq.pos_only) {
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.alleles_at, buf->d_cpall.ptr,
+                                second.packed_alleles * sizeof(dv_candidate_allele), hipMemcpyDeviceToHost, stream));
+  }
+  if (second.packed_blocks) {
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.blocks_at, buf->d_gpack.ptr, second.packed_blocks * sizeof(dv_gvcf_block),
+                                hipMemcpyDeviceToHost, stream));
+  }
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  return DV_OK;
+}
+
+// Out of the second image into the kept regions' results; the events are put in order.
+void unpack(const BatchRequest& rq, const dv::SecondImage& second, const BatchBuffers& buf, BatchResults* results) {
+  const uint8_t* host = buf.h_second.ptr;
+  for (int32_t k = 0; k < rq.n; ++k) {
+    const dv::SecondImage::Region& r = second.regions[k];
+    if (!r.kept) continue;
+    if (rq.co) {
+      dv_candidates* cand = results->cout[k];
+      if (r.n_sites) std::memcpy(cand->sites.data(), host + r.sites_at, r.n_sites * sizeof(dv_candidate_site));
+      if (r.n_alleles && !rq.pos_only) {
+        std::memcpy(cand->alleles.data(), host + r.alleles_at, r.n_alleles * sizeof(dv_candidate_allele));
+      }
+    }
+    if (rq.pos_only) continue;
+    dv_allele_counts* counts = results->out[k];
+    if (r.n_events) std::memcpy(counts->raw.ptr, host + r.events_at, r.n_events * sizeof(dv_allele_event));
+    if (rq.co) {
+      order_events_with_words(counts, r.n_events, reinterpret_cast<const int32_t*>(host + r.words_at),
+                              &results->cout[k]->words);
+    } else {
+      order_events(counts, r.n_events);
+    }
+    if (rq.gv && r.n_blocks) {
+      std::memcpy(results->gout[k]->blocks.data(), host + r.blocks_at, r.n_blocks * sizeof(dv_gvcf_block));
+    }
+  }
+}
+
+// The regions the batch did not answer, one by one: the one-region entry, then each pass from its counts.
+int run_alone(const BatchRequest& rq, const dv::SecondImage& second, const dv_gvcf_site* d_table, BatchResults* results) {
+  for (int32_t k = 0; k < rq.n; ++k) {
+    if (second.regions[k].kept) continue;
+    if (int rc = dv_count_alleles(rq.reads[k], rq.options[k], &results->out[k], rq.stream)) return rc;
+    if (rq.co) {
+      if (int rc = candidates_from_counts(results->out[k], rq.options[k], rq.reads[k], rq.keys_of(k), rq.co, rq.stream,
+                                          &results->cout[k])) {
+        return rc;
+      }
+    }
+    if (rq.gv) {
+      if (!d_table) {
+        if (int rc = dv::gvcf_table_on_device(rq.gv, &d_table, rq.stream)) return rc;
+      }
+      if (int rc = gvcf_from_counts(results->out[k], rq.options[k], rq.reads[k], rq.keys_of(k), rq.gv, d_table, rq.stream,
+                                    &results->gout[k])) {
+        return rc;
+      }
+    }
+  }
   return DV_OK;
 }
 
@@ -642,8 +1016,6 @@ extern "C" {
 
 int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_allele_counts** out, void* stream_v) {
   if (int rc = check_request(b, o, out, "dv_count_alleles")) return rc;
-  const int64_t reads_start = std::min(o->interval_start, o->reads_interval_start);
-  const int64_t reads_end = std::max(o->interval_end, o->reads_interval_end);
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const int64_t len = o->interval_end - o->interval_start;
   auto res = std::make_unique<dv_allele_counts>();
@@ -659,8 +1031,7 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
   // ... and so are the upload buffers of a host-resident table: seven hipMalloc + hipFree per call
   // were most of the millisecond a 300-read region took (the kernel itself is a few microseconds)
   static thread_local dv::DeviceBuffer up[7];
-  CountArgs a{};
-  a.n_reads = b->n_reads;
+  CountArgs a = fill_count_args(b, o, len);
   const size_t n = static_cast<size_t>(b->n_reads);
   if (int rc = to_device(up[0], b->read_pos, n, b->memory, &a.read_pos, stream)) return rc;
   if (int rc = to_device(up[1], b->read_seq_off, n + 1, b->memory, &a.seq_off, stream)) return rc;
@@ -673,37 +1044,22 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
   DV_HIP_CHECK(hipMemcpyAsync(d_ref.ptr, o->ref_bases, static_cast<size_t>(o->n_ref_bases), hipMemcpyHostToDevice,
                               stream));
   a.ref = static_cast<const uint8_t*>(d_ref.ptr);
-  a.ref_start = o->ref_start;
-  a.n_ref = o->n_ref_bases;
-  a.reads_start = reads_start;
-  a.reads_end = reads_end;
-  a.interval_start = o->interval_start;
-  a.interval_len = len;
-  a.contig_len = o->contig_n_bases > 0 ? o->contig_n_bases : o->ref_start + o->n_ref_bases;
-  a.min_mapq = o->min_mapping_quality;
-  a.min_bq = o->min_base_quality;
-  a.legacy = o->keep_legacy_behavior ? 1 : 0;
-  size_t n_candidate_refs = 0;
-  if (o->track_ref_reads && o->n_candidate_positions > 0) {
+  const size_t n_candidate_refs = dv::n_candidate_refs(o);
+  if (n_candidate_refs) {
     if (!o->candidate_positions) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles: candidate_positions is null");
-    std::vector<uint32_t> mask(static_cast<size_t>((len + 31) / 32), 0u);
-    for (int32_t k = 0; k < o->n_candidate_positions; ++k) {
-      const int64_t p = o->candidate_positions[k] - o->interval_start;
-      if (p >= 0 && p < len) mask[static_cast<size_t>(p >> 5)] |= 1u << (p & 31);
-    }
+    std::vector<uint32_t> mask(dv::mask_words(len));
+    build_candidate_mask(o, len, mask.data());
     if (int rc = d_mask.reserve_on_current_device(mask.size() * sizeof(uint32_t))) return rc;
     DV_HIP_CHECK(hipMemcpyAsync(d_mask.ptr, mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    DV_HIP_CHECK(hipStreamSynchronize(stream));      // `mask` is a local
+    DV_HIP_CHECK(hipStreamSynchronize(stream));      // `mask` is a local: the copy must have read it before it goes
     a.candidate_mask = static_cast<const uint32_t*>(d_mask.ptr);
-    n_candidate_refs = static_cast<size_t>(o->n_candidate_positions);
   }
   if (int rc = d_cnt.reserve_on_current_device(static_cast<size_t>(len) * sizeof(int32_t))) return rc;
   if (int rc = d_ctr.reserve_on_current_device(4 * sizeof(uint32_t))) return rc;
   a.ref_count = static_cast<int32_t*>(d_cnt.ptr);
   a.counters = static_cast<uint32_t*>(d_ctr.ptr);
-  // events: substitutions are a few per cent of the bases, indels at most one per CIGAR op;
   // the counter keeps counting past the capacity, so a second pass sizes it exactly
-  uint32_t cap = b->n_cigar + b->n_bases / 16 + 4096 + static_cast<uint32_t>(std::min<size_t>(n_candidate_refs * 64, 1u << 24));
+  uint32_t cap = dv::first_event_cap(b, n_candidate_refs);
   uint32_t ctr[4] = {0, 0, 0, 0};
   for (int pass = 0; pass < 2; ++pass) {
     if (int rc = d_ev.reserve_on_current_device(static_cast<size_t>(cap) * sizeof(dv_allele_event))) return rc;
@@ -711,21 +1067,14 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
     a.event_cap = cap;
     DV_HIP_CHECK(hipMemsetAsync(d_cnt.ptr, 0, static_cast<size_t>(len) * sizeof(int32_t), stream));
     DV_HIP_CHECK(hipMemsetAsync(d_ctr.ptr, 0, 4 * sizeof(uint32_t), stream));
-    {
-      dv::ProfileScope prof(dv::kProfOther, stream);
-      hipLaunchKernelGGL(count_alleles_kernel, dim3((b->n_reads + 4 * kReadsPerWave - 1) / (4 * kReadsPerWave)),
-                         dim3(256), 0, stream, a);
-    }
+    launch_count(a, b->n_reads, stream);
     DV_HIP_CHECK(hipGetLastError());
     DV_HIP_CHECK(hipMemcpyAsync(ctr, d_ctr.ptr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
     DV_HIP_CHECK(hipStreamSynchronize(stream));
     if (ctr[0] <= cap) break;
     cap = ctr[0];
   }
-  if (ctr[2] != 0) {
-    return dv::fail(DV_ERR_BAD_INPUT,
-                    "dv_count_alleles: an indel reaches outside the reference window (pass more margin)");
-  }
+  if (ctr[2] != 0) return window_too_small();
   res->n_reads_counted = static_cast<int32_t>(ctr[1]);
   if (int rc = res->ref_count.reserve(static_cast<size_t>(len))) return rc;
   if (int rc = res->raw.reserve(ctr[0])) return rc;
@@ -756,454 +1105,27 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
                        const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
                        dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout, void* stream_v,
                        const char* who) {
-  const std::string name(who);
-  const bool pos_only = co && co->positions_only;
-  // positions only: the one-region path's counts live here and go with the call
-  std::vector<dv_allele_counts*> own_out;
-  if (pos_only && n > 0) {
-    own_out.assign(static_cast<size_t>(n), nullptr);
-    out = own_out.data();
-  }
-  if (n < 0 || (n > 0 && (!reads || !options || !out || (gv && !gout) || (co && !cout)))) {
-    return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
-  }
-  for (int32_t k = 0; k < n; ++k) out[k] = nullptr;
-  if (gv) {
-    for (int32_t k = 0; k < n; ++k) gout[k] = nullptr;
-  }
-  if (co) {
-    for (int32_t k = 0; k < n; ++k) cout[k] = nullptr;
-  }
-  auto fail_all = [&](int rc) {
-    for (int32_t k = 0; k < n; ++k) {
-      delete out[k];
-      out[k] = nullptr;
-      if (gv) {
-        delete gout[k];
-        gout[k] = nullptr;
-      }
-      if (co) {
-        delete cout[k];
-        cout[k] = nullptr;
-      }
-    }
-    return rc;
-  };
-  if (gv) {
-    if (int rc = dv::gvcf_check_options(gv, who)) return rc;
-  }
-  if (co) {
-    if (int rc = dv::cand_check_options(co, who)) return rc;
-    if (pos_only && gv) return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": positions_only excludes the gVCF pass");
-  }
-  for (int32_t k = 0; k < n; ++k) {
-    if (gv) {   // before check_request: bad input is reported as such with or without a device
-      if (int rc = dv::gvcf_check_region(options[k], gv, who)) return rc;
-    }
-    if (int rc = check_request(reads[k], options[k], &out[k], who)) return rc;
-    if (options[k]->track_ref_reads && options[k]->n_candidate_positions > 0 && !options[k]->candidate_positions) {
-      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": candidate_positions is null");
-    }
-    if (co && options[k]->interval_end - options[k]->interval_start > 0x7fffffff - 2) {
-      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": interval too long for the candidate pass");
-    }
-  }
-  std::vector<char> done(static_cast<size_t>(n), 0);   // regions the batched path has answered
-  auto keys_of = [&](int32_t k) -> const int32_t* { return read_keys ? read_keys[k] : nullptr; };
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const BatchRequest rq{n, reads, options, read_keys, gv, co, co && co->positions_only, static_cast<hipStream_t>(stream_v), who};
+  BatchResults results;              // frees whatever it holds on every return but the last
+  if (int rc = check_batch(rq, out, gout, cout, &results)) return rc;
+  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, read_keys, gv, co);
+  dv::SecondImage second;            // of no region yet: which regions the batch has answered
+  second.regions.resize(plan.regions.size());
   const dv_gvcf_site* d_table = nullptr;
-  // Everything from here on may have results in out[]: the body runs as one callable so that EVERY error exit
-  // -- the DV_HIP_CHECK returns included -- passes through fail_all ("on an error no result is left allocated").
-  auto body = [&]() -> int {
-  struct Plan {
-    bool batched = false;
-    size_t up[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // staging offsets: read_pos, seq_off, cigar_off, mapq, bases, quals, cigar, ref, mask
-    size_t cnt_off = 0, ev_off = 0;              // in ints / events
-    int64_t len = 0;
-    uint32_t cap = 0;
-    size_t mask_words = 0;
-    size_t key_up = 0, scr_off = 0, blk_off = 0;  // gVCF: staging offset of the read keys, scratch ints, records
-    int gv_slot = -1;                             // gVCF: index among the batched regions
-    int cd_slot = -1;                             // candidates: likewise, and the region's scratch ints
-    size_t cscr_off = 0;
-  };
-  std::vector<Plan> plan(static_cast<size_t>(n));
-  size_t up_bytes = 0, cnt_ints = 0, ev_total = 0;
-  int n_batched = 0;
-  int n_gv = 0;                                  // gVCF: batched regions, their scratch and record totals
-  size_t scr_ints = 0, blk_total = 0;
-  int n_cd = 0;                                  // candidates: batched regions and their scratch total
-  size_t cscr_ints = 0;
-  int64_t max_len = 0;
-  uint32_t max_cap = 0;
-  for (int32_t k = 0; k < n; ++k) {
-    const dv_batch* b = reads[k];
-    const dv_allele_counter_options* o = options[k];
-    Plan& p = plan[k];
-    p.len = o->interval_end - o->interval_start;
-    if (b->n_reads == 0 || p.len == 0 || b->memory != DV_MEM_HOST) continue;     // one-region path below
-    p.batched = true;
-    ++n_batched;
-    const size_t nr = static_cast<size_t>(b->n_reads);
-    const size_t sizes[9] = {nr * 4, (nr + 1) * 4, (nr + 1) * 4, nr, b->n_bases, b->n_bases,
-                             static_cast<size_t>(b->n_cigar) * 4, static_cast<size_t>(o->n_ref_bases), 0};
-    for (int f = 0; f < 8; ++f) {
-      p.up[f] = up_bytes;
-      up_bytes += align16(std::max<size_t>(sizes[f], 1));
-    }
-    size_t n_candidate_refs = 0;
-    if (o->track_ref_reads && o->n_candidate_positions > 0) {
-      p.mask_words = static_cast<size_t>((p.len + 31) / 32);
-      p.up[8] = up_bytes;
-      up_bytes += align16(p.mask_words * 4);
-      n_candidate_refs = static_cast<size_t>(o->n_candidate_positions);
-    }
-    p.cnt_off = cnt_ints;
-    cnt_ints += static_cast<size_t>(p.len);
-    p.cap = b->n_cigar + b->n_bases / 16 + 4096 + static_cast<uint32_t>(std::min<size_t>(n_candidate_refs * 64, 1u << 24));
-    p.ev_off = ev_total;
-    ev_total += p.cap;
-    if ((gv || co) && keys_of(k)) {
-      p.key_up = up_bytes;
-      up_bytes += align16(nr * 4);
-    }
-    if (co) {
-      p.cd_slot = n_cd;
-      ++n_cd;
-      p.cscr_off = cscr_ints;
-      cscr_ints += dv::cand_scratch_ints(p.len, p.cap);
-      max_cap = std::max(max_cap, p.cap);
-    }
-    if (gv) {
-      p.gv_slot = n_gv;
-      ++n_gv;
-      p.scr_off = scr_ints;
-      scr_ints += dv::gvcf_scratch_ints(p.len, p.cap);
-      p.blk_off = blk_total;
-      blk_total += static_cast<size_t>(p.len - gv->left_padding - gv->right_padding);
-      max_len = std::max(max_len, p.len);
-      max_cap = std::max(max_cap, p.cap);
-    }
+  if (plan.n_batched > 0) {
+    static thread_local BatchBuffers buf;
+    if (int rc = buf.reserve(plan)) return rc;
+    if (int rc = stage_and_launch(rq, plan, buf, &d_table)) return rc;
+    if (int rc = download_first(rq, plan, buf)) return rc;
+    second = dv::second_image(plan, at<const uint32_t>(buf.h_down.ptr, plan.counters_at),
+                              at<const int32_t>(buf.h_down.ptr, plan.n_blocks_at),
+                              at<const int32_t>(buf.h_down.ptr, plan.n_cand_at), rq.pos_only);
+    if (int rc = allocate_results(rq, plan, second, buf, &results)) return rc;
+    if (int rc = download_second(rq, plan, second, &buf)) return rc;
+    unpack(rq, second, buf, &results);
   }
-  // gVCF: the batched regions' descriptors travel at the end of the staging image
-  const size_t desc_up = up_bytes;
-  if (n_gv) up_bytes += align16(static_cast<size_t>(n_gv) * sizeof(dv::GvcfRegion));
-  const size_t cdesc_up = up_bytes;
-  if (n_cd) up_bytes += align16(static_cast<size_t>(n_cd) * sizeof(dv::CandRegion));
-  if (n_batched > 0) {
-    // grow-only scratch per host thread: pinned staging both ways, device images
-    static thread_local PinnedBytes h_up, h_down;
-    static thread_local dv::DeviceBuffer d_up, d_res, d_ev;
-    static thread_local dv::DeviceBuffer d_gscr, d_gblk, d_gpack;
-    static thread_local dv::DeviceBuffer d_cscr, d_csite, d_call, d_cword, d_cpsite, d_cpall;
-    const size_t ctr_bytes = align16(static_cast<size_t>(n) * 4 * sizeof(uint32_t));
-    // gVCF: each region's record count follows the counts (and comes back with them)
-    const size_t nblk_off = align16(ctr_bytes + cnt_ints * sizeof(int32_t));
-    size_t res_bytes = gv ? nblk_off + static_cast<size_t>(n) * sizeof(int32_t) : ctr_bytes + cnt_ints * sizeof(int32_t);
-    // candidates: then each region's site and allele record counts
-    const size_t ncand_off = align16(res_bytes);
-    if (co) res_bytes = ncand_off + static_cast<size_t>(n) * 2 * sizeof(int32_t);
-    if (int rc = h_up.reserve(up_bytes)) return rc;
-    if (int rc = d_up.reserve_on_current_device(up_bytes)) return rc;
-    if (int rc = d_res.reserve_on_current_device(res_bytes)) return rc;
-    if (int rc = d_ev.reserve_on_current_device(std::max<size_t>(ev_total, 1) * sizeof(dv_allele_event))) return rc;
-    if (n_gv) {
-      if (int rc = d_gscr.reserve_on_current_device(scr_ints * sizeof(int32_t))) return rc;
-      if (int rc = d_gblk.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
-      if (int rc = d_gpack.reserve_on_current_device(std::max<size_t>(blk_total, 1) * sizeof(dv_gvcf_block))) return rc;
-    }
-    if (n_cd) {
-      const size_t sites = std::max<size_t>(cnt_ints, 1), evs = std::max<size_t>(ev_total, 1);
-      if (int rc = d_cscr.reserve_on_current_device(std::max<size_t>(cscr_ints, 1) * sizeof(int32_t))) return rc;
-      if (int rc = d_csite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
-      if (int rc = d_cpsite.reserve_on_current_device(sites * sizeof(dv_candidate_site))) return rc;
-      if (int rc = d_call.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
-      if (int rc = d_cpall.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
-      if (int rc = d_cword.reserve_on_current_device(evs * sizeof(int32_t))) return rc;
-    }
-    for (int32_t k = 0; k < n; ++k) {
-      const Plan& p = plan[k];
-      if (!p.batched) continue;
-      const dv_batch* b = reads[k];
-      const dv_allele_counter_options* o = options[k];
-      const size_t nr = static_cast<size_t>(b->n_reads);
-      uint8_t* base = h_up.ptr;
-      std::memcpy(base + p.up[0], b->read_pos, nr * 4);
-      std::memcpy(base + p.up[1], b->read_seq_off, (nr + 1) * 4);
-      std::memcpy(base + p.up[2], b->read_cigar_off, (nr + 1) * 4);
-      std::memcpy(base + p.up[3], b->read_mapq, nr);
-      std::memcpy(base + p.up[4], b->bases, b->n_bases);
-      std::memcpy(base + p.up[5], b->quals, b->n_bases);
-      std::memcpy(base + p.up[6], b->cigar, static_cast<size_t>(b->n_cigar) * 4);
-      std::memcpy(base + p.up[7], o->ref_bases, static_cast<size_t>(o->n_ref_bases));
-      if (p.mask_words) {
-        uint32_t* mask = reinterpret_cast<uint32_t*>(base + p.up[8]);
-        std::memset(mask, 0, p.mask_words * 4);
-        for (int32_t c = 0; c < o->n_candidate_positions; ++c) {
-          const int64_t q = o->candidate_positions[c] - o->interval_start;
-          if (q >= 0 && q < p.len) mask[static_cast<size_t>(q >> 5)] |= 1u << (q & 31);
-        }
-      }
-      const uint8_t* dup0 = static_cast<const uint8_t*>(d_up.ptr);
-      uint8_t* dres0 = static_cast<uint8_t*>(d_res.ptr);
-      if ((gv || co) && keys_of(k)) std::memcpy(base + p.key_up, keys_of(k), nr * 4);
-      if (p.cd_slot >= 0) {
-        dv::CandRegion g{};
-        g.ref_count = reinterpret_cast<const int32_t*>(dres0 + ctr_bytes) + p.cnt_off;
-        g.events = static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off;
-        g.n_events = reinterpret_cast<const uint32_t*>(dres0) + static_cast<size_t>(k) * 4;
-        g.event_cap = p.cap;
-        g.read_key = keys_of(k) ? reinterpret_cast<const int32_t*>(dup0 + p.key_up) : nullptr;
-        g.ref = dup0 + p.up[7] + (o->interval_start - o->ref_start);
-        g.bases = dup0 + p.up[4];
-        g.seq_off = reinterpret_cast<const uint32_t*>(dup0 + p.up[1]);
-        g.len = static_cast<int32_t>(p.len);
-        g.scratch = static_cast<int32_t*>(d_cscr.ptr) + p.cscr_off;
-        g.sites = static_cast<dv_candidate_site*>(d_csite.ptr) + p.cnt_off;
-        g.alleles = static_cast<dv_candidate_allele*>(d_call.ptr) + p.ev_off;
-        g.words = static_cast<int32_t*>(d_cword.ptr) + p.ev_off;
-        g.n_out = reinterpret_cast<int32_t*>(dres0 + ncand_off) + static_cast<size_t>(k) * 2;
-        std::memcpy(base + cdesc_up + static_cast<size_t>(p.cd_slot) * sizeof(dv::CandRegion), &g, sizeof(g));
-      }
-      if (p.gv_slot >= 0) {
-        // the descriptor points into the device images: the counts, events and reference the counter uses
-        dv::GvcfRegion g{};
-        g.ref_count = reinterpret_cast<const int32_t*>(dres0 + ctr_bytes) + p.cnt_off;
-        g.events = static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off;
-        g.n_events = reinterpret_cast<const uint32_t*>(dres0) + static_cast<size_t>(k) * 4;
-        g.event_cap = p.cap;
-        g.read_key = keys_of(k) ? reinterpret_cast<const int32_t*>(dup0 + p.key_up) : nullptr;
-        g.ref = dup0 + p.up[7] + (o->interval_start - o->ref_start);
-        g.interval_start = o->interval_start;
-        g.len = static_cast<int32_t>(p.len);
-        g.lo = gv->left_padding;
-        g.hi = static_cast<int32_t>(p.len - gv->right_padding);
-        g.scratch = static_cast<int32_t*>(d_gscr.ptr) + p.scr_off;
-        g.blocks = static_cast<dv_gvcf_block*>(d_gblk.ptr) + p.blk_off;
-        g.n_blocks = reinterpret_cast<int32_t*>(dres0 + nblk_off) + k;
-        std::memcpy(base + desc_up + static_cast<size_t>(p.gv_slot) * sizeof(dv::GvcfRegion), &g, sizeof(g));
-      }
-    }
-    DV_HIP_CHECK(hipMemcpyAsync(d_up.ptr, h_up.ptr, up_bytes, hipMemcpyHostToDevice, stream));
-    DV_HIP_CHECK(hipMemsetAsync(d_res.ptr, 0, res_bytes, stream));
-    if (n_gv) {
-      DV_HIP_CHECK(hipMemsetAsync(d_gscr.ptr, 0, scr_ints * sizeof(int32_t), stream));
-      if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
-    }
-    if (n_cd) DV_HIP_CHECK(hipMemsetAsync(d_cscr.ptr, 0, cscr_ints * sizeof(int32_t), stream));
-    uint8_t* dres = static_cast<uint8_t*>(d_res.ptr);
-    const uint8_t* dup = static_cast<const uint8_t*>(d_up.ptr);
-    for (int32_t k = 0; k < n; ++k) {
-      const Plan& p = plan[k];
-      if (!p.batched) continue;
-      const dv_batch* b = reads[k];
-      const dv_allele_counter_options* o = options[k];
-      CountArgs a{};
-      a.n_reads = b->n_reads;
-      a.read_pos = reinterpret_cast<const int32_t*>(dup + p.up[0]);
-      a.seq_off = reinterpret_cast<const uint32_t*>(dup + p.up[1]);
-      a.cigar_off = reinterpret_cast<const uint32_t*>(dup + p.up[2]);
-      a.mapq = dup + p.up[3];
-      a.bases = dup + p.up[4];
-      a.quals = dup + p.up[5];
-      a.cigar = reinterpret_cast<const uint32_t*>(dup + p.up[6]);
-      a.ref = dup + p.up[7];
-      a.ref_start = o->ref_start;
-      a.n_ref = o->n_ref_bases;
-      a.reads_start = std::min(o->interval_start, o->reads_interval_start);
-      a.reads_end = std::max(o->interval_end, o->reads_interval_end);
-      a.interval_start = o->interval_start;
-      a.interval_len = p.len;
-      a.contig_len = o->contig_n_bases > 0 ? o->contig_n_bases : o->ref_start + o->n_ref_bases;
-      a.min_mapq = o->min_mapping_quality;
-      a.min_bq = o->min_base_quality;
-      a.legacy = o->keep_legacy_behavior ? 1 : 0;
-      a.candidate_mask = p.mask_words ? reinterpret_cast<const uint32_t*>(dup + p.up[8]) : nullptr;
-      a.counters = reinterpret_cast<uint32_t*>(dres) + static_cast<size_t>(k) * 4;
-      a.ref_count = reinterpret_cast<int32_t*>(dres + ctr_bytes) + p.cnt_off;
-      a.events = static_cast<dv_allele_event*>(d_ev.ptr) + p.ev_off;
-      a.event_cap = p.cap;
-      dv::ProfileScope prof(dv::kProfOther, stream);
-      hipLaunchKernelGGL(count_alleles_kernel, dim3((b->n_reads + 4 * kReadsPerWave - 1) / (4 * kReadsPerWave)),
-                         dim3(256), 0, stream, a);
-    }
-    DV_HIP_CHECK(hipGetLastError());
-    if (n_gv) {
-      // the reference-confidence pass reads the counts where the kernels above leave them
-      if (int rc = dv::gvcf_launch(reinterpret_cast<const dv::GvcfRegion*>(dup + desc_up), n_gv, max_len, max_cap, gv,
-                                   d_table, static_cast<dv_gvcf_block*>(d_gpack.ptr), stream)) {
-        return rc;
-      }
-    }
-    if (n_cd) {
-      // the candidate caller reads the same counts and events, and the read bases the events point into
-      if (int rc = dv::cand_launch(reinterpret_cast<const dv::CandRegion*>(dup + cdesc_up), n_cd, max_cap, co,
-                                   static_cast<dv_candidate_site*>(d_cpsite.ptr),
-                                   static_cast<dv_candidate_allele*>(d_cpall.ptr), stream)) {
-        return rc;
-      }
-    }
-    // counters and counts come back together; the events follow once their numbers are known
-    if (int rc = h_down.reserve(res_bytes)) return rc;
-    if (pos_only) {                  // the counters and the record counts only
-      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, ctr_bytes, hipMemcpyDeviceToHost, stream));
-      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr + ncand_off, dres + ncand_off, res_bytes - ncand_off, hipMemcpyDeviceToHost,
-                                  stream));
-    } else {
-      DV_HIP_CHECK(hipMemcpyAsync(h_down.ptr, d_res.ptr, res_bytes, hipMemcpyDeviceToHost, stream));
-    }
-    DV_HIP_CHECK(hipStreamSynchronize(stream));
-    const int32_t* ncand = reinterpret_cast<const int32_t*>(h_down.ptr + ncand_off);
-    const uint32_t* ctrs = reinterpret_cast<const uint32_t*>(h_down.ptr);
-    const int32_t* cnts = reinterpret_cast<const int32_t*>(h_down.ptr + ctr_bytes);
-    size_t ev_bytes = 0;
-    for (int32_t k = 0; k < n; ++k) {
-      Plan& p = plan[k];
-      if (!p.batched) continue;
-      const uint32_t* ctr = ctrs + static_cast<size_t>(k) * 4;
-      if (ctr[2] != 0) {
-        return fail_all(dv::fail(DV_ERR_BAD_INPUT,
-                                 "dv_count_alleles: an indel reaches outside the reference window (pass more margin)"));
-      }
-      if (ctr[0] > p.cap) {          // the first guess was too small: this region goes alone (two passes there)
-        p.batched = false;
-        continue;
-      }
-      done[k] = 1;
-      if (co) {
-        cout[k] = new dv_candidates();
-        cout[k]->sites.resize(static_cast<size_t>(ncand[2 * k]));
-        if (!pos_only) cout[k]->alleles.resize(static_cast<size_t>(ncand[2 * k + 1]));
-      }
-      if (pos_only) continue;
-      auto res = std::make_unique<dv_allele_counts>();
-      res->length = p.len;
-      res->n_reads_counted = static_cast<int32_t>(ctr[1]);
-      if (int rc = res->ref_count.reserve(static_cast<size_t>(p.len))) return fail_all(rc);
-      std::memcpy(res->ref_count.ptr, cnts + p.cnt_off, static_cast<size_t>(p.len) * sizeof(int32_t));
-      if (int rc = res->raw.reserve(ctr[0])) return fail_all(rc);
-      out[k] = res.release();
-      ev_bytes += static_cast<size_t>(ctr[0]) * sizeof(dv_allele_event);
-      if (gv) {
-        gout[k] = new dv_gvcf_blocks();
-        gout[k]->blocks.resize(static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]));
-      }
-    }
-    // gVCF: every batched region's records lie packed in region order (gvcf_pack_kernel), the overflowed
-    // regions' included: they come back in one copy behind the events
-    size_t packed_blocks = 0;
-    if (gv) {
-      for (int32_t k = 0; k < n; ++k) {
-        if (plan[k].gv_slot >= 0) packed_blocks += static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]);
-      }
-    }
-    const size_t packed_at = ev_bytes;
-    ev_bytes += packed_blocks * sizeof(dv_gvcf_block);
-    // candidates: the event words region by region (as the events), then the packed site and allele
-    // records of every batched region (cand_pack_kernel), the overflowed regions' included
-    const size_t words_at = ev_bytes;
-    size_t packed_sites = 0, packed_alleles = 0;
-    if (co) {
-      for (int32_t k = 0; k < n; ++k) {
-        if (plan[k].cd_slot < 0) continue;
-        packed_sites += static_cast<size_t>(ncand[2 * k]);
-        packed_alleles += static_cast<size_t>(ncand[2 * k + 1]);
-        if (plan[k].batched && !pos_only) ev_bytes += static_cast<size_t>(ctrs[static_cast<size_t>(k) * 4]) * sizeof(int32_t);
-      }
-    }
-    const size_t sites_at = ev_bytes;
-    ev_bytes += packed_sites * sizeof(dv_candidate_site);
-    const size_t alleles_at = ev_bytes;
-    if (!pos_only) ev_bytes += packed_alleles * sizeof(dv_candidate_allele);
-    // the events (and gVCF records) of every region into one pinned image, one synchronisation
-    static thread_local PinnedBytes h_ev;
-    if (int rc = h_ev.reserve(ev_bytes)) return fail_all(rc);
-    size_t at = 0, wat = words_at;
-    for (int32_t k = 0; k < n; ++k) {
-      const Plan& p = plan[k];
-      if (!p.batched || pos_only) continue;
-      const size_t n_ev = ctrs[static_cast<size_t>(k) * 4];
-      const size_t bytes = n_ev * sizeof(dv_allele_event);
-      if (bytes) {
-        DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + at, static_cast<const dv_allele_event*>(d_ev.ptr) + p.ev_off, bytes,
-                                    hipMemcpyDeviceToHost, stream));
-        if (co) {
-          DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + wat, static_cast<const int32_t*>(d_cword.ptr) + p.ev_off,
-                                      n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        }
-      }
-      at += bytes;
-      if (co) wat += n_ev * sizeof(int32_t);
-    }
-    if (packed_sites) {
-      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + sites_at, d_cpsite.ptr, packed_sites * sizeof(dv_candidate_site),
-                                  hipMemcpyDeviceToHost, stream));
-    }
-    if (packed_alleles && !pos_only) {
-      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + alleles_at, d_cpall.ptr, packed_alleles * sizeof(dv_candidate_allele),
-                                  hipMemcpyDeviceToHost, stream));
-    }
-    if (packed_blocks) {
-      DV_HIP_CHECK(hipMemcpyAsync(h_ev.ptr + packed_at, d_gpack.ptr, packed_blocks * sizeof(dv_gvcf_block),
-                                  hipMemcpyDeviceToHost, stream));
-    }
-    DV_HIP_CHECK(hipStreamSynchronize(stream));
-    at = 0;
-    wat = words_at;
-    for (int32_t k = 0; k < n; ++k) {
-      const Plan& p = plan[k];
-      if (!p.batched || pos_only) continue;
-      const size_t n_ev = ctrs[static_cast<size_t>(k) * 4];
-      if (n_ev) std::memcpy(out[k]->raw.ptr, h_ev.ptr + at, n_ev * sizeof(dv_allele_event));
-      at += n_ev * sizeof(dv_allele_event);
-      if (co) {
-        order_events_with_words(out[k], n_ev, reinterpret_cast<const int32_t*>(h_ev.ptr + wat), &cout[k]->words);
-        wat += n_ev * sizeof(int32_t);
-      } else {
-        order_events(out[k], n_ev);
-      }
-    }
-    if (co) {
-      size_t sat = sites_at, aat = alleles_at;
-      for (int32_t k = 0; k < n; ++k) {
-        if (plan[k].cd_slot < 0) continue;
-        const size_t sbytes = static_cast<size_t>(ncand[2 * k]) * sizeof(dv_candidate_site);
-        const size_t abytes = static_cast<size_t>(ncand[2 * k + 1]) * sizeof(dv_candidate_allele);
-        if (plan[k].batched) {
-          if (sbytes) std::memcpy(cout[k]->sites.data(), h_ev.ptr + sat, sbytes);
-          if (abytes && !pos_only) std::memcpy(cout[k]->alleles.data(), h_ev.ptr + aat, abytes);
-        }
-        sat += sbytes;
-        aat += abytes;
-      }
-    }
-    at = packed_at;
-    for (int32_t k = 0; k < n; ++k) {
-      if (plan[k].gv_slot < 0) continue;
-      const size_t gbytes = static_cast<size_t>(reinterpret_cast<const int32_t*>(h_down.ptr + nblk_off)[k]) *
-                            sizeof(dv_gvcf_block);
-      if (plan[k].batched && out[k] && gbytes) std::memcpy(gout[k]->blocks.data(), h_ev.ptr + at, gbytes);
-      at += gbytes;
-    }
-  }
-  for (int32_t k = 0; k < n; ++k) {
-    if (done[k]) continue;
-    if (int rc = dv_count_alleles(reads[k], options[k], &out[k], stream_v)) return rc;
-    if (co) {
-      if (int rc = candidates_from_counts(out[k], options[k], reads[k], keys_of(k), co, stream, &cout[k])) return rc;
-    }
-    if (gv) {
-      if (!d_table) {
-        if (int rc = dv::gvcf_table_on_device(gv, &d_table, stream)) return rc;
-      }
-      if (int rc = gvcf_from_counts(out[k], options[k], reads[k], keys_of(k), gv, d_table, stream, &gout[k])) return rc;
-    }
-  }
-  return DV_OK;
-  };
-  const int rc = body();
-  if (rc != DV_OK) return fail_all(rc);
-  for (dv_allele_counts* c : own_out) delete c;
+  if (int rc = run_alone(rq, second, d_table, &results)) return rc;
+  results.release();
   return DV_OK;
 }
 

@@ -342,18 +342,29 @@ def test_readless_region_in_a_batch_and_a_counter_that_has_run():
   assert alone == calls
 
 
-def test_events_beyond_the_first_guess():
-  """A region whose events overflow the batch's first guess (every base of every read is a mismatch) is
-  counted alone and takes the same kernels from its counts (the one-region path), next to an ordinary
-  region of the same batch."""
-  ref = _corner_ref()
+def _noisy_reads(ref):
+  """300 reads of 100 bases over [950, 1450), every base a mismatch."""
   rng = np.random.default_rng(11)
   noisy = []
   for i in range(300):
     start = int(rng.integers(950, 1350))
     seq = ''.join(_other(b) if i % 3 else ('G' if b != 'G' else 'T') for b in ref.seq[start:start + 100])
     noisy.append(HG._read('n%d' % i, 1, start, seq, [(100, 'M')]))    # pylint: disable=protected-access
-  quiet = _pile(ref, 'ref', 10, start=2000) + _pile(ref, 'alt', 4, start=2000, edit=_sub_at(2030, 2000))
+  return noisy
+
+
+def _quiet_reads(ref, start=2000):
+  """Ten reference reads and four with a substitution at start + 30."""
+  return _pile(ref, 'ref', 10, start=start) + _pile(ref, 'alt', 4, start=start, edit=_sub_at(start + 30, start))
+
+
+def test_events_beyond_the_first_guess():
+  """A region whose events overflow the batch's first guess (every base of every read is a mismatch) is
+  counted alone and takes the same kernels from its counts (the one-region path), next to an ordinary
+  region of the same batch."""
+  ref = _corner_ref()
+  noisy = _noisy_reads(ref)
+  quiet = _quiet_reads(ref)
   caller = _caller()
 
   def make(positions):
@@ -395,6 +406,144 @@ def test_with_gvcf_in_one_pass():
   for b, o in zip(both, only):
     assert b._gvcf is not None and b.gvcf_block_array(opts).tobytes() == o.gvcf_block_array(opts).tobytes()   # pylint: disable=protected-access
     HG._same(b.gvcf_blocks(opts), HG._host(o, opts))                # pylint: disable=protected-access
+
+
+# ---------------------------------------------------------------- the overflow route inside a batch
+
+_OVERFLOW_SPANS = ((1990, 2070), (1000, 1400), (2100, 2180))       # quiet, noisy, quiet
+_OVERFLOW_GVCF = vc.GvcfOptions('s', include_med_dp=True)
+_overflow_cache = {}
+
+
+def _overflow_counters(track):
+  """Three fresh counters: the noisy region of test_events_beyond_the_first_guess between two quiet ones.
+  With `track` every region has candidate positions; the noisy one few enough that it still overflows."""
+  ref = _corner_ref()
+  reads = (_quiet_reads(ref), _noisy_reads(ref), _quiet_reads(ref, 2110))
+  positions = ([2030], list(range(1000, 1400, 8)), [2140]) if track else ((), (), ())
+  out = []
+  for (s, e), rs, pos in zip(_OVERFLOW_SPANS, reads, positions):
+    c = A.AlleleCounter(ref, 'c', s, e, candidate_positions=pos, min_mapping_quality=10, min_base_quality=10,
+                        track_ref_reads=track)
+    for r in rs:
+      c.add(r)
+    out.append(c)
+  return out
+
+
+def _overflow_reference(track):
+  """Once per `track`: each region counted alone by the one-region entry, and the host's records, calls
+  and call positions from those counts."""
+  if track not in _overflow_cache:
+    caller = _caller(track=track)
+    alone = _overflow_counters(track)
+    for c in alone:
+      c.counts()
+    # the noisy region's events exceed dv_count_alleles_batch's first guess
+    n_positions = len(alone[1]._candidate_positions) if track else 0   # pylint: disable=protected-access
+    assert len(alone[1]._events) > 300 + 300 * 100 // 16 + 4096 + 64 * n_positions   # pylint: disable=protected-access
+    assert len(alone[0]._events) < 14 + 14 * 60 // 16 + 4096           # pylint: disable=protected-access
+    _overflow_cache[track] = dict(
+        caller=caller, alone=alone,
+        records=[HG._host(c, _OVERFLOW_GVCF) for c in alone],          # pylint: disable=protected-access
+        calls=[_host_calls(caller, c) for c in alone],
+        positions=[caller.call_positions_from_allele_counts(c.counts()) for c in alone])
+    assert len(_overflow_cache[track]['calls'][1]) == 400 and [len(x) for x in _overflow_cache[track]['positions']] == [1, 400, 1]
+  return _overflow_cache[track]
+
+
+def _run_overflow(track, way, groups):
+  """Runs the three regions in `groups` (lists of region indices, one run_batch each) -> the counters."""
+  want = _overflow_reference(track)
+  caller = want['caller']
+  kwargs = {'gvcf': dict(gvcf=_OVERFLOW_GVCF),
+            'gvcf+call': dict(gvcf=_OVERFLOW_GVCF, call=caller.candidate_options()),
+            'positions': dict(call=caller.candidate_options(positions_only=True)),
+            'plain': {}}[way]
+  counters = _overflow_counters(track)
+  for group in groups:
+    A.AlleleCounter.run_batch([counters[k] for k in group], **kwargs)
+  return counters
+
+
+@pytest.mark.parametrize('way', ['gvcf', 'gvcf+call', 'positions', 'plain'])
+@pytest.mark.parametrize('track', [False, True])
+def test_overflowing_region_in_the_middle_of_a_batch(track, way):
+  """Quiet, noisy, quiet: the noisy region leaves the batch (its events exceed the first guess) and the
+  packed records behind it still land in the right region.  Every way of running the batch against the
+  host, and against the same regions run one per batch."""
+  want = _overflow_reference(track)
+  caller = want['caller']
+  together = _run_overflow(track, way, [[0, 1, 2]])
+  one_each = _run_overflow(track, way, [[0], [1], [2]])
+  for k, (t, o, a) in enumerate(zip(together, one_each, want['alone'])):
+    for c in (t, o):
+      if way == 'positions':
+        assert c._events is None                                      # pylint: disable=protected-access
+        assert caller.call_positions_from_allele_counter(c) == want['positions'][k]
+        continue
+      assert np.array_equal(c._events, a._events)                     # pylint: disable=protected-access
+      assert np.array_equal(c.ref_supporting_read_counts(), a.ref_supporting_read_counts())
+      assert c.n_counted_reads() == a.n_counted_reads()
+      if 'gvcf' in way:
+        assert c._gvcf is not None                                    # pylint: disable=protected-access
+        HG._same(c.gvcf_blocks(_OVERFLOW_GVCF), want['records'][k])   # pylint: disable=protected-access
+      if 'call' in way:
+        assert c._cand is not None                                    # pylint: disable=protected-access
+        assert caller.calls_from_allele_counter(c) == want['calls'][k]
+    if 'gvcf' in way:
+      assert t.gvcf_block_array(_OVERFLOW_GVCF).tobytes() == o.gvcf_block_array(_OVERFLOW_GVCF).tobytes()
+    if 'call' in way:
+      for x, y in zip(t._cand[1:], o._cand[1:]):                      # pylint: disable=protected-access
+        assert x.tobytes() == y.tobytes()
+
+
+def test_device_resident_read_table_in_a_batch_with_call():
+  """A region whose read table is in device memory takes the one-region path and the candidate pass from
+  its counts, reading the bases where the caller left them; next to a host-resident region of the same
+  batch it gives the sites, alleles and words of the same region passed host-resident."""
+  import torch
+  from deepvariant_amd import _lib
+  ref, reads = _synthetic_with_candidates()
+  caller = _caller()
+
+  def make():
+    out = []
+    for s, e in ((1000, 1200), (1200, 1450)):                         # the first has shared read keys
+      c = A.AlleleCounter(ref, 'c', s, e, min_mapping_quality=10, min_base_quality=10)
+      for r in reads:
+        c.add(r)
+      out.append(c)
+    return out
+
+  def on_device(counter):
+    host_request = counter._request                                   # pylint: disable=protected-access
+
+    def request():
+      b, opt, keep, ctx = host_request()
+      tensors = []
+      for name, dtype in (('read_pos', np.int32), ('read_seq_off', np.uint32), ('read_cigar_off', np.uint32),
+                          ('read_mapq', np.uint8), ('bases', np.uint8), ('quals', np.uint8), ('cigar', np.uint32)):
+        host = np.ascontiguousarray(getattr(ctx[0], name), dtype).view(np.uint8)
+        tensors.append(torch.from_numpy(host.copy()).cuda())
+        setattr(b, name, tensors[-1].data_ptr())
+      torch.cuda.synchronize()
+      b.memory = _lib.DV_MEM_DEVICE
+      return b, opt, (keep, tensors), ctx
+    counter._request = request                                        # pylint: disable=protected-access
+
+  host = make()
+  A.AlleleCounter.run_batch(host, call=caller.candidate_options())
+  mixed = make()
+  on_device(mixed[0])
+  A.AlleleCounter.run_batch(mixed, call=caller.candidate_options())
+  for m, h in zip(mixed, host):
+    assert len(m._cand[1]) and len(m._cand[2]) and len(m._cand[3])    # pylint: disable=protected-access
+    for x, y in zip(m._cand[1:], h._cand[1:]):                        # sites, alleles, words   pylint: disable=protected-access
+      assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
+    assert np.array_equal(m._events, h._events)                       # pylint: disable=protected-access
+    assert caller.calls_from_allele_counter(m) == _host_calls(caller, m)
+  assert 1070 in [c.variant.start for c in caller.calls_from_allele_counter(mixed[0])]
 
 
 # ---------------------------------------------------------------- through the product
