@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
     'dv_debruijn_device_last_stats', 'dv_debruijn_from_compact', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
+    'dv_phase_reads_batch', 'dv_phase_reads_batch_device', 'dv_phase_device_last_stats',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
     'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
@@ -300,6 +301,21 @@ class DvPhasingCandidate(C.Structure):
   _fields_ = [('start', C.c_int64), ('end', C.c_int64), ('allele_off', C.c_int32), ('n_alleles', C.c_int32)]
 
 
+class DvPhasingRegion(C.Structure):
+  _fields_ = [('candidate_off', C.c_int32), ('n_candidates', C.c_int32), ('allele_off', C.c_int32),
+              ('n_alleles', C.c_int32), ('support_off', C.c_int64), ('n_support', C.c_int64),
+              ('first_read', C.c_int64), ('n_reads', C.c_int32), ('reserved', C.c_int32)]
+
+
+class DvPhasingStats(C.Structure):
+  _fields_ = [('regions', C.c_int64), ('regions_on_host', C.c_int64), ('sites_in_graphs', C.c_int64),
+              ('vertices', C.c_int64), ('combinations', C.c_int64), ('launches', C.c_int64)]
+
+
+DV_PHASING_DEVICE_MAX_READS = 1024
+DV_PHASING_DEVICE_MAX_VERTICES = 8
+
+
 class DvAltMergeEntry(C.Structure):
   _fields_ = [('example', C.c_int64), ('first_row', C.c_int32), ('rows', C.c_int32),
               ('scratch_alt1', C.c_int64), ('scratch_alt2', C.c_int64)]
@@ -506,6 +522,12 @@ def lib():
     l.dv_phase_reads.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_char_p, C.c_int64, C.c_void_p,
                                  C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int32]
+    phase_batch = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                   C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p]
+    l.dv_phase_reads_batch.argtypes = phase_batch
+    l.dv_phase_reads_batch_device.argtypes = phase_batch + [C.c_void_p]
+    l.dv_phase_device_last_stats.argtypes = [C.c_void_p]
     l.dv_count_alleles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_count_alleles_batch.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_allele_counts_arrays.argtypes = [C.c_void_p] + [C.c_void_p] * 4

@@ -96,6 +96,92 @@ def total_allele_counts(allele_count: AlleleCount, include_low_quality: bool = F
   return n + allele_count.ref_supporting_read_count
 
 
+def phasing_arrays_from_events(ev, words, sites, alleles, key_ids, start, bases, seq_off, window, w0):
+  """The pure array step of AlleleCounter.phasing_arrays: the device caller's sites, selected alleles and event
+  words plus the counter's events -> (candidates, alleles, bases, support_reads, support_low_quality) in
+  direct_phasing's record layouts, offsets relative to these arrays.
+
+  Per site, as VariantCaller._add_supporting_reads followed by DirectPhasing.phase build them: read_alleles is a map
+  by read key in the order the keys first appear among the site's events, each key with its last ("standing") event;
+  one is_ref entry from the standing REFERENCE events, then one entry per selected allele in the order the standing
+  events first name it; events with the "uncalled" word are UNCALLED_ALLELE and left out.  A read index is the LAST
+  row that has the event's key (`key_ids`: key number per row, None = all distinct).  start / end are the variant's:
+  the reference bases grow with the longest selected deletion, and an allele's bases are the variant's alternate:
+  substitutions byte for byte; an insertion or deletion only has the right length, which is all the candidate filter
+  reads of a site it refuses."""
+  from deepvariant_amd import direct_phasing as dp     # pylint: disable=g-import-not-at-top
+  n_sites = len(sites)
+  lo = np.searchsorted(ev['position'], sites['offset'], 'left')
+  hi = np.searchsorted(ev['position'], sites['offset'], 'right')
+  counts = hi - lo
+  before = np.cumsum(counts) - counts
+  site_of = np.repeat(np.arange(n_sites), counts)
+  idx = np.arange(int(counts.sum())) - np.repeat(before, counts) + np.repeat(lo, counts)
+  e, word = ev[idx], words[idx].astype(np.int64)
+  packed = e['length_type']
+  kind, low = (packed >> 28) & 7, (packed >> 31).astype(np.uint8)
+  row = e['read'].astype(np.int64)
+  order = np.arange(len(idx))                     # read_alleles order: where the event's key first appears in the site
+  read_index = row
+  if key_ids is not None:
+    key_ids = np.asarray(key_ids, np.int64)
+    n_keys = int(key_ids.max()) + 1 if len(key_ids) else 1
+    _, first, inverse = np.unique(site_of * n_keys + key_ids[row], return_index=True, return_inverse=True)
+    order = first[inverse]
+    last_row = np.zeros(n_keys, np.int64)
+    last_row[key_ids] = np.arange(len(key_ids))   # a later row with the same key wins
+    read_index = last_row[key_ids[row]]
+  kept = np.nonzero((word != EVENT_OVERWRITTEN) & ((kind == REFERENCE) | (word >= 0)))[0]
+  stride = int(sites['n_alleles'].max()) + 1 if n_sites else 1
+  slot = np.where(kind[kept] == REFERENCE, 0, 1 + word[kept])
+  entries, entry_of = np.unique(site_of[kept] * stride + slot, return_inverse=True)
+  first_named = np.full(len(entries), np.iinfo(np.int64).max)
+  np.minimum.at(first_named, entry_of, order[kept])
+  entry_site, entry_slot = entries // stride, entries % stride
+  by_order = np.lexsort((first_named, entry_slot != 0, entry_site))     # the is_ref entry first, then as first named
+  rank = np.empty(len(entries), np.int64)
+  rank[by_order] = np.arange(len(entries))
+  final = np.lexsort((order[kept], rank[entry_of]))
+  support_reads = np.ascontiguousarray(read_index[kept][final], np.int32)
+  support_low = np.ascontiguousarray(low[kept][final], np.uint8)
+  n_support = np.bincount(entry_of, minlength=len(entries))[by_order]
+  entry_site, entry_slot = entry_site[by_order], entry_slot[by_order]
+
+  # the variant's reference span: one base, or the longest selected deletion behind its anchor
+  a_packed = alleles['length_type']
+  a_len, a_kind = (a_packed & 0x0fffffff).astype(np.int64), (a_packed >> 28) & 7
+  a_site = np.repeat(np.arange(n_sites), sites['n_alleles'])
+  a_index = np.arange(len(a_site)) - np.repeat(np.cumsum(sites['n_alleles']) - sites['n_alleles'], sites['n_alleles']) + \
+      np.repeat(sites['first_allele'], sites['n_alleles'])
+  span = np.ones(n_sites, np.int64)
+  np.maximum.at(span, a_site, np.where(a_kind[a_index] == DELETION, 1 + a_len[a_index], 1))
+  is_ref = entry_slot == 0
+  chosen = sites['first_allele'][entry_site] + np.maximum(entry_slot - 1, 0)      # the entry's selected allele
+  c_kind, c_len = a_kind[chosen], a_len[chosen]
+  width = span[entry_site]
+  bases_len = np.where(is_ref, 0, np.where(c_kind == INSERTION, width + c_len,
+                                           np.where(c_kind == DELETION, width - c_len, width)))
+  bases_off = np.cumsum(bases_len) - bases_len
+  blob = np.full(int(bases_len.sum()), ord('N'), np.uint8)
+  substitution = ~is_ref & (c_kind == SUBSTITUTION)
+  s0 = seq_off[alleles['read'][chosen]].astype(np.int64) + alleles['read_offset'][chosen]
+  blob[bases_off[substitution]] = bases[s0[substitution]]
+  for k in np.nonzero(substitution & (width > 1))[0].tolist():       # a substitution beside a deletion: its reference tail
+    anchor = start + int(sites['offset'][entry_site[k]]) - w0
+    tail = np.frombuffer(window[anchor + 1:anchor + int(width[k])], np.uint8)
+    blob[bases_off[k] + 1:bases_off[k] + 1 + len(tail)] = tail
+
+  allele_records = np.zeros(len(entries), dp.ALLELE_DTYPE)
+  allele_records['bases_off'], allele_records['bases_len'], allele_records['is_ref'] = bases_off, bases_len, is_ref
+  allele_records['support_off'], allele_records['n_support'] = np.cumsum(n_support) - n_support, n_support
+  per_site = np.bincount(entry_site, minlength=n_sites)
+  candidates = np.zeros(n_sites, dp.CANDIDATE_DTYPE)
+  candidates['start'] = start + sites['offset'].astype(np.int64)
+  candidates['end'] = candidates['start'] + span
+  candidates['allele_off'], candidates['n_alleles'] = np.cumsum(per_site) - per_site, per_site
+  return candidates, allele_records, blob, support_reads, support_low
+
+
 class AlleleCounter:
   def __init__(self, ref_reader, reference_name: str, start: int, end: int,
                candidate_positions: Sequence[int] = (), min_mapping_quality: int = 0,
@@ -490,6 +576,19 @@ class AlleleCounter:
       c.read_alleles = read_alleles
       out.append(c)
     return out
+
+  def phasing_arrays(self, call):
+    """What read phasing reads of this counter's sites, as arrays (direct_phasing.phase_arrays' region layout
+    without n_reads: candidates, alleles, bases, support_reads, support_low_quality) -- the lists
+    DirectPhasing.phase builds from the calls of `candidates(call)`, with no Read, call or name made.  Read indices
+    are rows of the counter's table.  Needs the candidate pass with track_ref_reads (run now unless
+    run_batch(call=...) already did)."""
+    if self._cand is None or self._cand[0] != call.key():
+      AlleleCounter._run_call_batch([self], call.calls_form())
+    _, sites, alleles, words = self._cand
+    table, window, w0 = self._event_ctx
+    return phasing_arrays_from_events(self._events, words, sites, alleles, AlleleCounter._read_key_ids(table.keys),
+                                      self._start, table.bases, table.read_seq_off, window, w0)
 
   def gvcf_block_array(self, gvcf) -> np.ndarray:
     """The device's gVCF records of this counter (GVCF_BLOCK_DTYPE; MED_DP -1 unless asked for),

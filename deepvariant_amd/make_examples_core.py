@@ -25,6 +25,7 @@ import dataclasses
 import numpy as np
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
+from deepvariant_amd import _lib
 from deepvariant_amd import allelecounter
 from deepvariant_amd import direct_phasing
 from deepvariant_amd import dv_types as T
@@ -350,14 +351,16 @@ class RegionProcessor:
 
   # ---- the table path: the region's reads stay a packed table from the BAM decoder to the
   # encoder (make_examples.RegionReads.table); no Read objects.  It covers the default short-read
-  # calling configuration and window-trimmed pileups (trim_reads_for_pileup /
-  # keep_only_window_spanning_reads: alt_aligned_pileup_lib.trim_table); everything that works on
-  # Read objects (read phasing, spliced-read splitting, alt-aligned pileups, channels with per-read
-  # aux pixels) takes the object path above.
+  # calling configuration, window-trimmed pileups (trim_reads_for_pileup /
+  # keep_only_window_spanning_reads: alt_aligned_pileup_lib.trim_table) and, behind
+  # DV_PHASE_TABLES=1 (read at each call, as DV_REALIGN_DEVICE is), read phasing (phase_reads:
+  # _phase_tables below); everything that works on Read objects (spliced-read splitting,
+  # alt-aligned pileups, channels with per-read aux pixels) takes the object path above.
   def table_path_ok(self) -> bool:
+    import os
     from deepvariant_amd import alt_aligned_pileup_lib as aap
     po, gen = self.processor_options, self.generator
-    return (not po.phase_reads and
+    return ((not po.phase_reads or os.environ.get('DV_PHASE_TABLES') == '1') and
             not (self.realigner is not None and self.realigner.config.split_skip_reads) and
             gen._alt_mode == aap.NONE and                                      # pylint: disable=protected-access
             not gen._encoder_api._need_aux and not gen._encoder_api._need_seq_aux)   # pylint: disable=protected-access
@@ -412,32 +415,74 @@ class RegionProcessor:
     (AlleleCounter.candidates); the calls are then built region by region for its sites."""
     if realigned_tables is None:
       realigned_tables = self.realign_tables(tables, regions)
+    po = self.processor_options
+    # with phase_reads the counters run over the padded region, as `process` does
+    effective = list(regions)
+    if po.phase_reads and po.phase_reads_region_padding_pct > 0:
+      effective = [utils.expand(r, int((r.end - r.start) * po.phase_reads_region_padding_pct / 100),
+                                self.ref_reader.n_bases(r.reference_name)) for r in regions]
     out = [([], realigned) for realigned in realigned_tables]
-    slots, in_region = [], []
+    slots, in_region, rows_of = [], [], []
     for k, (region, realigned) in enumerate(zip(regions, realigned_tables)):
       rows = np.nonzero((realigned.read_end > region.start) & (region.end > realigned.read_pos.astype(np.int64)))[0]
       if len(rows):
         slots.append(k)
         in_region.append(realigned.take(rows))
+        rows_of.append(rows)
     run_batch = getattr(allelecounter.AlleleCounter, 'run_batch', None) or (lambda counters, **kwargs: None)
     positions = [()] * len(slots)
-    if self.processor_options.track_ref_reads:
-      first_pass = [self._allele_counter(regions[k], t) for k, t in zip(slots, in_region)]
+    if po.track_ref_reads:
+      first_pass = [self._allele_counter(effective[k], t) for k, t in zip(slots, in_region)]
       run_batch(first_pass, **self._device_call(positions_only=True))
       positions = [self.variant_caller.call_positions_from_allele_counter(c) for c in first_pass]
-    counters = [self._allele_counter(regions[k], t, p) for k, t, p in zip(slots, in_region, positions)]
-    if self.processor_options.gvcf:
+    counters = [self._allele_counter(effective[k], t, p) for k, t, p in zip(slots, in_region, positions)]
+    if po.gvcf:
       # the same counts, with the regions' gVCF blocks computed behind them on the device
-      opts = self._gvcf_options()
-      allelecounter.AlleleCounter.run_batch(counters, gvcf=opts, **self._device_call())
       self.gvcf_records = [[] for _ in regions]
-      for k, counter in zip(slots, counters):
-        self.gvcf_records[k] = counter.gvcf_blocks(opts)
+      if po.phase_reads:
+        # summary_counts(left_padding, right_padding): the padding of a padded region is not reported
+        for k, counter in zip(slots, counters):
+          opts = self._gvcf_options(regions[k].start - effective[k].start, effective[k].end - regions[k].end)
+          allelecounter.AlleleCounter.run_batch([counter], gvcf=opts, **self._device_call())
+          self.gvcf_records[k] = counter.gvcf_blocks(opts)
+      else:
+        opts = self._gvcf_options()
+        allelecounter.AlleleCounter.run_batch(counters, gvcf=opts, **self._device_call())
+        for k, counter in zip(slots, counters):
+          self.gvcf_records[k] = counter.gvcf_blocks(opts)
     else:
       run_batch(counters, **self._device_call())
+    phased = self._phase_tables(slots, counters, in_region, rows_of, realigned_tables) if po.phase_reads else {}
     for k, counter in zip(slots, counters):
-      out[k] = (self.variant_caller.calls_from_allele_counter(counter), realigned_tables[k])
+      candidates = self.variant_caller.calls_from_allele_counter(counter)
+      if effective[k] is not regions[k]:              # filter_candidates_by_region
+        candidates = [c for c in candidates if regions[k].start <= c.variant.start < regions[k].end]
+      out[k] = (candidates, phased.get(k, realigned_tables[k]))
     return out
+
+  def _phase_tables(self, slots, counters, in_region, rows_of, realigned_tables) -> Dict[int, 'packing.ReadTable']:
+    """Read phasing on tables: the regions' phasing arrays straight from their counters' events
+    (AlleleCounter.phasing_arrays), ONE device call for the batch (direct_phasing.phase_arrays), and the phases
+    written into a copy of each region's table's read_hp for the rows that overlap the region -- the reads
+    `candidates_in_region` phases.  Rows it leaves alone keep their read_hp.  -> {slot: table}."""
+    po = self.processor_options
+    call = self.variant_caller.candidate_options()
+    arrays, which, tables = [], [], {}
+    for k, counter, table, rows in zip(slots, counters, in_region, rows_of):
+      parts = counter.phasing_arrays(call)
+      hp = realigned_tables[k].read_hp.copy()
+      hp[rows] = _lib.DV_HP_NONE                      # an existing phasing must not leak into the images
+      tables[k] = dataclasses.replace(realigned_tables[k], read_hp=hp)
+      if not (po.phase_max_candidates and len(parts[0]) > po.phase_max_candidates):
+        arrays.append(parts + (table.n_reads,))
+        which.append((hp, rows))
+    if arrays:
+      results = direct_phasing.phase_arrays(arrays, po.min_alleles_to_phase, device=True)
+      for (hp, rows), (phases, _, _) in zip(which, results):
+        if self.options.pic_options.reverse_haplotypes:
+          phases = np.where(phases > 0, 3 - phases, phases)
+        hp[rows] = phases
+    return tables
 
   def examples_in_region_table(self, region: T.Range, table, stats: Optional[dict] = None, realigned=None,
                                called=None) -> Tuple[List[T.DeepVariantCall], List[bytes]]:

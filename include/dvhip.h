@@ -906,6 +906,59 @@ int dv_phase_reads(const dv_phasing_candidate* candidates, int32_t n_candidates,
                    int32_t min_alleles_to_phase, int32_t* read_phases, int32_t* allele_phases,
                    uint8_t* allele_flags, char* graphviz, int32_t graphviz_cap);
 
+/* ---- the same for a batch of regions, from arrays (csrc/phasing.hip) -------------
+ * The candidate, allele, bases and support arrays are dv_phase_reads' layouts concatenated over the regions;
+ * allele_off, bases_off and support_off are absolute.  A region names its slices; its candidates' alleles and
+ * their support must lie inside them.  read_phases[first_read .. first_read + n_reads) receives the region's
+ * reads; allele_phases / allele_flags are written at the alleles of the region's candidates.  Nothing else is
+ * written. */
+typedef struct dv_phasing_region {
+  int32_t candidate_off, n_candidates;   /* into `candidates` */
+  int32_t allele_off, n_alleles;         /* into `alleles` */
+  int64_t support_off, n_support;        /* into support_reads / support_low_quality */
+  int64_t first_read;                    /* into read_phases */
+  int32_t n_reads;
+  int32_t reserved;
+} dv_phasing_region;
+
+typedef struct dv_phasing_stats {
+  int64_t regions;
+  int64_t regions_on_host;    /* outside the device limits below: dv_phase_reads_batch_device phased them with
+                                 the host code inside the call; dv_phase_reads_batch only counts them */
+  int64_t sites_in_graphs;    /* sites that passed the candidate filter */
+  int64_t vertices;
+  int64_t combinations;       /* (to-pair, from-pair) combinations the kernel scored; 0 from the host entry */
+  int64_t launches;           /* 1 when a region went to the device, else 0 */
+} dv_phasing_stats;
+
+/* A region goes to the device when it has at most DV_PHASING_DEVICE_MAX_READS reads (the two live positions'
+ * read sets are bitmaps in LDS), no site with more than DV_PHASING_DEVICE_MAX_VERTICES graph vertices, distinct
+ * vertex texts within every site and no read (known, not low quality) listed twice under one site. */
+#define DV_PHASING_DEVICE_MAX_READS 1024
+#define DV_PHASING_DEVICE_MAX_VERTICES 8
+
+/* Host code: dv_phase_reads' checker region by region.  Candidates of a region not strictly ordered by start,
+ * or a read index >= n_reads: DV_ERR_BAD_INPUT naming the smallest such region.  Null pointers, negative counts
+ * and slices outside their tables: DV_ERR_INVALID_ARGUMENT.  An error leaves the outputs untouched.
+ * allele_phases, allele_flags and stats may be NULL. */
+int dv_phase_reads_batch(const dv_phasing_region* regions, int32_t n_regions, const dv_phasing_candidate* candidates,
+                         int32_t n_candidates, const dv_phasing_allele* alleles, int32_t n_alleles, const char* bases,
+                         int64_t n_bases, const int32_t* support_reads, const uint8_t* support_low_quality,
+                         int64_t n_support, int64_t n_reads_total, int32_t min_alleles_to_phase, int32_t* read_phases,
+                         int32_t* allele_phases, uint8_t* allele_flags, dv_phasing_stats* stats);
+/* The same on the device: one upload, ONE launch (a workgroup per region), one download and one synchronisation
+ * on `stream` (NULL = a non-blocking stream the library owns); identical arrays.  A region outside the limits is
+ * not an error: the host code phases it inside the same call.  No region or no candidate at all is DV_OK without
+ * a device; no device is DV_ERR_NO_DEVICE (there is no CPU fallback). */
+int dv_phase_reads_batch_device(const dv_phasing_region* regions, int32_t n_regions,
+                                const dv_phasing_candidate* candidates, int32_t n_candidates,
+                                const dv_phasing_allele* alleles, int32_t n_alleles, const char* bases, int64_t n_bases,
+                                const int32_t* support_reads, const uint8_t* support_low_quality, int64_t n_support,
+                                int64_t n_reads_total, int32_t min_alleles_to_phase, int32_t* read_phases,
+                                int32_t* allele_phases, uint8_t* allele_flags, dv_phasing_stats* stats, void* stream);
+/* What the calling thread's last dv_phase_reads_batch_device did. */
+int dv_phase_device_last_stats(dv_phasing_stats* out);
+
 /* ---- alt-aligned channel merge (device) --------------------------------------
  * FillPileupArray's diff_channels / base_channels modes (deepvariant/pileup_image_native.h:
  * 246-271) on images that stay in HBM: `images` holds the examples followed, from
