@@ -92,6 +92,39 @@ def hand_made():
   return cases
 
 
+def distinct_kmers(ref, reads, k):
+  """(distinct k-mers, distinct (k+1)-mers) of a window whose bases are all good: the vertices and edges of its graph
+  at k, counted without the library."""
+  seqs = [ref] + [r.aligned_sequence for r in reads if len(r.aligned_sequence) > k]
+  return (len({s[i:i + k] for s in seqs for i in range(len(s) - k + 1)}),
+          len({s[i:i + k + 1] for s in seqs for i in range(len(s) - k)}))
+
+
+def _unrelated_reads(seed, n, length=150):
+  rng = np.random.default_rng(seed)
+  return [read(''.join('ACGT'[int(i)] for i in rng.integers(0, 4, size=length)), name='u%d' % i) for i in range(n)]
+
+
+def limit_windows():
+  """[(name, ref, reads, options)]: windows at and past the limits the device kernel finds at run time
+  (DV_DEBRUIJN_DEVICE_MAX_VERTICES / _EDGES, a full vertex table), all below DV_DEBRUIJN_DEVICE_MAX_BASES.  A random
+  reference and N unrelated random reads of 150 bases have about |ref| - k + 1 + N * (151 - k) distinct k-mers;
+  tests/test_debruijn_compact_cpu.py asserts what each name says on the host's graph.
+    just_under     min_k wins at once with 0.95 * MAX_VERTICES <= V <= MAX_VERTICES: the device's tables at their fullest
+    vertices_over  MAX_VERTICES < V <= 1.2 * MAX_VERTICES under 16384 bases: the table has room, the count decides
+    table_full     a few hundred more distinct k-mers than the table's 16384 slots: the probe runs out (only a few
+                   hundred: every insert into the full table walks all its slots before it gives up)
+    edges_over     a 40-base reference, k = 6 .. 8: at most 4^6 vertices but more than MAX_EDGES edges at k = 6, and
+                   every k cyclic, so the host's answer is "no graph" after the whole schedule"""
+  ref = random_bases(31, 300)
+  wide = options(min_k=12, max_k=24)
+  short = random_bases(36, 40)
+  return [('just_under', ref, _unrelated_reads(32, 56), wide),
+          ('vertices_over', ref, _unrelated_reads(33, 64), wide),
+          ('table_full', ref, _unrelated_reads(34, 118), wide),
+          ('edges_over', short, _unrelated_reads(35, 130), options(min_k=6, max_k=8))]
+
+
 def assembly_window(rng):
   """tests/test_reference_graphs_cpu.py::_assembly_window."""
   n = int(rng.integers(120, 320))

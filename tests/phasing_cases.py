@@ -1,5 +1,6 @@
 """Regions for the batch phasing entry points (dv_phase_reads_batch / _device): the reference's vectors of
-test_direct_phasing_cpu.py as arrays, a seeded generator and named cases.  A case is
+test_direct_phasing_cpu.py as arrays, two seeded generators (small regions; dense ones up to the device limits) and
+named cases.  A case is
   {'name', 'n_reads', 'sites': [(start, end, [(bases, is_ref, [(read, is_low_quality), ...]), ...]), ...]}
 with the entries of a site in the order DirectPhasing.phase builds them (the is_ref entry first).  The checker is
 dv_phase_reads on the region alone (`reference`)."""
@@ -174,6 +175,92 @@ def generated_cases(n):
   return [generated_case(seed) for seed in range(n)]
 
 
+# ---- dense seeded generator: read sets of 1-16 bitmap words, sites of up to MAX_VERTICES vertices
+
+DENSE_READ_COUNTS = (41, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 320, 511, 512, 513, 767, 1000, 1023,
+                     MAX_READS)      # both sides of the 64-read word edges, up to the limit
+_TWO_BASE_TEXTS = [a + b for a in 'ACGT' for b in 'ACGT']
+
+
+def dense_case(seed):
+  """2, 3, 4 or 6 haplotypes (the checker does not care about ploidy) over 3-40 sites, each haplotype with one allele
+  per site, so that many vertices carry real read sets and real edges.  n_reads is DENSE_READ_COUNTS[seed % 21]; the
+  error rate cycles through 0, 0.03 and 0.15, shifted every 21 seeds so that every read count meets each.  Sites: REF
+  with A, C, G and T (5 vertices, "REF" between G and T); REF with 7 two-base texts (MAX_VERTICES); 2-8 two-base texts;
+  2-4 SNP alleles; REF with one allele; generated_case's indel site, whose span shadows its followers.  A read covers
+  a random run of sites, skips a site inside it with probability 0.05 and carries exactly one allele per site (a read
+  under two alleles of one site would send the region to the host code); half of the regions have a cut that no read
+  crosses, which forces a new block.  5 % of the entries are low quality, a -1 entry goes into 10 % of the lists, REF
+  support is cut to 2 or 3 entries at 20 % of the REF sites, and sites left without entries are dropped."""
+  rng = np.random.RandomState(1000003 + seed)
+  n_reads = DENSE_READ_COUNTS[seed % len(DENSE_READ_COUNTS)]
+  error_rate = (0.0, 0.03, 0.15)[(seed + seed // len(DENSE_READ_COUNTS)) % 3]
+  n_sites = int(rng.randint(3, 41))
+  n_haps = int(rng.choice([2, 3, 4, 6]))
+  plan = []      # (start, end, names, the haplotypes' alleles)
+  pos = 100
+  for _ in range(n_sites):
+    kind = str(rng.choice(['ref5', 'ref8', 'texts', 'texts', 'snp', 'ref1', 'indel']))
+    span = 1
+    if kind == 'ref5':
+      names = ['REF', 'A', 'C', 'G', 'T']
+    elif kind == 'ref8':
+      span = 2
+      names = ['REF'] + [_TWO_BASE_TEXTS[int(t)] for t in rng.choice(16, MAX_VERTICES - 1, replace=False)]
+    elif kind == 'texts':
+      span = 2
+      names = [_TWO_BASE_TEXTS[int(t)] for t in rng.choice(16, int(rng.randint(2, MAX_VERTICES + 1)), replace=False)]
+    elif kind == 'snp':
+      names = [str(t) for t in rng.choice(list('ACGT'), int(rng.randint(2, 5)), replace=False)]
+    elif kind == 'ref1':
+      names = ['REF', str(rng.choice(list('ACGT')))]
+    else:
+      span = int(rng.randint(2, 5))
+      names = ['A' * span, 'C']              # the second is a deletion: the site is refused and shadows its span
+    haps = [int(h) for h in rng.randint(len(names), size=n_haps)]
+    plan.append((pos, pos + span, names, haps))
+    pos += int(rng.randint(1, 6)) if kind == 'indel' else span + int(rng.randint(0, 5))
+  cut = int(rng.randint(1, n_sites)) if rng.rand() < 0.5 else None     # no read has sites on both sides of it
+  support = [dict() for _ in plan]          # allele -> [(read, low quality)], in order of first support
+  for read in range(n_reads):
+    hap = int(rng.randint(n_haps))
+    a = int(rng.randint(n_sites))
+    b = int(rng.randint(a, n_sites))
+    if cut is not None and a < cut <= b:
+      if rng.rand() < 0.5:
+        b = cut - 1
+      else:
+        a = cut
+    for s in range(a, b + 1):
+      if a < s < b and rng.rand() < 0.05:
+        continue
+      names, haps = plan[s][2], plan[s][3]
+      allele = haps[hap]
+      if rng.rand() < error_rate:
+        allele = int(rng.randint(len(names)))
+      support[s].setdefault(names[allele], []).append((read, bool(rng.rand() < 0.05)))
+  sites = []
+  for (start, end, names, _), by_allele in zip(plan, support):
+    if not by_allele:
+      continue
+    for infos in by_allele.values():
+      if rng.rand() < 0.1:
+        infos.insert(int(rng.randint(len(infos) + 1)), (-1, False))
+    entries = []
+    if 'REF' in by_allele:
+      infos = by_allele['REF']
+      if rng.rand() < 0.2:
+        infos = infos[:int(rng.choice([2, 3]))]
+      entries.append(('', True, infos))
+    entries += [(name, False, infos) for name, infos in by_allele.items() if name != 'REF']
+    sites.append((start, end, entries))
+  return {'name': 'dense_%d' % seed, 'n_reads': n_reads, 'sites': sites}
+
+
+def dense_cases(n):
+  return [dense_case(seed) for seed in range(n)]
+
+
 # ---- named cases
 
 def two_haplotypes(name, n_reads, n_sites, pairs=None):
@@ -221,6 +308,36 @@ def named_cases():
   noisy = generated_case(7, n_reads=129, n_sites=9)
   noisy['name'] = 'reads_129_noisy'
   return cases + [noisy]
+
+
+def edge_cases():
+  """Inside the device limits, at the edges of the kernel's arithmetic: scores past 2^16, vertices whose read set is
+  empty, sites of one vertex.  (Apart from named_cases, whose length other tests slice.)"""
+  def infos(*reads, low=False):
+    return [(r, low) for r in reads]
+  return [
+      # 70 sites of 1024 continuing reads: the score passes 2^16 at the 64th, and both halves of the reads are phased
+      two_haplotypes('deep_and_long', MAX_READS, 70),
+      # every entry of G at 110 is low quality: its read set is empty, no read reaches it and it is joined to A and C
+      {'name': 'vertex_all_low_quality_middle', 'n_reads': 6, 'sites': [
+          (100, 101, [('A', False, infos(0, 1, 2)), ('C', False, infos(3, 4, 5))]),
+          (110, 111, [('G', False, infos(0, 1, 2, low=True)), ('T', False, infos(3, 4, 5))]),
+          (120, 121, [('A', False, infos(0, 1, 2)), ('C', False, infos(3, 4, 5))])]},
+      # the same at the block's start: starting scores with n1 = 0
+      {'name': 'vertex_all_low_quality_first', 'n_reads': 6, 'sites': [
+          (100, 101, [('A', False, infos(0, 1, 2, low=True)), ('C', False, infos(3, 4, 5))]),
+          (110, 111, [('G', False, infos(0, 1, 2)), ('T', False, infos(3, 4, 5))]),
+          (120, 121, [('A', False, infos(0, 1, 2)), ('C', False, infos(3, 4, 5))])]},
+      # three entries make REF a vertex, but none of them is a read of the region
+      {'name': 'ref_vertex_of_unknown_reads', 'n_reads': 6, 'sites': [
+          (100, 101, [('', True, infos(-1, -1, -1)), ('A', False, infos(0, 1, 2)), ('C', False, infos(3, 4, 5))]),
+          (110, 111, [('', True, infos(-1, -1, -1)), ('G', False, infos(0, 1, 2)), ('T', False, infos(3, 4, 5))])]},
+      # one vertex, one ordered pair
+      {'name': 'single_vertex_sites', 'n_reads': 8, 'sites': [
+          (100, 101, [('', True, infos(0, 1, 2, 3))]),
+          (110, 111, [('G', False, infos(0, 1, 4, 5)), ('T', False, infos(2, 3, 6, 7))]),
+          (120, 121, [('', True, infos(0, 1, 2, 3))])]},
+  ]
 
 
 def at_limit_cases():

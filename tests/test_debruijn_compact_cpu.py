@@ -83,6 +83,44 @@ def test_generated_windows_round_trip(seed):
   assert built > 25 and multi > 8
 
 
+def test_case_lists_keep_their_lengths():
+  assert len(AC.hand_made()) == 22 and len(AC.limit_windows()) == 4
+  assert [len(AC.generated(seed)) for seed in AC.SEEDS] == [40] * 4
+
+
+def test_limit_windows_are_where_their_names_say():
+  """The host's own graphs of AC.limit_windows(): the sizes that decide, in the device route, whether the kernel
+  builds the window or hands it back (tests/test_hip_debruijn.py runs them there)."""
+  max_v, max_e = _lib.DV_DEBRUIJN_DEVICE_MAX_VERTICES, _lib.DV_DEBRUIJN_DEVICE_MAX_EDGES
+  table = 2 * max_v                                    # the kernel's vertex table at these windows' sizes
+  cases = {c[0]: c for c in AC.limit_windows()}
+  graphs = dict(zip(cases, _compact(list(cases.values()))))
+  for name, (_, ref, reads, opts) in cases.items():
+    bases = len(ref) + sum(len(r.aligned_sequence) for r in reads)
+    assert bases <= _lib.DV_DEBRUIJN_DEVICE_MAX_BASES, name          # none is sorted out before the launch
+    assert AC.distinct_kmers(ref, [], opts.min_k)[0] == len(ref) - opts.min_k + 1, name    # repeat-free: min_k is tried
+    print(name, 'bases', bases, 'k', graphs[name].k, 'k_tries', graphs[name].k_tries, 'V', len(graphs[name].vertex_seq),
+          'E', len(graphs[name].edge_from), 'distinct at min_k', AC.distinct_kmers(ref, reads, opts.min_k))
+  for name in ('just_under', 'vertices_over', 'table_full'):
+    g, (_, ref, reads, opts) = graphs[name], cases[name]
+    assert g.k == opts.min_k and g.k_tries == 1, name                                      # one try, acyclic
+    assert (len(g.vertex_seq), len(g.edge_from)) == AC.distinct_kmers(ref, reads, g.k), name
+    _check_round_trip(cases[name], g)
+  g = graphs['just_under']
+  assert 0.95 * max_v <= len(g.vertex_seq) <= max_v and len(g.edge_from) <= max_e
+  g = graphs['vertices_over']
+  assert max_v < len(g.vertex_seq) <= 1.2 * max_v
+  assert len(cases['vertices_over'][1]) + sum(len(r.aligned_sequence) for r in cases['vertices_over'][2]) < table
+  g = graphs['table_full']
+  assert table + 100 <= len(g.vertex_seq) <= table + 600
+  # edges_over: the host finds a cycle at every k; at the first the graph has room for its vertices, not for its edges
+  g, (_, ref, reads, opts) = graphs['edges_over'], cases['edges_over']
+  schedule = list(range(opts.min_k, min(opts.max_k, len(ref) - 1) + 1, opts.step_k))
+  assert g.k == 0 and g.k_tries == len(schedule) == 3 and len(g.vertex_seq) == 0
+  vertices, edges = AC.distinct_kmers(ref, reads, opts.min_k)
+  assert vertices <= max_v < edges <= table
+
+
 def _malformed(compact, **changes):
   arrays = {name: getattr(compact, name).copy() for name in debruijn_graph.CompactGraph.ARRAYS}
   for name, (index, value) in changes.items():

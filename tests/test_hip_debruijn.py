@@ -1,7 +1,8 @@
 """compact_batch_device (csrc/debruijn.hip: every window's graph, the choice of k and the cycle test included, in one
 kernel launch) against compact_batch (the host's own constructor): identical arrays on the hand-made windows of
 tests/assembly_cases.py and on the 160 seeded ones, stats that keep a run that never reached the device from passing,
-and the windows past the kernel's limits built by the host inside the same call."""
+and the windows past the kernel's limits -- the one sorted out before the launch and the ones the kernel finds at run
+time (AC.limit_windows()) -- built by the host inside the same call."""
 import numpy as np
 import pytest
 
@@ -22,8 +23,9 @@ def _bases(case):
   return len(case[1]) + sum(len(r.aligned_sequence) for r in case[2])
 
 
-def _compare(cases, opts):
-  """One batch through both routes; -> (device graphs, stats)."""
+def _compare(cases, opts, on_host=0):
+  """One batch through both routes; -> (device graphs, stats).  on_host: the windows of `cases` that the kernel hands
+  back to the host at run time."""
   want = debruijn_graph.compact_batch(_pairs(cases), opts)
   got, stats = debruijn_graph.compact_batch_device(_pairs(cases), opts, with_stats=True)
   assert len(got) == len(want) == len(cases)
@@ -31,11 +33,12 @@ def _compare(cases, opts):
     assert a.k == b.k and a.k_tries == b.k_tries, case[0]
     for name in debruijn_graph.CompactGraph.ARRAYS:
       assert np.array_equal(getattr(a, name), getattr(b, name)), (case[0], name)
-  # under the limits (checked on the host's graphs), so nothing may have gone back to the host
-  assert max(len(g.vertex_seq) for g in want) <= _lib.DV_DEBRUIJN_DEVICE_MAX_VERTICES
-  assert max(len(g.edge_from) for g in want) <= _lib.DV_DEBRUIJN_DEVICE_MAX_EDGES
+  # with on_host == 0 all are under the limits (checked on the host's graphs), so nothing may have gone back to the host
+  past = sum(len(g.vertex_seq) > _lib.DV_DEBRUIJN_DEVICE_MAX_VERTICES or len(g.edge_from) > _lib.DV_DEBRUIJN_DEVICE_MAX_EDGES
+             for g in want)
+  assert past <= on_host                          # a window past them at a k that did not win has no such graph
   assert max(_bases(c) for c in cases) <= _lib.DV_DEBRUIJN_DEVICE_MAX_BASES
-  assert stats.windows == len(cases) and stats.launches == 1 and stats.windows_on_host == 0
+  assert stats.windows == len(cases) and stats.launches == 1 and stats.windows_on_host == on_host
   assert stats.windows_rejected == 0 and stats.kmers > 0
   assert stats.k_tries == sum(g.k_tries for g in want)
   return got, stats
@@ -113,3 +116,40 @@ def test_a_window_over_the_limit_is_built_by_the_host_inside_the_call():
   got, stats = debruijn_graph.compact_batch_device(_pairs([big]), _LONG, with_stats=True)
   assert AC.same_graph(got[0], want[-1])
   assert stats.windows == 1 and stats.windows_on_host == 1 and stats.launches == 0
+
+
+_HANDED_BACK = ('vertices_over', 'table_full', 'edges_over')       # of AC.limit_windows(), by the kernel at run time
+
+
+def _among_neighbours(group):
+  hand = AC.hand_made()
+  return hand[:3] + group + hand[3:6]
+
+
+def test_windows_at_and_past_the_run_time_limits():
+  """AC.limit_windows() (tests/test_debruijn_compact_cpu.py asserts their sizes on the host's graphs) between small
+  windows, in one launch per set of graph options: just_under is the device's own with its tables at their fullest;
+  a graph past MAX_VERTICES or MAX_EDGES and a vertex table whose probe runs out are found by the kernel, built by the
+  host inside the call, with the host's k_tries, and leave their neighbours' outputs alone."""
+  groups = AC.batches(AC.limit_windows())
+  assert [[c[0] for c in group] for _, group in groups] == [['just_under', 'vertices_over', 'table_full'], ['edges_over']]
+  for opts, group in groups:
+    cases = _among_neighbours(group)
+    on_host = sum(c[0] in _HANDED_BACK for c in cases)
+    assert on_host == len(group) - (group[0][0] == 'just_under') > 0
+    got, _ = _compare(cases, opts, on_host=on_host)      # every window's arrays, the neighbours' included
+    assert [g.k for g in got[3:3 + len(group)]] == [0 if c[0] == 'edges_over' else opts.min_k for c in group]
+    # the same batch again: identical bytes
+    again = debruijn_graph.compact_batch_device(_pairs(cases), opts)
+    for a, b in zip(got, again):
+      assert (a.k, a.k_tries) == (b.k, b.k_tries)
+      for name in debruijn_graph.CompactGraph.ARRAYS:
+        assert getattr(a, name).tobytes() == getattr(b, name).tobytes()
+
+
+def test_a_window_just_under_the_limits_is_the_devices():
+  just_under = AC.limit_windows()[0]
+  assert just_under[0] == 'just_under'
+  got, stats = _compare([just_under], just_under[3])
+  assert got[0].k == just_under[3].min_k and stats.k_tries == 1
+  assert len(got[0].vertex_seq) >= 0.95 * _lib.DV_DEBRUIJN_DEVICE_MAX_VERTICES

@@ -59,6 +59,60 @@ def test_generated_regions(min_alleles_to_phase):
   assert kinds['phased'] >= 100
 
 
+def test_case_lists_keep_their_lengths():
+  """Other tests slice these lists and pin the generated regions: new cases go into lists of their own."""
+  assert len(pc.vector_cases()) == 19 and len(pc.named_cases()) == 8 and len(pc.generated_cases(200)) == 200
+  assert len(pc.at_limit_cases()) == 2 and len(pc.over_limit_cases()) == 4 and len(pc.edge_cases()) == 5
+  assert pc.generated_case(3) == pc.generated_cases(4)[3] and pc.dense_case(5) == pc.dense_cases(6)[5]
+  assert [c['n_reads'] for c in pc.dense_cases(21)] == list(pc.DENSE_READ_COUNTS)
+
+
+@pytest.mark.parametrize('min_alleles_to_phase', [1, 2, 3])
+def test_dense_regions(min_alleles_to_phase):
+  cases = pc.dense_cases(126)
+  check_batch(cases, min_alleles_to_phase)           # regions_on_host == 0: all of them are the device's
+  # the generator reaches what it is for
+  words, site_sizes = {}, {}
+  both_phases = blocks = 0
+  for case in cases:
+    n_words = (case['n_reads'] + 63) // 64
+    words[n_words] = words.get(n_words, 0) + 1
+    for size in {len(entries) for _, _, entries in case['sites']}:
+      site_sizes[size] = site_sizes.get(size, 0) + 1
+    assert max(len(entries) for _, _, entries in case['sites']) <= pc.MAX_VERTICES
+    phases, _, flags = pc.reference(case, min_alleles_to_phase)
+    both_phases += {1, 2} <= set(phases.tolist())
+    at = np.cumsum([0] + [len(entries) for _, _, entries in case['sites']])
+    blocks += sum(bool(flags[a:b].any()) for a, b in zip(at[:-1], at[1:])) >= 2
+  print('words per read set -> cases:', dict(sorted(words.items())))
+  print('entries per site -> cases:', dict(sorted(site_sizes.items())))
+  print('cases with both phases: %d, with two or more first-in-block allele pairs: %d' % (both_phases, blocks))
+  assert all(words.get(n, 0) >= 5 for n in (1, 2, 3, 4, 5, 8, 9, 12, 16)), words
+  assert site_sizes.get(8, 0) >= 15 and all(site_sizes.get(n, 0) >= 10 for n in (5, 6, 7)), site_sizes
+  assert both_phases >= 100 and blocks >= 40
+
+
+def test_edge_cases():
+  cases = pc.edge_cases()
+  for m in (1, 2, 3):
+    check_batch(cases, m)
+  by_name = {c['name']: c for c in cases}
+  # what the names promise, in the checker's own answer
+  phases, allele_phases, _ = pc.reference(by_name['deep_and_long'], 1)
+  assert set(phases[0::2].tolist()) | set(phases[1::2].tolist()) == {1, 2} and len(set(phases[0::2].tolist())) == 1
+  assert len(set(phases[1::2].tolist())) == 1 and (len(by_name['deep_and_long']['sites']) - 1) * pc.MAX_READS > 1 << 16
+  for name in ('vertex_all_low_quality_middle', 'vertex_all_low_quality_first'):
+    phases, allele_phases, _ = pc.reference(by_name[name], 1)
+    assert (allele_phases >= 0).all(), name             # the vertex without reads is a vertex all the same
+    assert phases[3] != 0 and phases[3] == phases[4] == phases[5], name
+    assert phases[0] == phases[1] == phases[2] and phases[0] not in (0, phases[3]), name
+  phases, allele_phases, _ = pc.reference(by_name['ref_vertex_of_unknown_reads'], 1)
+  assert allele_phases[0] >= 0 and allele_phases[3] >= 0             # REF is in the graph at both sites
+  assert phases[0] == phases[1] == phases[2] != 0 and phases[3] == phases[4] == phases[5] not in (0, phases[0])
+  phases, allele_phases, _ = pc.reference(by_name['single_vertex_sites'], 1)
+  assert allele_phases.tolist()[0] >= 0 and allele_phases.tolist()[3] >= 0 and set(phases.tolist()) >= {1, 2}
+
+
 def test_named_cases():
   check_batch(pc.named_cases(), 1)
   check_batch(pc.named_cases(), 2)
