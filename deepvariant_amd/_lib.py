@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     'dv_fast_pass_batch', 'dv_fast_pass_batch_device', 'dv_fast_pass_device_last_stats',
     'dv_trim_reads_batch', 'dv_trim_reads_batch_device', 'dv_trimmed_reads_arrays', 'dv_trimmed_reads_free',
     'dv_trim_device_last_stats',
+    'dv_alt_align_batch', 'dv_alt_align_batch_device', 'dv_alt_aligned_arrays', 'dv_alt_aligned_free',
+    'dv_alt_align_device_last_stats',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
     'dv_debruijn_device_last_stats', 'dv_debruijn_from_compact', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
@@ -234,6 +236,23 @@ class DvTrimmedReadsView(C.Structure):
 class DvTrimStats(C.Structure):
   _fields_ = [('pairs_tested', C.c_int64), ('pairs_kept', C.c_int64), ('words_read', C.c_int64),
               ('words_written', C.c_int64), ('launches', C.c_int64)]
+
+
+class DvAltAlignItem(C.Structure):
+  _fields_ = [('first_row', C.c_int32), ('n_rows', C.c_int32), ('target', C.c_int32), ('read_size', C.c_int32),
+              ('ref_start', C.c_int64), ('reserved', C.c_int64)]
+
+
+class DvAltAlignedView(C.Structure):
+  _fields_ = [('n_items', C.c_int32), ('n_pairs', C.c_int32), ('n_words', C.c_int64),
+              ('item_pair_off', C.c_void_p), ('status', C.c_void_p), ('position', C.c_void_p),
+              ('cigar_off', C.c_void_p), ('cigar', C.c_void_p)]
+
+
+class DvAltAlignStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('items', 'items_on_host', 'pairs', 'pairs_fast', 'pairs_swept',
+                                       'pairs_swept_on_host', 'pairs_traced_on_host', 'status0', 'status1', 'status2',
+                                       'words_written', 'launches')]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -497,6 +516,13 @@ def lib():
     l.dv_trimmed_reads_free.argtypes = [C.c_void_p]
     l.dv_trimmed_reads_free.restype = None
     l.dv_trim_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_alt_align_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    l.dv_alt_align_batch_device.argtypes = l.dv_alt_align_batch.argtypes + [C.c_void_p]
+    l.dv_alt_aligned_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_alt_aligned_free.argtypes = [C.c_void_p]
+    l.dv_alt_aligned_free.restype = None
+    l.dv_alt_align_device_last_stats.argtypes = [C.c_void_p]
     l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -312,3 +312,104 @@ def trim_table(table, windows: Sequence, device: bool = True, stream: int = 0, w
   off = d['window_row_off'].tolist()
   ranges = list(zip(off[:-1], off[1:]))
   return (trimmed, ranges, d.get('stats')) if with_stats else (trimmed, ranges)
+
+
+# ------------------------------------------------------------------ alt-aligned realignment on a packed table
+def alt_align_arrays(table, items: Sequence, targets: Sequence, aln_config: Optional[dict] = None,
+                     device: bool = True, stream: int = 0) -> dict:
+  """RealignReadsToHaplotype for many (candidate, sample, alt allele) items over one table of trimmed reads, in
+  libdvhip (include/dvhip.h dv_alt_align_batch_device: fast pass, sweeps and the finish kernels; device=False: the
+  host code, FastPassAligner item by item).  `items`: (first_row, n_rows, target index, ref_start, read_size) each;
+  `targets`: the haplotypes (str or bytes); `aln_config`: fields of dv_aligner_options (force_alignment is set here).
+  -> the arrays of dv_alt_aligned_view, copied, and `stats` (device only)."""
+  import ctypes as C
+  from deepvariant_amd import _lib
+  lib = _lib.lib()
+  keep = [np.ascontiguousarray(table.read_seq_off, np.uint32), np.ascontiguousarray(table.bases, np.uint8)]
+  b = _lib.DvBatch()
+  b.memory, b.n_reads = _lib.DV_MEM_HOST, int(table.n_reads)
+  b.read_seq_off, b.bases = keep[0].ctypes.data, keep[1].ctypes.data
+  b.n_bases = int(keep[0][-1]) if len(keep[0]) else 0
+  descs = (_lib.DvAltAlignItem * max(len(items), 1))()
+  for k, (first_row, n_rows, target, ref_start, read_size) in enumerate(items):
+    descs[k] = _lib.DvAltAlignItem(int(first_row), int(n_rows), int(target), int(read_size), int(ref_start), 0)
+  raw = [t.encode('latin-1') if isinstance(t, str) else bytes(t) for t in targets]
+  off = np.zeros(len(raw) + 1, np.int64)
+  np.cumsum([len(t) for t in raw], out=off[1:])
+  blob = b''.join(raw)
+  opt = _lib.DvAlignerOptions()
+  for name, value in (aln_config or {}).items():
+    setattr(opt, name, value)
+  opt.force_alignment = 1
+  handle = C.c_void_p()
+  args = (C.byref(b), len(items), descs, len(raw), blob, off.ctypes.data, C.byref(opt), C.byref(handle))
+  if device:
+    _lib.check(lib.dv_alt_align_batch_device(*args, C.c_void_p(stream or None)))
+  else:
+    _lib.check(lib.dv_alt_align_batch(*args))
+  try:
+    view = _lib.DvAltAlignedView()
+    _lib.check(lib.dv_alt_aligned_arrays(handle, C.byref(view)))
+
+    def arr(ptr, dtype, count):
+      if not count:
+        return np.zeros(0, dtype)
+      buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+      return np.frombuffer(buf, dtype=dtype, count=count).copy()
+
+    n = view.n_pairs
+    out = dict(item_pair_off=arr(view.item_pair_off, np.int32, view.n_items + 1), status=arr(view.status, np.int32, n),
+               position=arr(view.position, np.int64, n), cigar_off=arr(view.cigar_off, np.uint32, n + 1),
+               cigar=arr(view.cigar, np.uint32, view.n_words))
+  finally:
+    lib.dv_alt_aligned_free(handle)
+  if device:
+    st = _lib.DvAltAlignStats()
+    _lib.check(lib.dv_alt_align_device_last_stats(C.byref(st)))
+    out['stats'] = {name: int(getattr(st, name)) for name, _ in st._fields_}   # pylint: disable=protected-access
+  return out
+
+
+def alt_align_table(trimmed_table, items: Sequence, targets: Sequence, aln_config: Optional[dict] = None,
+                    device: bool = True, stream: int = 0, with_stats: bool = False):
+  """-> (the ReadTable of every item's realigned reads, [(lo, hi) rows per item][, stats]): field for field what
+  ReadTable.from_reads(kept objects, alignment_positions=untrimmed starts) gives for the object route
+  (fast_pass_aligner.realign_reads_to_haplotype item after item): rows with a new alignment get its position,
+  CIGAR and end, rows whose alignment was kept stay as trimmed, rows the aligner dropped are absent;
+  read_sort_pos is the trimmed table's.  Array operations only.  A table with per-read aux pixels or per-base aux
+  planes is refused, as trim_table refuses it."""
+  from deepvariant_amd import packing
+  table = trimmed_table
+  if table.read_aux is not None or any(getattr(table, 'base_aux%d' % k) is not None for k in range(3)):
+    raise ValueError('alt_align_table: the table carries per-read aux pixels or per-base aux planes; those channels '
+                     'are computed on the trimmed sequence, which only the Read-object path does')
+  d = alt_align_arrays(table, items, targets, aln_config, device=device, stream=stream)
+  n_items = len(items)
+  first = np.array([it[0] for it in items], np.int64).reshape(n_items)
+  pair_off = d['item_pair_off'].astype(np.int64)
+  counts = np.diff(pair_off)
+  # the trimmed row of every pair: item order, then row order
+  src_all = np.arange(int(pair_off[-1]), dtype=np.int64) + np.repeat(first - pair_off[:-1], counts)
+  seq_len = np.diff(table.read_seq_off.astype(np.int64))
+  kept = (d['status'] != 2) & (seq_len[src_all] > 0)
+  kept_before = np.zeros(len(kept) + 1, np.int64)
+  np.cumsum(kept, out=kept_before[1:])
+  ranges = list(zip(kept_before[pair_off[:-1]].tolist(), kept_before[pair_off[1:]].tolist()))
+  out = table.take(src_all[kept])
+  n = out.n_reads
+  flags = out.read_flags
+  for name, bit in (('mod_5mc', packing.DV_READ_HAS_5MC), ('mod_6ma', packing.DV_READ_HAS_6MA)):
+    if getattr(out, name) is not None and not (flags & bit).any():
+      setattr(out, name, None)
+  if out.read_sort_pos is None and n:
+    out.read_sort_pos = table.read_pos[src_all[kept]].astype(np.int32)
+  if not n:
+    out.read_sort_pos = None
+  moved = d['status'][kept] == 1
+  if moved.any():
+    pairs = np.nonzero(kept)[0][moved]            # the call's pairs with a new alignment, in order
+    coff = d['cigar_off'].astype(np.int64)
+    # only status-1 pairs hold words, so their ranges are contiguous in `cigar`, in order
+    new_off = np.concatenate([coff[pairs], coff[pairs[-1] + 1:pairs[-1] + 2]])
+    out = out.with_alignments_csr(np.nonzero(moved)[0], d['position'][pairs], new_off, d['cigar'])
+  return (out, ranges, d.get('stats')) if with_stats else (out, ranges)

@@ -354,15 +354,17 @@ class RegionProcessor:
   # calling configuration, window-trimmed pileups (trim_reads_for_pileup /
   # keep_only_window_spanning_reads: alt_aligned_pileup_lib.trim_table) and, behind
   # DV_PHASE_TABLES=1 (read at each call, as DV_REALIGN_DEVICE is), read phasing (phase_reads:
-  # _phase_tables below); everything that works on Read objects (spliced-read splitting,
-  # alt-aligned pileups, channels with per-read aux pixels) takes the object path above.
+  # _phase_tables below) and, behind DV_ALT_ALIGN_TABLES=1 (read at each call too), alt-aligned
+  # pileups (alt_aligned_pileup_lib.alt_align_table realigns the trimmed table to the alt
+  # haplotypes); everything that works on Read objects (spliced-read splitting, channels with
+  # per-read aux pixels) takes the object path above.
   def table_path_ok(self) -> bool:
     import os
     from deepvariant_amd import alt_aligned_pileup_lib as aap
     po, gen = self.processor_options, self.generator
     return ((not po.phase_reads or os.environ.get('DV_PHASE_TABLES') == '1') and
             not (self.realigner is not None and self.realigner.config.split_skip_reads) and
-            gen._alt_mode == aap.NONE and                                      # pylint: disable=protected-access
+            (gen._alt_mode == aap.NONE or os.environ.get('DV_ALT_ALIGN_TABLES') == '1') and   # pylint: disable=protected-access
             not gen._encoder_api._need_aux and not gen._encoder_api._need_seq_aux)   # pylint: disable=protected-access
 
   def realign_table(self, table, region: T.Range):

@@ -243,6 +243,7 @@ class ExamplesGenerator:
         starts[s].extend(original)
         ranges[(ci, s)] = (lo, lo + len(kept))
     new_tables = []
+    self._trimmed_tables = [None] * len(reads_per_sample)   # the packed samples', for _realign_for_alt_images
     for s, reads in enumerate(reads_per_sample):
       if not packed[s]:
         new_tables.append(self._table_of(trimmed[s], starts[s]))
@@ -259,7 +260,8 @@ class ExamplesGenerator:
       if table.read_sort_pos is None:
         table.read_sort_pos = table.read_pos.copy()
       new_tables.append(table)
-      trimmed[s] = starts[s] = None      # no Read objects: _realign_for_alt_images cannot take this sample
+      self._trimmed_tables[s] = table
+      trimmed[s] = starts[s] = None      # no Read objects: _realign_for_alt_images takes the table (DV_ALT_ALIGN_TABLES=1)
     self._trimmed_reads, self._trimmed_starts = trimmed, starts
     return new_tables, ranges
 
@@ -295,6 +297,12 @@ class ExamplesGenerator:
     reads_out = [[] for _ in range(n_samples)]
     starts_out = [[] for _ in range(n_samples)]
     ranges = {}
+    # a packed sample (DV_ALT_ALIGN_TABLES=1, read at each call): its items are gathered here, in the loops' order,
+    # and realigned in one call below (alt_aligned_pileup_lib.alt_align_table, csrc/alt_align.hip)
+    on_tables = os.environ.get('DV_ALT_ALIGN_TABLES') == '1'
+    table_items = [[] for _ in range(n_samples)]     # (first_row, n_rows, target, ref_start, read_size)
+    table_targets = [[] for _ in range(n_samples)]
+    table_keys = [[] for _ in range(n_samples)]      # (candidate, sample, alt), haplotype window
     for ci, cand in enumerate(candidates):
       if not need_alt[ci]:
         continue
@@ -302,10 +310,21 @@ class ExamplesGenerator:
       for s in sample_order:
         if (ci, s) not in trim_ranges or not self._sample_needs_alt(self._options.sample_options[s]):
           continue
-        if self._trimmed_reads[s] is None:
-          raise NotImplementedError('alt-aligned pileups realign the trimmed reads as Read objects '
-                                    '(RealignReadsToHaplotype), not a packed table')
         lo, hi = trim_ranges[(ci, s)]
+        if self._trimmed_reads[s] is None:
+          if not on_tables:
+            raise NotImplementedError('alt-aligned pileups realign the trimmed reads as Read objects '
+                                      '(RealignReadsToHaplotype), not a packed table')
+          table = self._trimmed_tables[s]
+          first_len = int(table.read_seq_off[lo + 1]) - int(table.read_seq_off[lo]) if hi > lo else 0
+          for alt in variant.alternate_bases:
+            haplotype, ref_start, _ = aap.create_haplotype(self._ref, variant, alt, self._half_width)
+            if len(haplotype) < pic.width:
+              continue
+            table_items[s].append((lo, hi - lo, len(table_targets[s]), ref_start, first_len if first_len > 15 else 200))
+            table_targets[s].append(haplotype)
+            table_keys[s].append(((ci, s, alt), haplotype[:pic.width]))
+          continue
         trimmed = self._trimmed_reads[s][lo:hi]
         starts = self._trimmed_starts[s][lo:hi]
         for alt in variant.alternate_bases:
@@ -320,7 +339,19 @@ class ExamplesGenerator:
               reads_out[s].append(read)
               starts_out[s].append(start)
           ranges[(ci, s, alt)] = (a, len(reads_out[s]), haplotype[:pic.width])
-    return [self._table_of(reads_out[s], starts_out[s]) for s in range(n_samples)], ranges
+    alt_tables = []
+    for s in range(n_samples):
+      if self._trimmed_reads[s] is not None or not table_items[s]:
+        alt_tables.append(self._table_of(reads_out[s], starts_out[s]))
+        continue
+      # the table route: one call per sample over every item; there is no host fallback
+      table, rows = aap.alt_align_table(self._trimmed_tables[s], table_items[s], table_targets[s], cfg, device=True)
+      for (key, window), (a, b) in zip(table_keys[s], rows):
+        ranges[key] = (a, b, window)
+      if table.read_sort_pos is None:
+        table.read_sort_pos = table.read_pos.copy()
+      alt_tables.append(table)
+    return alt_tables, ranges
 
   @staticmethod
   def _sample_needs_alt(so) -> bool:

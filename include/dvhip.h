@@ -701,6 +701,81 @@ typedef struct dv_trim_stats {
 /* What the calling thread's last dv_trim_reads_batch_device did. */
 int dv_trim_device_last_stats(dv_trim_stats* out);
 
+/* ---- alt-aligned realignment on a packed table --------------------------------------
+ * RealignReadsToHaplotype (deepvariant/alt_aligned_pileup_lib.cc:278-313) for many (candidate, sample, alt allele)
+ * items over one table of trimmed reads.  Per item the reference builds a FastPassAligner whose one haplotype IS its
+ * reference (the target), with force_alignment and no reference padding: the haplotype is never discarded, its CIGAR
+ * to the reference is one match run, the score threshold decides nothing.  For pair (item t, read R of L bytes --
+ * upper-cased by the call --, target T of n bytes, taken as given):
+ *   - choice: the fast pass' position p (dv_fast_pass_batch's contract, T both haplotype and reference) gives
+ *     read-to-haplotype "<L>=" at p; otherwise dv_local_align(T, R) with score > 0 gives p = (uint16_t)ref_begin and
+ *     its CIGAR, soft clips included; otherwise status 2;
+ *   - merge: CalculateReadToRefAlignment against "<n>=": p >= n is status 0; a leading soft clip is taken as it is;
+ *     every other operation of the read is cut where the n - p haplotype bases end (an insertion takes none of them)
+ *     and goes through MergeCigarOp -- lengths capped so that the read-consuming ones sum to L at most, an insertion
+ *     beside a deletion cancelling base by base into matches planted in front of the indel --; past the haplotype's
+ *     end the remaining operations are merged whole, a cut soft clip's tail too; a cut operation of any other kind
+ *     left over clears the CIGAR (status 0);
+ *   - normalisation: IsAlignmentNormalized of the merged CIGAR against T at offset p and the read's bytes, unless
+ *     options->normalize_reads; not normalised is status 0;
+ *   - result: status 1, position = ref_start + p, the merged CIGAR.  An empty CIGAR is status 0.
+ * `reads` is a DV_MEM_HOST dv_batch of which only bases and read_seq_off are read (alt_aligned_pileup_lib.trim_table's
+ * output).  Targets are raw bytes: target s is target_bytes[target_off[s], target_off[s + 1]).  Items may share rows
+ * (two alts of one candidate name the same range).  options: as dv_aligner_create (0 keeps the class default), with
+ * read_size taken from each item; force_alignment must be 1 and ref_prefix_len / ref_suffix_len 0.
+ * Null pointers, negative counts, descending offsets, a row range or target index outside its table, a negative
+ * ref_start, a table not in host memory, options outside the above or that the class refuses:
+ * DV_ERR_INVALID_ARGUMENT before any device work.  On any error *out is NULL and nothing stays allocated. */
+typedef struct dv_alt_align_item {
+  int32_t first_row, n_rows;   /* its reads: rows [first_row, first_row + n_rows) of `reads` */
+  int32_t target;              /* index into the target table */
+  int32_t read_size;           /* AlignerOptions.read_size: the first read's length if it exceeds 15, else 200 */
+  int64_t ref_start;           /* reference coordinate of target[0] */
+  int64_t reserved;
+} dv_alt_align_item;
+typedef struct dv_alt_aligned dv_alt_aligned;   /* owns the host arrays of one call's result */
+typedef struct dv_alt_aligned_view {            /* views into the result; valid until dv_alt_aligned_free */
+  int32_t n_items;
+  int32_t n_pairs;                 /* (item, row) pairs: item order, then row order */
+  int64_t n_words;
+  const int32_t* item_pair_off;    /* [n_items + 1]: item t's pairs are [off[t], off[t + 1]) */
+  const int32_t* status;           /* [n_pairs] 0 / 1 / 2 as dv_realigned_read */
+  const int64_t* position;         /* [n_pairs] status 1 only, else 0 */
+  const uint32_t* cigar_off;       /* [n_pairs + 1] into cigar; words only for status 1 */
+  const uint32_t* cigar;           /* [n_words] dv_batch's encoding */
+} dv_alt_aligned_view;
+/* Host code (csrc/alt_align.hip): FastPassAligner::AlignReads item by item, what dv_aligner_* does for Read objects.
+ * The checker of the device route, and the route of the items outside its limits. */
+int dv_alt_align_batch(const dv_batch* reads, int32_t n_items, const dv_alt_align_item* items, int32_t n_targets,
+                       const char* target_bytes, const int64_t* target_off, const dv_aligner_options* options,
+                       dv_alt_aligned** out);
+/* The same on the device: the fast pass of every item in one launch (csrc/fast_pass.hip), the Smith-Waterman sweeps
+ * of every pair it did not place in one launch (csrc/local_align.hip; trace-back as DV_REALIGN_DEVICE_TRACEBACK says),
+ * and three launches (count, scan, emit; one lane per pair) that merge, check and compact every pair's CIGAR; three
+ * round trips on `stream` (NULL = a non-blocking stream the library owns); identical arrays.  An item whose target is
+ * longer than DV_FAST_PASS_DEVICE_MAX_HAPLOTYPE (or reaches 65,535 bytes: positions are uint16_t) is not an error:
+ * the host code runs it inside the call; so is a pair outside DV_LOCAL_ALIGN_DEVICE_MAX_*.  No pair at all is DV_OK
+ * without a device; no device is DV_ERR_NO_DEVICE (there is no CPU fallback). */
+int dv_alt_align_batch_device(const dv_batch* reads, int32_t n_items, const dv_alt_align_item* items,
+                              int32_t n_targets, const char* target_bytes, const int64_t* target_off,
+                              const dv_aligner_options* options, dv_alt_aligned** out, void* stream);
+int dv_alt_aligned_arrays(const dv_alt_aligned* a, dv_alt_aligned_view* out);
+void dv_alt_aligned_free(dv_alt_aligned* a);
+typedef struct dv_alt_align_stats {
+  int64_t items;              /* items asked for */
+  int64_t items_on_host;      /* of them outside the fast pass' limits: run whole by the host code */
+  int64_t pairs;              /* (item, row) pairs */
+  int64_t pairs_fast;         /* placed by the fast pass */
+  int64_t pairs_swept;        /* sent through Smith-Waterman (pairs = pairs_fast + pairs_swept) */
+  int64_t pairs_swept_on_host;   /* of them outside the sweep kernel's limits, or of an item on the host */
+  int64_t pairs_traced_on_host;  /* swept on the device, holding an alignment, traced back by the host code */
+  int64_t status0, status1, status2;
+  int64_t words_written;
+  int64_t launches;           /* kernel launches: fast pass + sweeps + the three finish kernels */
+} dv_alt_align_stats;
+/* What the calling thread's last dv_alt_align_batch_device did. */
+int dv_alt_align_device_last_stats(dv_alt_align_stats* out);
+
 /* ---- local assembly for the window realigner ------------------------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
  * CandidateHaplotypes, GraphViz; python binding deepvariant/realigner/python/
