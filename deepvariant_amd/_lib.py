@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     'dv_cram_read_region', 'dv_cram_header', 'dv_read_table_aux_planes',
     'dv_pack_region', 'dv_packed_region_fill_batch', 'dv_packed_region_items',
     'dv_packed_region_free',
+    'dv_pack_regions_device', 'dv_packed_regions_fill_batch', 'dv_packed_regions_download', 'dv_packed_regions_items',
+    'dv_packed_regions_free', 'dv_pack_regions_device_last_stats',
     'dv_aligner_create', 'dv_aligner_destroy', 'dv_aligner_set_reference',
     'dv_aligner_set_haplotypes', 'dv_aligner_set_reads', 'dv_aligner_align_reads',
     'dv_aligner_stage', 'dv_aligner_fast_align', 'dv_aligner_haplotype_info',
@@ -231,6 +233,32 @@ class DvTrimmedReadsView(C.Structure):
   _fields_ = [('n_windows', C.c_int32), ('n_rows', C.c_int32), ('n_words', C.c_int64),
               ('window_row_off', C.c_void_p), ('src_row', C.c_void_p), ('pos', C.c_void_p), ('end', C.c_void_p),
               ('read_trim', C.c_void_p), ('new_len', C.c_void_p), ('cigar_off', C.c_void_p), ('cigar', C.c_void_p)]
+
+
+class DvPackRows(C.Structure):
+  _fields_ = [('n_reads', C.c_int32), ('read_pos', C.c_void_p), ('read_end', C.c_void_p), ('read_key', C.c_void_p)]
+
+
+class DvPackRegionSlice(C.Structure):
+  _fields_ = [('read_first', C.c_int32), ('n_reads', C.c_int32), ('cand_first', C.c_int32), ('n_cands', C.c_int32)]
+
+
+class DvPackRegionsOptions(C.Structure):
+  _fields_ = [('width', C.c_int32), ('read_overlap_buffer_bp', C.c_int32), ('pileup_height', C.c_int32),
+              ('n_candidates', C.c_int32), ('n_combo_masks', C.c_uint32), ('n_support', C.c_uint32),
+              ('example_bytes', C.c_uint64), ('mean_coverage', C.c_float)]
+
+
+class DvPackedRegionsView(C.Structure):
+  _fields_ = [('n_items', C.c_int32), ('n_list', C.c_uint32), ('max_list_len', C.c_uint32)] + [
+      (name, C.c_void_p) for name in (
+          'item_variant_start', 'item_image_start', 'item_ref_idx', 'item_list_off', 'item_height', 'item_out_off',
+          'item_mean_coverage', 'item_candidate', 'item_combo', 'list_read', 'list_code', 'list_group')]
+
+
+class DvPackDeviceStats(C.Structure):
+  _fields_ = [('regions', C.c_int64), ('candidates', C.c_int64), ('items', C.c_int64), ('list_entries', C.c_int64),
+              ('regions_unsorted', C.c_int64), ('launches', C.c_int64)]
 
 
 class DvTrimStats(C.Structure):
@@ -479,6 +507,13 @@ def lib():
     l.dv_packed_region_fill_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     l.dv_packed_region_items.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_packed_region_free.argtypes = [C.c_void_p]
+    l.dv_pack_regions_device.argtypes = [C.c_int32] + [C.c_void_p] * 9
+    l.dv_packed_regions_fill_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    l.dv_packed_regions_download.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_packed_regions_items.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    l.dv_packed_regions_free.argtypes = [C.c_void_p]
+    l.dv_packed_regions_free.restype = None
+    l.dv_pack_regions_device_last_stats.argtypes = [C.c_void_p]
     l.dv_read_table_ends.restype = C.c_void_p
     l.dv_read_table_ends.argtypes = [C.c_void_p]
     l.dv_read_table_free.argtypes = [C.c_void_p]

@@ -561,11 +561,14 @@ class AlleleCounter:
       c.selected = sorted(selected, key=lambda a: (a.bases, a.type))     # SumAlleleCounts' map order
       # read_alleles in the map's order: a key stands where it was first inserted, with its last value
       read_alleles: Dict[str, Optional[Allele]] = {}
+      read_rows: Dict[str, int] = {}           # the event's row beside each entry: the row its value came from
       for (_, read, _, packed), word in zip(ev[lo:hi].tolist(), words[lo:hi].tolist()):
         key = keys[read]
         if word == EVENT_OVERWRITTEN:
           read_alleles.setdefault(key, None)
+          read_rows.setdefault(key, read)
           continue
+        read_rows[key] = read
         type_k, low = (packed >> 28) & 7, bool(packed >> 31)
         if type_k == REFERENCE:
           read_alleles[key] = Allele(c.ref_base, REFERENCE, 1, low)
@@ -574,6 +577,7 @@ class AlleleCounter:
         else:
           read_alleles[key] = Allele(None, type_k, 1, low)
       c.read_alleles = read_alleles
+      c.read_rows = read_rows
       out.append(c)
     return out
 

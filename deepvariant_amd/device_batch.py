@@ -82,6 +82,22 @@ class DeviceBatch:
     self.c.max_cigar_ops, self.c.max_item_height = host_c.max_cigar_ops, host_c.max_item_height
     self.input_bytes = int(self.storage.numel())
 
+  @classmethod
+  def from_packed_regions(cls, batch: packing.PackedBatch, packed: 'packing.PackedRegions', device: torch.device,
+                          reference_band_height: int, use_groups: bool, max_item_height: int) -> 'DeviceBatch':
+    """A batch whose read table and reference windows come from `batch` -- a table-only PackedBatch (the merged
+    table of a batch of regions, their reference windows, n_items 0), checked and uploaded as usual -- and whose
+    item / list arrays are the ones dv_pack_regions_device left on the device (`packed`, kept alive here).  The
+    device wrote those arrays from rows the library checked against the table's slices."""
+    if batch.n_items:
+      raise ValueError('from_packed_regions takes a PackedBatch without items')
+    self = cls(batch, device, reference_band_height)
+    self.packed = packed
+    packed.fill_batch(self.c, use_groups)
+    self.n_items = int(self.c.n_items)
+    self.c.max_item_height = int(max_item_height)
+    return self
+
   def encode(self, encoder, out_channels: int, out: torch.Tensor,
              rows: torch.Tensor = None, stream=None):
     if stream is None:

@@ -243,6 +243,10 @@ class DeepVariantCall:
   ref_support_ext: List[ReadSupport] = field(default_factory=list)
   make_examples_alt_allele_indices: List[AltAlleleIndices] = field(
       default_factory=list)
+  # Not a proto field.  allele_support by ROW: support_rows[allele][j] is the row, in the table the region is packed
+  # from, of the read allele_support[allele].read_names[j] names (filled by the device caller's route only; None
+  # for every other call, whose names the device packer resolves through packing.support_arrays).
+  support_rows: Optional[Dict[str, 'np.ndarray']] = field(default=None, compare=False, repr=False)
 
 
 @dataclass

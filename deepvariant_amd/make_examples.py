@@ -595,6 +595,19 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
       stats['wait_for_prepared_batches_s'] = stats.get('wait_for_prepared_batches_s', 0.0) + time.perf_counter() - t_wait
       pending = start_batch(at + _REGION_BATCH) if at + _REGION_BATCH < len(pieces) else None
       called = proc.process_tables(batch, tables, realigned_tables)       # the batch's allele counts: one device call
+      if model is not None and packing.pack_device_enabled():
+        # DV_PACK_DEVICE=1: the batch's regions packed and drawn together (one pack call, one encoder launch)
+        for in_table, (candidates, _) in zip(tables, called):
+          stats['n_regions'] += 1
+          stats['n_reads'] += in_table.n_reads
+          stats['n_candidates'] += len(candidates)
+        proc.queue_regions_candidates(called, model)
+        if proc.n_queued_examples >= _CLASSIFY_AT:
+          for records in proc.flush_queue(model):
+            for rec in records:
+              writer.write(rec)
+            stats['n_examples'] += len(records)
+        continue
       for region, in_table, (candidates, realigned) in zip(batch, tables, called):
         stats['n_regions'] += 1
         stats['n_reads'] += in_table.n_reads

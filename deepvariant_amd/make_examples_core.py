@@ -455,10 +455,15 @@ class RegionProcessor:
     else:
       run_batch(counters, **self._device_call())
     phased = self._phase_tables(slots, counters, in_region, rows_of, realigned_tables) if po.phase_reads else {}
-    for k, counter in zip(slots, counters):
+    for k, counter, rows in zip(slots, counters, rows_of):
       candidates = self.variant_caller.calls_from_allele_counter(counter)
       if effective[k] is not regions[k]:              # filter_candidates_by_region
         candidates = [c for c in candidates if regions[k].start <= c.variant.start < regions[k].end]
+      for c in candidates:
+        # the caller's rows are those of the counter's table (the region's rows of the realigned one): as rows of
+        # the table the region is packed from
+        if c.support_rows is not None:
+          c.support_rows = {allele: rows[r] for allele, r in c.support_rows.items()}
       out[k] = (candidates, phased.get(k, realigned_tables[k]))
     return out
 
@@ -516,6 +521,25 @@ class RegionProcessor:
     self._queue.append((candidates, plan, images))
     self.n_queued_examples += len(plan)
     return candidates
+
+  def queue_regions_candidates(self, called, model) -> None:
+    """queue_region_candidates for a batch of regions (`called`: process_tables' [(candidates, realigned table)]):
+    the regions that qualify are packed on the device by one call and drawn by one encoder launch
+    (ExamplesGenerator.encode_regions_on_device, DV_PACK_DEVICE=1); the others take the per-region call.  The
+    queue gets the same (candidates, plan, images) entries, in region order."""
+    gen = self.generator
+    batched = [k for k, (candidates, realigned) in enumerate(called) if candidates and gen.device_pack_ok(realigned)]
+    drawn = {}
+    if batched:
+      results = gen.encode_regions_on_device([called[k] for k in batched], model.input_shape)
+      drawn = dict(zip(batched, results))
+    for k, (candidates, realigned) in enumerate(called):
+      if k in drawn:
+        images, plan = drawn[k]
+        self._queue.append((candidates, plan, images))
+        self.n_queued_examples += len(plan)
+      else:
+        self.queue_region_candidates(candidates, realigned, model)
 
   def flush_queue(self, model) -> List[List[bytes]]:
     """-> the CallVariantsOutput records of every queued region, in queue order.  Examples are

@@ -651,6 +651,79 @@ class ExamplesGenerator:
       self._merge_alt_channels_device(flat, image_shape)
     return images, plan
 
+  def device_pack_ok(self, reads=None) -> bool:
+    """Whether a region (its reads: a packed table) qualifies for encode_regions_on_device: _plan_region's fast
+    path -- one sample, no trimming or alt-aligned mode, no list-aux channel, no blanking, no non-uniform
+    downsampling -- with nothing per read that a packed table lacks."""
+    from deepvariant_amd import alt_aligned_pileup_lib as aap
+    api = self._encoder_api
+    if (len(self._options.sample_options) != 1 or self._alt_mode != aap.NONE or api._need_list_aux or api._need_aux or
+        any(api._need_seq_aux or ()) or os.environ.get('DV_PY_PACKER') is not None or
+        getattr(self._options, 'trim_reads_for_pileup', False)):
+      return False
+    so = self._options.sample_options[0]
+    if (so.keep_only_window_spanning_reads or so.channels_enum_to_blank or so.variant_types_to_blank or
+        so.use_non_uniform_downsampling):
+      return False
+    return reads is None or isinstance(reads, packing.ReadTable)
+
+  def encode_regions_on_device(self, regions, model_shape, mean_coverage: float = 0.0):
+    """encode_region_on_device for a batch of regions -- regions[k] = (candidates, the region's table), each of
+    which `device_pack_ok` accepts -- with ONE pack call on the device (packing.pack_regions_device: read support
+    by row, no strings) and ONE encoder launch over the merged table.  -> per region (its slice of the image
+    tensor or None, [(candidate index, alt combination)]): what encode_region_on_device returns for it."""
+    import torch  # device memory + stream only
+    from deepvariant_amd.device_batch import DeviceBatch
+    pic = self._options.pic_options
+    so = self._options.sample_options[0]
+    width = pic.width
+    image_shape = [self._height, width, len(pic.channels)]
+    if list(image_shape) != list(model_shape):
+      raise ValueError('example shape %s != model shape %s' % (image_shape, list(model_shape)))
+    example_bytes = int(np.prod(image_shape))
+    for _, table in regions:
+      if not self.device_pack_ok(table):
+        raise ValueError('encode_regions_on_device: a region does not qualify; use encode_region_on_device')
+    tables = [table for _, table in regions]
+    windows = [[get_reference_bases_for_pileup(self._ref, c.variant, width) for c in cands] for cands, _ in regions]
+    combos = [[list(alt_allele_combinations(c, pic.multi_allelic_mode)) if w else [] for c, w in zip(cands, wins)]
+              for (cands, _), wins in zip(regions, windows)]
+    dev = torch.device('cuda', self._device)
+    with torch.cuda.device(dev):
+      stream = torch.cuda.current_stream(dev).cuda_stream
+      packed, plan = packing.pack_regions_device(
+          tables, [cands for cands, _ in regions], combos, windows, width, pic.read_overlap_buffer_bp,
+          so.pileup_height, example_bytes, mean_coverage=float(mean_coverage), stream=stream)
+      out = [(None, []) for _ in regions]
+      if not plan:
+        packed.close()
+        return out
+      if self._device_encoder is None:
+        self._device_encoder = _Encoder(pic, pic.width, self._device)
+      merged = packing.merge_region_tables([t for t in tables if t.n_reads] or tables[:1])
+      batch = packing.PackedBatch(table=merged, width=width, use_ref_aux=self._encoder_api._need_ref_aux)
+      batch.ref_windows_list = packed.ref_windows_list
+      dbatch = DeviceBatch.from_packed_regions(batch, packed, dev, pic.reference_band_height,
+                                               bool(pic.sort_by_alt_allele_support), so.pileup_height)
+      flat = torch.empty(len(plan) * example_bytes, dtype=torch.uint8, device=dev)
+      dbatch.encode(self._device_encoder, image_shape[2], flat, stream=stream)
+      # the handle's arrays are freed by the library, not by torch's stream-aware allocator: the batch is kept
+      # until the encoder that reads them has run
+      done = torch.cuda.Event()
+      done.record(torch.cuda.current_stream(dev))
+      self._drawing = [(e, b) for e, b in getattr(self, '_drawing', []) if not e.query()] + [(done, dbatch)]
+    images = flat.view([len(plan)] + list(image_shape))
+    at = 0
+    for k in range(len(regions)):
+      n = at
+      while n < len(plan) and plan[n][0] == k:
+        n += 1
+      if n > at:
+        out[k] = (images[at:n], [(ci, combo) for _, ci, combo in plan[at:n]])
+      at = n
+    self._alt_plan = []
+    return out
+
   def _encode_example(self, variant, alt_combination, image: np.ndarray,
                       image_shape, label, stats) -> bytes:
     """EncodeExample, make_examples_native.cc:388-474."""

@@ -1077,6 +1077,247 @@ def pack_region_native(table: 'ReadTable', candidates: Sequence, combos: Sequenc
   return batch, plan
 
 
+# ---- the same on the device, for a batch of regions, with read support by row (DV_PACK_DEVICE=1;
+# dv_pack_regions_device, csrc/pack_regions.hip): no string is encoded or hashed
+def pack_device_enabled() -> bool:
+  """The switch, read at each call (as DV_PHASE_TABLES is)."""
+  return os.environ.get('DV_PACK_DEVICE') == '1'
+
+
+def table_key_ids(table: 'ReadTable') -> Optional[np.ndarray]:
+  """int32 per row, equal for two rows iff their keys are equal, or None when all keys differ (what
+  AlleleCounter._read_key_ids computes), cached on the table."""
+  cached = table.__dict__.get('_key_ids_cache')
+  if cached is None:
+    ids: Dict[str, int] = {}
+    per_read = [ids.setdefault(name, len(ids)) for name in table.keys]
+    cached = (None if len(ids) == len(per_read) else np.ascontiguousarray(per_read, np.int32),)
+    table.__dict__['_key_ids_cache'] = cached
+  return cached[0]
+
+
+def _row_keys(table: 'ReadTable') -> np.ndarray:
+  """The integer key of every row as the device packer takes it: table_key_ids, or the row itself."""
+  ids = table_key_ids(table)
+  return ids if ids is not None else np.arange(table.n_reads, dtype=np.int32)
+
+
+def _key_of_name(table: 'ReadTable') -> Dict[str, int]:
+  """One dict per table, name -> the integer key of its rows, for calls that carry names only."""
+  cached = table.__dict__.get('_key_of_name_cache')
+  if cached is None:
+    cached = dict(zip(table.keys, _row_keys(table).tolist()))
+    table.__dict__['_key_of_name_cache'] = cached
+  return cached
+
+
+NO_SUCH_KEY = -1     # a support entry whose name no read of the table has: it matches no row
+
+
+def support_arrays(table: 'ReadTable', candidates: Sequence):
+  """allele_support of a region's candidates as integers: -> (first_support[n], n_support[n], support_key int32,
+  support_alt uint8), the entries of candidate i in alternate_bases order then list order, as pack_region_native
+  lists them by name.  A call of the device caller carries the rows (`support_rows`); any other call's names go
+  through one dict per table."""
+  keys_of_rows = _row_keys(table)
+  first, count, key_parts, alt_parts = [], [], [], []
+  by_name = None
+  total = 0
+  for cand in candidates:
+    first.append(total)
+    n = 0
+    rows_of = getattr(cand, 'support_rows', None)
+    for ai, alt in enumerate(cand.variant.alternate_bases):
+      if alt not in cand.allele_support:
+        continue
+      if rows_of is not None and alt in rows_of:
+        keys = keys_of_rows[np.asarray(rows_of[alt], np.int64)]
+      else:
+        if by_name is None:
+          by_name = _key_of_name(table)
+        keys = np.array([by_name.get(name, NO_SUCH_KEY) for name in cand.allele_support[alt].read_names], np.int32)
+      key_parts.append(keys)
+      alt_parts.append(np.full(len(keys), ai, np.uint8))
+      n += len(keys)
+    count.append(n)
+    total += n
+  support_key = np.concatenate(key_parts).astype(np.int32) if key_parts else np.zeros(0, np.int32)
+  support_alt = np.concatenate(alt_parts) if alt_parts else np.zeros(0, np.uint8)
+  return np.array(first, np.uint32), np.array(count, np.uint32), support_key, support_alt
+
+
+def merge_region_tables(tables: Sequence['ReadTable']) -> 'ReadTable':
+  """Rows of several regions' tables one after the other, for ONE encoder batch whose every item lists rows of
+  one region only: read_name_rank, which orders reads within an item, keeps each table's own ranks."""
+  if len(tables) == 1:
+    return tables[0]
+  cat = lambda name: np.concatenate([getattr(t, name) for t in tables])       # noqa: E731
+
+  def offsets(name):
+    out, base = [np.zeros(1, np.int64)], 0
+    for t in tables:
+      o = getattr(t, name).astype(np.int64)
+      out.append(o[1:] + base)
+      base += int(o[-1])
+    return np.concatenate(out).astype(np.uint32)
+
+  def opt(name):
+    have = [getattr(t, name) for t in tables]
+    if all(h is None for h in have):
+      return None
+    like = next(h for h in have if h is not None)
+    parts = []
+    for t, h in zip(tables, have):
+      if h is None:
+        if name == 'read_sort_pos':
+          h = t.read_pos.astype(like.dtype)
+        elif name in ('read_aux', 'flow_present'):
+          h = np.zeros((t.n_reads,) + like.shape[1:], like.dtype)
+        else:                                  # per-base arrays
+          h = np.zeros(len(t.bases), like.dtype)
+      parts.append(h)
+    return np.concatenate(parts)
+  return ReadTable(
+      n_reads=sum(t.n_reads for t in tables), read_pos=cat('read_pos'), read_sort_pos=opt('read_sort_pos'),
+      read_seq_off=offsets('read_seq_off'), read_cigar_off=offsets('read_cigar_off'), read_mapq=cat('read_mapq'),
+      read_flags=cat('read_flags'), read_frag_len=cat('read_frag_len'), read_hp=cat('read_hp'),
+      read_name_rank=cat('read_name_rank'), read_aux=opt('read_aux'), bases=cat('bases'), quals=cat('quals'),
+      mod_5mc=opt('mod_5mc'), mod_6ma=opt('mod_6ma'), cigar=cat('cigar'), keys=[k for t in tables for k in t.keys],
+      read_end=cat('read_end'), base_aux0=opt('base_aux0'), base_aux1=opt('base_aux1'), base_aux2=opt('base_aux2'),
+      flow_tp=opt('flow_tp'), flow_t0=opt('flow_t0'), flow_present=opt('flow_present'))
+
+
+class PackedRegions:
+  """A dv_packed_regions handle (item / list arrays in device memory) and what the host knows of it."""
+
+  def __init__(self, handle, n_items: int, ref_windows_list: List[bytes], read_first: List[int]):
+    self.handle = handle
+    self.n_items = n_items
+    self.ref_windows_list = ref_windows_list      # of the whole batch: cands' ref_idx index it
+    self.read_first = read_first                  # region k's first row in the concatenated table
+
+  def fill_batch(self, c_batch, use_groups: bool) -> None:
+    _lib.check(_lib.lib().dv_packed_regions_fill_batch(self.handle, int(use_groups), C.byref(c_batch)))
+
+  def download(self) -> Dict[str, np.ndarray]:
+    """The arrays copied to the host, by dv_batch field name (plus item_candidate / item_combo / max_list_len)."""
+    view = _lib.DvPackedRegionsView()
+    _lib.check(_lib.lib().dv_packed_regions_download(self.handle, C.byref(view)))
+    n, m = view.n_items, view.n_list
+
+    def arr(ptr, dtype, count):
+      if not count:
+        return np.zeros(0, dtype)
+      buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+      return np.frombuffer(buf, dtype=dtype, count=count).copy()
+    return dict(
+        item_variant_start=arr(view.item_variant_start, np.int32, n), item_image_start=arr(view.item_image_start, np.int32, n),
+        item_ref_idx=arr(view.item_ref_idx, np.uint32, n), item_list_off=arr(view.item_list_off, np.uint32, n + 1),
+        item_height=arr(view.item_height, np.uint16, n), item_out_off=arr(view.item_out_off, np.uint64, n),
+        item_mean_coverage=arr(view.item_mean_coverage, np.float32, n), item_candidate=arr(view.item_candidate, np.int32, n),
+        item_combo=arr(view.item_combo, np.uint32, n), list_read=arr(view.list_read, np.uint32, m),
+        list_code=arr(view.list_code, np.uint8, m), list_group=arr(view.list_group, np.uint8, m),
+        max_list_len=int(view.max_list_len))
+
+  def close(self) -> None:
+    if self.handle is not None:
+      _lib.lib().dv_packed_regions_free(self.handle)
+      self.handle = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # pylint: disable=broad-except   (interpreter shutdown)
+      pass
+
+
+def pack_device_stats() -> Dict[str, int]:
+  """dv_pack_regions_device_last_stats of the calling thread."""
+  s = _lib.DvPackDeviceStats()
+  _lib.check(_lib.lib().dv_pack_regions_device_last_stats(C.byref(s)))
+  return {name: int(getattr(s, name)) for name, _ in s._fields_}    # pylint: disable=protected-access
+
+
+def pack_regions_device(tables: Sequence['ReadTable'], candidates_per_region: Sequence[Sequence],
+                        combos: Sequence[Sequence[Sequence[Sequence[str]]]],
+                        windows: Sequence[Sequence[Optional[str]]], width: int, read_overlap_buffer_bp: int,
+                        pileup_height: int, example_bytes: int, mean_coverage: float = 0.0, stream=None):
+  """dv_pack_regions_device (include/dvhip.h) for a batch of regions: region k's reads are tables[k], its candidates
+  candidates_per_region[k] with combos[k][i] / windows[k][i] as pack_region_native takes them.  One native call,
+  three launches; the arrays stay on the device.  -> (PackedRegions, [(region, candidate index, alt combination)])."""
+  lib = _lib.lib()
+  n_regions = len(tables)
+  read_first, at = [], 0
+  for t in tables:
+    read_first.append(at)
+    at += t.n_reads
+  cat = lambda parts, dtype: (np.ascontiguousarray(np.concatenate(parts), dtype) if parts   # noqa: E731
+                              else np.zeros(0, dtype))
+  read_pos = cat([t.read_pos for t in tables], np.int32)
+  read_end = cat([t.read_end for t in tables], np.int64)
+  read_key = cat([_row_keys(t) for t in tables], np.int32)
+  rows = _lib.DvPackRows(at, read_pos.ctypes.data if at else None, read_end.ctypes.data if at else None,
+                         read_key.ctypes.data if at else None)
+  n_cands = sum(len(c) for c in candidates_per_region)
+  slices = (_lib.DvPackRegionSlice * max(n_regions, 1))()
+  cands = (_lib.DvPackCandidate * max(n_cands, 1))()
+  masks: List[int] = []
+  ref_windows_list: List[bytes] = []
+  key_parts, alt_parts = [], []
+  flat = []              # (region, candidate index, alts) of every entry of cands
+  ci, n_support = 0, 0
+  for k, (table, region_cands) in enumerate(zip(tables, candidates_per_region)):
+    slices[k].read_first, slices[k].n_reads = read_first[k], table.n_reads
+    slices[k].cand_first, slices[k].n_cands = ci, len(region_cands)
+    first, count, support_key, support_alt = support_arrays(table, region_cands)
+    key_parts.append(support_key)
+    alt_parts.append(support_alt)
+    for i, cand in enumerate(region_cands):
+      v = cand.variant
+      alts = list(v.alternate_bases)
+      c = cands[ci]
+      c.start, c.end, c.n_alts = int(v.start), int(v.end), len(alts)
+      window = windows[k][i]
+      if window:
+        if len(window) != width:
+          raise ValueError('ref_bases.size() != width')  # pileup_image_native.cc:308
+        ref_windows_list.append(window.encode() if isinstance(window, str) else bytes(window))
+        c.ref_idx = len(ref_windows_list) - 1
+      else:
+        c.ref_idx = -1
+      c.first_combo, c.n_combos = len(masks), len(combos[k][i])
+      for combo in combos[k][i]:
+        m = 0
+        for a in combo:
+          m |= 1 << alts.index(a)
+        masks.append(m)
+      c.first_support, c.n_support = n_support + int(first[i]), int(count[i])
+      flat.append((k, i, alts))
+      ci += 1
+    n_support += len(support_key)
+  mask_arr = np.array(masks or [0], np.uint32)
+  key_arr = cat(key_parts, np.int32)
+  alt_arr = cat(alt_parts, np.uint8)
+  opt = _lib.DvPackRegionsOptions(int(width), int(read_overlap_buffer_bp), int(pileup_height), n_cands, len(masks),
+                                  len(key_arr), int(example_bytes), float(mean_coverage))
+  handle = C.c_void_p()
+  _lib.check(lib.dv_pack_regions_device(
+      n_regions, slices, C.byref(rows), C.byref(opt), cands, mask_arr.ctypes.data,
+      key_arr.ctypes.data if len(key_arr) else None, alt_arr.ctypes.data if len(alt_arr) else None,
+      C.c_void_p(stream) if stream else None, C.byref(handle)))
+  ic, im = C.c_void_p(), C.c_void_p()
+  n_items = lib.dv_packed_regions_items(handle, C.byref(ic), C.byref(im))
+  packed = PackedRegions(handle, n_items, ref_windows_list, read_first)
+  plan = []
+  if n_items:
+    item_cand = np.frombuffer((C.c_char * (4 * n_items)).from_address(ic.value), np.int32, n_items).tolist()
+    item_mask = np.frombuffer((C.c_char * (4 * n_items)).from_address(im.value), np.uint32, n_items).tolist()
+    for c_index, m in zip(item_cand, item_mask):
+      k, i, alts = flat[c_index]
+      plan.append((k, i, [a for bit, a in enumerate(alts) if (m >> bit) & 1]))
+  return packed, plan
+
+
 @dataclasses.dataclass
 class PackedBatch:
   """Host image of `dv_batch` (numpy arrays), plus the ctypes view."""

@@ -369,7 +369,8 @@ class VariantCaller:
                         calls=[T.VariantCall(call_set_name=self._options.sample_name, genotype=[-1, -1])])
     call = T.DeepVariantCall(variant=variant)
     self._add_read_depths(allele_count, alt_alleles, allele_map, refbases, variant, dp)
-    self._add_supporting_reads(allele_count.read_alleles, allele_map, refbases, call)
+    self._add_supporting_reads(allele_count.read_alleles, allele_map, refbases, call,
+                               getattr(allele_count, 'read_rows', None))
     return call
 
   def calls_from_allele_counts(self, allele_counts: Sequence) -> List[T.DeepVariantCall]:
@@ -434,19 +435,25 @@ class VariantCaller:
     info['AD'] = T.ListValue(values=[T.Value(int_value=v) for v in ad])
     info['VAF'] = T.ListValue(values=[T.Value(number_value=v) for v in vaf])
 
-  def _add_supporting_reads(self, read_alleles, allele_map, refbases, call):
-    """AddSupportingReads (:673-713)."""
+  def _add_supporting_reads(self, read_alleles, allele_map, refbases, call, read_rows=None):
+    """AddSupportingReads (:673-713).  `read_rows` (a device caller's site: the table row behind every entry of
+    read_alleles) fills call.support_rows next to allele_support: the same keys, the same order, the same suffix."""
     suffix = ''
     if len(call.variant.reference_bases) > len(refbases):
       suffix = call.variant.reference_bases[len(refbases):]
+    rows = {} if read_rows is not None else None
     for read_name, allele in read_alleles.items():
       if allele.type != ac.REFERENCE:
         alt = allele_map.get(_allele_order(allele))
         key = K_SUPPORTING_UNCALLED_ALLELE if alt is None else alt + suffix
         call.allele_support.setdefault(key, T.SupportingReads()).read_names.append(read_name)
+        if rows is not None:
+          rows.setdefault(key, []).append(read_rows[read_name])
         call.allele_support_ext.setdefault(key, []).append(T.ReadSupport(read_name, bool(allele.is_low_quality)))
       elif self._options.track_ref_reads:
         # REFERENCE read alleles are kept by name only under track_ref_reads, at candidate
         # positions (variant_calling.cc:706, variant_calling_multisample.cc:1231-1247)
         call.ref_support.append(read_name)
         call.ref_support_ext.append(T.ReadSupport(read_name, bool(allele.is_low_quality)))
+    if rows is not None:
+      call.support_rows = {key: np.array(r, np.int64) for key, r in rows.items()}

@@ -448,6 +448,94 @@ int dv_packed_region_items(const dv_packed_region* p, const int32_t** item_candi
                            const uint32_t** item_combo);
 void dv_packed_region_free(dv_packed_region* p);
 
+/* ---- the same for a batch of regions, on the device, read support by ROW -------------
+ * dv_pack_region's arrays for several regions at once, computed by three kernels (csrc/pack_regions.hip: count,
+ * scan, emit) and LEFT in device memory for dv_encode_batch.  No string is involved: a read is known by an integer
+ * key, and a candidate's support lists name keys.  dv_pack_region stays the checker: for one region the arrays are
+ * equal, array for array.
+ *   rows       the regions' read tables, concatenated.  read_key[r] is equal for two rows of one region iff their
+ *              "<fragment_name>/<read_number>" keys are equal (keys are compared within a region only); NULL =
+ *              every row is its own key, and a support entry then names the row in the concatenated table.
+ *   regions    region k owns rows [read_first, read_first + n_reads) and candidates [cand_first, cand_first +
+ *              n_cands); the candidate slices follow each other in region order and cover cands[n_candidates].
+ *   cands      as dv_pack_region's; ref_idx indexes the reference windows of the whole batch, first_support /
+ *              n_support slice support_key / support_alt (an entry whose key matches no picked read is ignored).
+ * Items are numbered across the batch, in region order then candidate order; list_read is the row in the
+ * concatenated table; item_candidate is the index into cands. */
+typedef struct dv_pack_rows {
+  int32_t n_reads;
+  const int32_t* read_pos;   /* alignment start */
+  const int64_t* read_end;   /* exclusive reference end */
+  const int32_t* read_key;   /* [n_reads] or NULL */
+} dv_pack_rows;
+
+typedef struct dv_pack_region_slice {
+  int32_t read_first, n_reads;
+  int32_t cand_first, n_cands;
+} dv_pack_region_slice;
+
+typedef struct dv_pack_regions_options {
+  int32_t width;                   /* as dv_pack_options */
+  int32_t read_overlap_buffer_bp;
+  int32_t pileup_height;
+  int32_t n_candidates;            /* entries of cands */
+  uint32_t n_combo_masks;          /* entries of combo_masks */
+  uint32_t n_support;              /* entries of support_key / support_alt */
+  uint64_t example_bytes;          /* item k is written at k * example_bytes */
+  float mean_coverage;             /* item_mean_coverage of every item */
+} dv_pack_regions_options;
+
+typedef struct dv_packed_regions dv_packed_regions; /* owns the item / list arrays, in device memory */
+
+/* One upload, pack_count_kernel and pack_scan_kernel, one small download and one synchronisation (the totals and
+ * max_list_len), one allocation, pack_emit_kernel -- all on `stream` (NULL = a non-blocking stream the library owns,
+ * which the call then also waits for).  With a caller's stream the arrays are ready in stream order: hand the same
+ * stream to dv_encode_batch.  Placement is a pure function of the input (no atomics): two calls give identical bytes.
+ * DV_ERR_INVALID_ARGUMENT before any device work, *out NULL: null pointers, negative counts, slices outside their
+ * arrays, and for a candidate with a reference window n_alts outside [0, 32] or a support_alt >= n_alts;
+ * width < 3, pileup_height <= 0.  No candidate with a reference window and a combination: DV_OK, an empty handle,
+ * no device needed.  Otherwise no device is DV_ERR_NO_DEVICE (dv_pack_region is the host code).  More than
+ * 2^32 - 1 list entries or 2^31 - 1 items: DV_ERR_BAD_INPUT, decided from the counts before anything is emitted. */
+int dv_pack_regions_device(int32_t n_regions, const dv_pack_region_slice* regions, const dv_pack_rows* rows,
+                           const dv_pack_regions_options* opt, const dv_pack_candidate* cands,
+                           const uint32_t* combo_masks, const int32_t* support_key, const uint8_t* support_alt,
+                           void* stream, dv_packed_regions** out);
+/* Points the item / list fields of `b` -- whose memory must be DV_MEM_DEVICE -- at the arrays (list_group iff
+ * use_groups), sets n_items, n_list, max_list_len, item_blank_mask = NULL (0) and item_mean_coverage (the options'
+ * value for every item); read-table and reference-window fields and the size hints are the caller's. */
+int dv_packed_regions_fill_batch(const dv_packed_regions* p, int use_groups, dv_batch* b);
+typedef struct dv_packed_regions_view {   /* host copies; valid until the handle is freed */
+  int32_t n_items;
+  uint32_t n_list, max_list_len;
+  const int32_t* item_variant_start;
+  const int32_t* item_image_start;
+  const uint32_t* item_ref_idx;
+  const uint32_t* item_list_off;      /* [n_items + 1] */
+  const uint16_t* item_height;
+  const uint64_t* item_out_off;
+  const float* item_mean_coverage;
+  const int32_t* item_candidate;
+  const uint32_t* item_combo;
+  const uint32_t* list_read;
+  const uint8_t* list_code;
+  const uint8_t* list_group;
+} dv_packed_regions_view;
+/* Waits for the emit kernel and copies the arrays to the host (once; later calls return the same copies). */
+int dv_packed_regions_download(dv_packed_regions* p, dv_packed_regions_view* out);
+/* Which (candidate, combination mask) each item is, in host memory; returns the item count. */
+int dv_packed_regions_items(const dv_packed_regions* p, const int32_t** item_candidate, const uint32_t** item_combo);
+void dv_packed_regions_free(dv_packed_regions* p);
+typedef struct dv_pack_device_stats {
+  int64_t regions;
+  int64_t candidates;
+  int64_t items;
+  int64_t list_entries;
+  int64_t regions_unsorted;   /* regions whose read_pos does not ascend: their candidates scan the whole slice */
+  int64_t launches;
+} dv_pack_device_stats;
+/* What the calling thread's last dv_pack_regions_device did. */
+int dv_pack_regions_device_last_stats(dv_pack_device_stats* out);
+
 /* ---- read realigner (host only) ----------------------------------------------
  * Replaces deepvariant/realigner/fast_pass_aligner.{h,cc} (class FastPassAligner) and the
  * local aligner it links (libssw v1.2.5 through deepvariant/realigner/ssw.{h,cc}); used by
