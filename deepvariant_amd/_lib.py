@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     'dv_packed_region_free',
     'dv_pack_regions_device', 'dv_packed_regions_fill_batch', 'dv_packed_regions_download', 'dv_packed_regions_items',
     'dv_packed_regions_free', 'dv_pack_regions_device_last_stats',
+    'dv_pack_draws_device', 'dv_pack_draws_device_last_stats',
     'dv_aligner_create', 'dv_aligner_destroy', 'dv_aligner_set_reference',
     'dv_aligner_set_haplotypes', 'dv_aligner_set_reads', 'dv_aligner_align_reads',
     'dv_aligner_stage', 'dv_aligner_fast_align', 'dv_aligner_haplotype_info',
@@ -259,6 +260,16 @@ class DvPackedRegionsView(C.Structure):
 class DvPackDeviceStats(C.Structure):
   _fields_ = [('regions', C.c_int64), ('candidates', C.c_int64), ('items', C.c_int64), ('list_entries', C.c_int64),
               ('regions_unsorted', C.c_int64), ('launches', C.c_int64)]
+
+
+class DvPackDraw(C.Structure):
+  _fields_ = [('cand', C.c_int32), ('combo_mask', C.c_uint32), ('row_first', C.c_int32), ('n_rows', C.c_int32),
+              ('ref_idx', C.c_uint32), ('variant_start', C.c_int32), ('image_start', C.c_int32), ('height', C.c_uint16),
+              ('out_off', C.c_uint64), ('mean_coverage', C.c_float)]
+
+
+class DvPackDrawsStats(C.Structure):
+  _fields_ = [('draws', C.c_int64), ('candidates', C.c_int64), ('list_entries', C.c_int64), ('launches', C.c_int64)]
 
 
 class DvTrimStats(C.Structure):
@@ -514,6 +525,9 @@ def lib():
     l.dv_packed_regions_free.argtypes = [C.c_void_p]
     l.dv_packed_regions_free.restype = None
     l.dv_pack_regions_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_pack_draws_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    l.dv_pack_draws_device_last_stats.argtypes = [C.c_void_p]
     l.dv_read_table_ends.restype = C.c_void_p
     l.dv_read_table_ends.argtypes = [C.c_void_p]
     l.dv_read_table_free.argtypes = [C.c_void_p]

@@ -309,6 +309,7 @@ def trim_table(table, windows: Sequence, device: bool = True, stream: int = 0, w
       read_aux=None, bases=table.bases[seq_idx], quals=table.quals[seq_idx],
       mod_5mc=per_base(table.mod_5mc, packing.DV_READ_HAS_5MC), mod_6ma=per_base(table.mod_6ma, packing.DV_READ_HAS_6MA),
       cigar=d['cigar'], keys=[keys[i] for i in src.tolist()], read_end=d['end'].astype(np.int64))
+  packing.set_table_src_rows(trimmed, src)          # the row of `table` every trimmed row is a copy of
   off = d['window_row_off'].tolist()
   ranges = list(zip(off[:-1], off[1:]))
   return (trimmed, ranges, d.get('stats')) if with_stats else (trimmed, ranges)
@@ -412,4 +413,5 @@ def alt_align_table(trimmed_table, items: Sequence, targets: Sequence, aln_confi
     # only status-1 pairs hold words, so their ranges are contiguous in `cigar`, in order
     new_off = np.concatenate([coff[pairs], coff[pairs[-1] + 1:pairs[-1] + 2]])
     out = out.with_alignments_csr(np.nonzero(moved)[0], d['position'][pairs], new_off, d['cigar'])
+  packing.set_table_src_rows(out, src_all[kept])      # the row of the trimmed table every realigned row came from
   return (out, ranges, d.get('stats')) if with_stats else (out, ranges)

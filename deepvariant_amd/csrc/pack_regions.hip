@@ -31,6 +31,11 @@
 // Placement is a pure function of the input; there are no atomics.  Every index is inside its array by
 // construction: rows inside the region's slice (checked on the host), list positions below the scanned total
 // (the emit walk is the count walk), support positions inside the candidate's slice (checked on the host).
+//
+// dv_pack_draws_device fills the same handle for items whose list is GIVEN -- a row range of a trimmed or
+// alt-aligned table -- so only the support rule is left: the host plan sorts the support the same way and lays the
+// lists out (prefix sum of the draws' n_rows), pack_draws_kernel runs one wave per draw.  One upload, one allocation,
+// one launch, no download and no synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -228,6 +233,27 @@ __global__ __launch_bounds__(kScanThreads) void pack_scan_kernel(Inputs in, cons
   }
 }
 
+// A read's place in a candidate's support, sorted by (key, alt): the start of its key's run gives first_alt, the
+// end group; both are left alone when no entry has the key.  ns > 0.
+__device__ __forceinline__ void support_of(const int32_t* skey, const uint8_t* salt, int32_t ns, int32_t key,
+                                           uint32_t* first_alt, uint32_t* group) {
+  int32_t a = 0, b = ns;            // first entry with key >= the read's
+  while (a < b) {
+    const int32_t m = a + ((b - a) >> 1);
+    if (skey[m] < key) a = m + 1; else b = m;
+  }
+  if (a < ns && skey[a] == key) {
+    *first_alt = salt[a];           // entries of one key ascend by alt
+    int32_t e = a + 1;
+    b = ns;                         // first entry with key > the read's
+    while (e < b) {
+      const int32_t m = e + ((b - e) >> 1);
+      if (skey[m] <= key) e = m + 1; else b = m;
+    }
+    *group = salt[e - 1];
+  }
+}
+
 // Pass 3: the lists and item records, at the places pass 2 gave them.
 __global__ __launch_bounds__(kThreads) void pack_emit_kernel(Inputs in, const uint32_t* picked,
                                                              const unsigned long long* list_base,
@@ -277,24 +303,7 @@ __global__ __launch_bounds__(kThreads) void pack_emit_kernel(Inputs in, const ui
     const uint32_t j = before + static_cast<uint32_t>(__popcll(ballot & ((1ull << lane) - 1ull)));
     if (j >= n_picked) continue;      // cannot happen: the count walk is this walk
     uint32_t first_alt = 255, group = static_cast<uint32_t>(cd.n_alts);
-    if (ns > 0) {
-      const int32_t key = in.read_key[row];
-      int32_t a = 0, b = ns;          // first entry with key >= the read's
-      while (a < b) {
-        const int32_t m = a + ((b - a) >> 1);
-        if (skey[m] < key) a = m + 1; else b = m;
-      }
-      if (a < ns && skey[a] == key) {
-        first_alt = salt[a];          // entries of one key ascend by alt
-        int32_t e = a + 1;
-        b = ns;                       // first entry with key > the read's
-        while (e < b) {
-          const int32_t m = e + ((b - e) >> 1);
-          if (skey[m] <= key) e = m + 1; else b = m;
-        }
-        group = salt[e - 1];
-      }
-    }
+    if (ns > 0) support_of(skey, salt, ns, in.read_key[row], &first_alt, &group);
     for (uint32_t k = 0; k < cd.n_combos; ++k) {
       const uint32_t mask = in.combo_masks[cd.first_combo + k];
       const uint32_t p = at + k * n_picked + j;
@@ -303,6 +312,66 @@ __global__ __launch_bounds__(kThreads) void pack_emit_kernel(Inputs in, const ui
       o.list_group[p] = static_cast<uint8_t>(group);
     }
   }
+}
+
+// ---- dv_pack_draws_device: items whose list is a given row range (trimmed and alt-aligned regions).  There is no
+// query, so every size is the host's: item_list_off is the prefix sum of the draws' n_rows and travels with them.
+struct Draw {              // as the kernel takes a draw: the caller's record, its candidate's support, its list's place
+  int32_t row_first, n_rows;
+  uint32_t list_off;
+  uint32_t mask;
+  uint32_t first_support, n_support;  // slice of the SORTED support arrays
+  int32_t n_alts;
+  int32_t variant_start, image_start;
+  uint32_t ref_idx;
+  uint64_t out_off;
+  float mean_coverage;
+  uint32_t height;
+};
+
+struct DrawInputs {        // device pointers into the upload
+  const Draw* draws;
+  const int32_t* rows_key;           // nullptr: a row is its own key
+  const int32_t* support_key;
+  const uint8_t* support_alt;
+  uint32_t n_draws, n_list;
+};
+
+// One wave per draw, four to a workgroup: lanes stride over the draw's rows; lane 0 copies the item record.  Every
+// index is inside its array by construction: rows inside the table and support slices inside their arrays (checked on
+// the host), list positions below n_list (the host's prefix sum of the same n_rows).
+__global__ __launch_bounds__(kThreads) void pack_draws_kernel(DrawInputs in, Outputs o) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint32_t d = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (d >= in.n_draws) return;       // the wave's
+  const Draw dr = in.draws[d];
+  if (lane == 0) {
+    o.item_variant_start[d] = dr.variant_start;
+    o.item_image_start[d] = dr.image_start;
+    o.item_ref_idx[d] = dr.ref_idx;
+    o.item_list_off[d] = dr.list_off;
+    o.item_height[d] = static_cast<uint16_t>(dr.height);
+    o.item_out_off[d] = dr.out_off;
+    o.item_mean_coverage[d] = dr.mean_coverage;
+    if (d == 0) o.item_list_off[in.n_draws] = in.n_list;
+  }
+  const int32_t* skey = in.support_key + dr.first_support;
+  const uint8_t* salt = in.support_alt + dr.first_support;
+  const int32_t ns = static_cast<int32_t>(dr.n_support);
+  for (int32_t i = lane; i < dr.n_rows; i += kWave) {
+    const int32_t row = dr.row_first + i;
+    uint32_t first_alt = 255, group = static_cast<uint32_t>(dr.n_alts);
+    if (ns > 0) support_of(skey, salt, ns, in.rows_key ? in.rows_key[row] : row, &first_alt, &group);
+    const uint32_t p = dr.list_off + static_cast<uint32_t>(i);
+    o.list_read[p] = static_cast<uint32_t>(row);
+    o.list_code[p] = first_alt == 255 ? 0 : ((dr.mask >> first_alt) & 1u) ? 1 : 2;
+    o.list_group[p] = static_cast<uint8_t>(group);
+  }
+}
+
+dv_pack_draws_stats& last_draws_stats() {
+  static thread_local dv_pack_draws_stats stats;
+  return stats;
 }
 
 dv_pack_device_stats& last_stats() {
@@ -347,6 +416,20 @@ struct dv_packed_regions {
 };
 
 namespace {
+
+// A support entry of the host plans, and the order the kernels search them in: by candidate, then (key, alt).
+struct Entry {
+  int32_t cand, key;
+  uint8_t alt;
+};
+
+void sort_support(std::vector<Entry>* entries) {
+  std::stable_sort(entries->begin(), entries->end(), [](const Entry& a, const Entry& b) {
+    if (a.cand != b.cand) return a.cand < b.cand;
+    if (a.key != b.key) return a.key < b.key;
+    return a.alt < b.alt;
+  });
+}
 
 // The call's arguments, checked, in the form the kernels take them.
 struct Plan {
@@ -395,10 +478,6 @@ int parse(int32_t n_regions, const dv_pack_region_slice* regions, const dv_pack_
   }
   if (next_cand != opt->n_candidates) return dv::fail(DV_ERR_INVALID_ARGUMENT, who + "the regions' candidate slices do not cover cands");
   // support entries of the candidates that give items, as (candidate, key, alt): one stable sort for the batch
-  struct Entry {
-    int32_t cand, key;
-    uint8_t alt;
-  };
   std::vector<Entry> entries;
   for (int32_t ci = 0; ci < opt->n_candidates; ++ci) {
     const dv_pack_candidate& c = cands[ci];
@@ -431,11 +510,7 @@ int parse(int32_t n_regions, const dv_pack_region_slice* regions, const dv_pack_
     }
   }
   if (entries.size() > UINT32_MAX) return dv::fail(DV_ERR_BAD_INPUT, who + "more than 2^32 - 1 support entries");
-  std::stable_sort(entries.begin(), entries.end(), [](const Entry& a, const Entry& b) {
-    if (a.cand != b.cand) return a.cand < b.cand;
-    if (a.key != b.key) return a.key < b.key;
-    return a.alt < b.alt;
-  });
+  sort_support(&entries);
   plan->support_key.resize(entries.size());
   plan->support_alt.resize(entries.size());
   for (size_t j = 0; j < entries.size(); ++j) {
@@ -570,6 +645,156 @@ int pack_on_device(const Plan& plan, const dv_pack_rows* rows, const dv_pack_reg
   return DV_OK;
 }
 
+// dv_pack_draws_device's arguments, checked, in the form the kernel takes them.
+struct DrawPlan {
+  std::vector<Draw> draws;
+  std::vector<int32_t> support_key;
+  std::vector<uint8_t> support_alt;
+  uint64_t n_list = 0;
+  uint32_t max_list_len = 0;
+};
+
+int parse_draws(int32_t n_rows, const dv_pack_draw* draws, int64_t n_draws,
+                const dv_pack_candidate* cands, int32_t n_cands, const int32_t* support_key, const uint8_t* support_alt,
+                uint32_t n_support, DrawPlan* plan) {
+  const std::string who = "dv_pack_draws_device: ";
+  if (n_rows < 0 || n_draws < 0 || n_cands < 0 || (n_draws > 0 && !draws) || (n_cands > 0 && !cands) ||
+      (n_support > 0 && (!support_key || !support_alt))) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, who + "null pointer with a non-zero count, or a negative count");
+  }
+  if (n_draws > INT32_MAX) return dv::fail(DV_ERR_BAD_INPUT, who + "more than 2^31 - 1 draws; pass fewer regions");
+  for (int32_t ci = 0; ci < n_cands; ++ci) {
+    const dv_pack_candidate& c = cands[ci];
+    const std::string which = who + "candidate " + std::to_string(ci) + ": ";
+    if (c.n_alts < 0 || c.n_alts > 32) return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "n_alts out of range");
+    if (static_cast<uint64_t>(c.first_support) + c.n_support > n_support) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "support entries outside the support arrays");
+    }
+    for (uint32_t j = c.first_support; j < c.first_support + c.n_support; ++j) {
+      if (support_alt[j] >= c.n_alts) return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "support_alt out of range");
+    }
+  }
+  std::vector<uint8_t> drawn(static_cast<size_t>(n_cands), 0);
+  for (int64_t d = 0; d < n_draws; ++d) {
+    const dv_pack_draw& w = draws[d];
+    const std::string which = who + "draw " + std::to_string(d) + ": ";
+    if (w.row_first < 0 || w.n_rows < 0 || static_cast<int64_t>(w.row_first) + w.n_rows > n_rows) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "rows outside the table");
+    }
+    if (w.cand < 0 || w.cand >= n_cands) return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "candidate outside cands");
+    if (w.height == 0) return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "height 0");
+    const int32_t n_alts = cands[w.cand].n_alts;
+    if (n_alts < 32 && (w.combo_mask >> n_alts) != 0) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, which + "combo_mask names an alt the candidate does not have");
+    }
+    drawn[w.cand] = 1;
+    plan->n_list += static_cast<uint64_t>(w.n_rows);
+    plan->max_list_len = std::max(plan->max_list_len, static_cast<uint32_t>(w.n_rows));
+  }
+  if (plan->n_list > UINT32_MAX) {
+    return dv::fail(DV_ERR_BAD_INPUT, who + std::to_string(plan->n_list) + " list entries, more than 2^32 - 1; pass fewer regions");
+  }
+  // support entries of the candidates that are drawn, sorted as the regions' plan sorts them
+  std::vector<Entry> entries;
+  for (int32_t ci = 0; ci < n_cands; ++ci) {
+    if (!drawn[ci]) continue;
+    const dv_pack_candidate& c = cands[ci];
+    for (uint32_t j = c.first_support; j < c.first_support + c.n_support; ++j) {
+      entries.push_back(Entry{ci, support_key[j], support_alt[j]});
+    }
+  }
+  sort_support(&entries);
+  std::vector<uint32_t> first(static_cast<size_t>(n_cands), 0), count(static_cast<size_t>(n_cands), 0);
+  plan->support_key.resize(entries.size());
+  plan->support_alt.resize(entries.size());
+  for (size_t j = 0; j < entries.size(); ++j) {
+    plan->support_key[j] = entries[j].key;
+    plan->support_alt[j] = entries[j].alt;
+    if (count[entries[j].cand]++ == 0) first[entries[j].cand] = static_cast<uint32_t>(j);
+  }
+  plan->draws.resize(static_cast<size_t>(n_draws));
+  uint32_t at = 0;
+  for (int64_t d = 0; d < n_draws; ++d) {
+    const dv_pack_draw& w = draws[d];
+    Draw& dr = plan->draws[static_cast<size_t>(d)];
+    dr.row_first = w.row_first;
+    dr.n_rows = w.n_rows;
+    dr.list_off = at;
+    dr.mask = w.combo_mask;
+    dr.first_support = first[w.cand];
+    dr.n_support = count[w.cand];
+    dr.n_alts = cands[w.cand].n_alts;
+    dr.variant_start = w.variant_start;
+    dr.image_start = w.image_start;
+    dr.ref_idx = w.ref_idx;
+    dr.out_off = w.out_off;
+    dr.mean_coverage = w.mean_coverage;
+    dr.height = w.height;
+    at += static_cast<uint32_t>(w.n_rows);
+  }
+  return DV_OK;
+}
+
+int pack_draws_on_device(const DrawPlan& plan, const int32_t* rows_key, int32_t n_rows, void* stream_in,
+                         dv_packed_regions* res, dv_pack_draws_stats* stats) {
+  const size_t n_draws = plan.draws.size(), n_sup = plan.support_key.size(), n_list = static_cast<size_t>(plan.n_list);
+  const size_t n_keys = rows_key ? static_cast<size_t>(n_rows) : 0;
+  dv::Layout up;
+  // upload image: draws | row keys | support keys | support alts
+  const size_t u_draws = up.add(n_draws * sizeof(Draw));
+  const size_t u_key = up.add(n_keys * sizeof(int32_t));
+  const size_t u_skey = up.add(n_sup * sizeof(int32_t));
+  const size_t u_salt = up.add(n_sup);
+  static thread_local dv::RoundTrip rt;
+  // as in pack_on_device: the kernel of this thread's previous call reads the staging that this call refills
+  static thread_local hipEvent_t previous_pack = nullptr;
+  if (previous_pack) (void)hipEventSynchronize(previous_pack);
+  if (int rc = rt.begin("dv_pack_draws_device: no HIP device", stream_in, up.bytes(), 0, 0)) return rc;
+  std::memcpy(rt.host_up<Draw>(u_draws), plan.draws.data(), n_draws * sizeof(Draw));
+  if (n_keys) std::memcpy(rt.host_up<int32_t>(u_key), rows_key, n_keys * sizeof(int32_t));
+  if (n_sup) {
+    std::memcpy(rt.host_up<int32_t>(u_skey), plan.support_key.data(), n_sup * sizeof(int32_t));
+    std::memcpy(rt.host_up<uint8_t>(u_salt), plan.support_alt.data(), n_sup);
+  }
+  DrawInputs in;
+  in.draws = rt.dev_up<const Draw>(u_draws);
+  in.rows_key = n_keys ? rt.dev_up<const int32_t>(u_key) : nullptr;
+  in.support_key = rt.dev_up<const int32_t>(u_skey);
+  in.support_alt = rt.dev_up<const uint8_t>(u_salt);
+  in.n_draws = static_cast<uint32_t>(n_draws);
+  in.n_list = static_cast<uint32_t>(n_list);
+  hipStream_t stream = rt.stream();
+  const Sections s(n_draws, n_list);
+  DV_HIP_CHECK(hipGetDevice(&res->device_id));
+  DV_HIP_CHECK(hipMalloc(&res->device, s.bytes));
+  DV_HIP_CHECK(hipEventCreateWithFlags(&res->emitted, hipEventDisableTiming));
+  uint8_t* base = static_cast<uint8_t*>(res->device);
+  Outputs o;
+  o.item_variant_start = reinterpret_cast<int32_t*>(base + s.ivs);
+  o.item_image_start = reinterpret_cast<int32_t*>(base + s.iis);
+  o.item_ref_idx = reinterpret_cast<uint32_t*>(base + s.iri);
+  o.item_list_off = reinterpret_cast<uint32_t*>(base + s.ilo);
+  o.item_height = reinterpret_cast<uint16_t*>(base + s.ih);
+  o.item_out_off = reinterpret_cast<uint64_t*>(base + s.ioo);
+  o.item_mean_coverage = reinterpret_cast<float*>(base + s.imc);
+  o.list_read = reinterpret_cast<uint32_t*>(base + s.lr);
+  o.list_code = base + s.lc;
+  o.list_group = base + s.lg;
+  if (int rc = rt.upload(up.bytes())) return rc;
+  {
+    dv::ProfileScope prof(dv::kProfOther, stream);
+    const unsigned blocks = static_cast<unsigned>((n_draws + kWaves - 1) / kWaves);
+    hipLaunchKernelGGL(pack_draws_kernel, dim3(blocks), dim3(kThreads), 0, stream, in, o);
+    DV_HIP_CHECK(hipGetLastError());
+  }
+  stats->launches += 1;
+  DV_HIP_CHECK(hipEventRecord(res->emitted, stream));
+  if (!previous_pack) DV_HIP_CHECK(hipEventCreateWithFlags(&previous_pack, hipEventDisableTiming));
+  DV_HIP_CHECK(hipEventRecord(previous_pack, stream));
+  if (!stream_in) DV_HIP_CHECK(hipStreamSynchronize(stream));   // nobody else can order work behind the library's stream
+  return DV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -600,6 +825,42 @@ int dv_pack_regions_device(int32_t n_regions, const dv_pack_region_slice* region
     *out = res.release();
     return DV_OK;
   });
+}
+
+int dv_pack_draws_device(const int32_t* rows_key, int32_t n_rows, const dv_pack_draw* draws, int64_t n_draws,
+                         const dv_pack_candidate* cands, int32_t n_cands, const int32_t* support_key,
+                         const uint8_t* support_alt, uint32_t n_support, void* stream, dv_packed_regions** out) {
+  return dv::guarded("dv_pack_draws_device", [&]() -> int {
+    last_draws_stats() = dv_pack_draws_stats{0, 0, 0, 0};
+    if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_pack_draws_device: null out");
+    *out = nullptr;
+    DrawPlan plan;
+    if (int rc = parse_draws(n_rows, draws, n_draws, cands, n_cands, support_key, support_alt, n_support, &plan)) return rc;
+    auto res = std::make_unique<dv_packed_regions>();      // frees its allocation and event on every error exit
+    res->item_candidate.resize(plan.draws.size());
+    res->item_combo.resize(plan.draws.size());
+    for (size_t d = 0; d < plan.draws.size(); ++d) {
+      res->item_candidate[d] = draws[d].cand;
+      res->item_combo[d] = draws[d].combo_mask;
+    }
+    dv_pack_draws_stats& stats = last_draws_stats();
+    stats.draws = n_draws;
+    stats.candidates = n_cands;
+    stats.list_entries = static_cast<int64_t>(plan.n_list);
+    if (!plan.draws.empty()) {               // otherwise nothing to launch
+      if (int rc = pack_draws_on_device(plan, rows_key, n_rows, stream, res.get(), &stats)) return rc;
+    }
+    res->n_list = static_cast<uint32_t>(plan.n_list);
+    res->max_list_len = plan.max_list_len;
+    *out = res.release();
+    return DV_OK;
+  });
+}
+
+int dv_pack_draws_device_last_stats(dv_pack_draws_stats* out) {
+  if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_pack_draws_device_last_stats: null");
+  *out = last_draws_stats();
+  return DV_OK;
 }
 
 int dv_packed_regions_fill_batch(const dv_packed_regions* p, int use_groups, dv_batch* b) {

@@ -652,26 +652,43 @@ class ExamplesGenerator:
     return images, plan
 
   def device_pack_ok(self, reads=None) -> bool:
-    """Whether a region (its reads: a packed table) qualifies for encode_regions_on_device: _plan_region's fast
-    path -- one sample, no trimming or alt-aligned mode, no list-aux channel, no blanking, no non-uniform
-    downsampling -- with nothing per read that a packed table lacks."""
+    """Whether a region (its reads: a packed table) qualifies for encode_regions_on_device: one sample, no list-aux
+    channel, no blanking, no non-uniform downsampling, nothing per read that a packed table lacks, and either
+    _plan_region's fast path (no trimming, no alt-aligned mode: items query the table by position) or
+    trim_reads_for_pileup with alt mode none / diff_channels / base_channels (DV_ALT_ALIGN_TABLES=1 for the latter
+    two): every candidate then draws row ranges of trimmed or alt-aligned copies (`_draws_route`)."""
     from deepvariant_amd import alt_aligned_pileup_lib as aap
     api = self._encoder_api
-    if (len(self._options.sample_options) != 1 or self._alt_mode != aap.NONE or api._need_list_aux or api._need_aux or
-        any(api._need_seq_aux or ()) or os.environ.get('DV_PY_PACKER') is not None or
-        getattr(self._options, 'trim_reads_for_pileup', False)):
+    if (len(self._options.sample_options) != 1 or api._need_list_aux or api._need_aux or
+        any(api._need_seq_aux or ()) or os.environ.get('DV_PY_PACKER') is not None):
       return False
     so = self._options.sample_options[0]
-    if (so.keep_only_window_spanning_reads or so.channels_enum_to_blank or so.variant_types_to_blank or
-        so.use_non_uniform_downsampling):
+    if so.channels_enum_to_blank or so.variant_types_to_blank or so.use_non_uniform_downsampling:
+      return False
+    if self._draws_route():
+      if self._alt_mode not in (aap.NONE, aap.DIFF_CHANNELS, aap.BASE_CHANNELS):
+        return False                                   # rows / single_row: alt images drawn in place, per region
+      if aap.get_sample_alt_aligned_pileup(self._alt_mode, so.alt_aligned_pileup or '') != self._alt_mode:
+        return False
+      if self._alt_mode != aap.NONE and os.environ.get('DV_ALT_ALIGN_TABLES') != '1':
+        return False
+    elif self._alt_mode != aap.NONE or so.keep_only_window_spanning_reads:
+      # an alt-aligned mode without trim-all: SNP candidates query the untrimmed table.  keep_only_window_spanning_
+      # reads alone also trims every candidate, but stays per region
       return False
     return reads is None or isinstance(reads, packing.ReadTable)
+
+  def _draws_route(self) -> bool:
+    """trim_reads_for_pileup: EVERY candidate draws trimmed reads, so the untrimmed table is never listed."""
+    return bool(getattr(self._options, 'trim_reads_for_pileup', False))
 
   def encode_regions_on_device(self, regions, model_shape, mean_coverage: float = 0.0):
     """encode_region_on_device for a batch of regions -- regions[k] = (candidates, the region's table), each of
     which `device_pack_ok` accepts -- with ONE pack call on the device (packing.pack_regions_device: read support
     by row, no strings) and ONE encoder launch over the merged table.  -> per region (its slice of the image
-    tensor or None, [(candidate index, alt combination)]): what encode_region_on_device returns for it."""
+    tensor or None, [(candidate index, alt combination)]): what encode_region_on_device returns for it.
+    With trim_reads_for_pileup the items are row ranges of trimmed and alt-aligned copies instead of position
+    queries: _encode_trimmed_regions_on_device."""
     import torch  # device memory + stream only
     from deepvariant_amd.device_batch import DeviceBatch
     pic = self._options.pic_options
@@ -684,6 +701,8 @@ class ExamplesGenerator:
     for _, table in regions:
       if not self.device_pack_ok(table):
         raise ValueError('encode_regions_on_device: a region does not qualify; use encode_region_on_device')
+    if self._draws_route():
+      return self._encode_trimmed_regions_on_device(regions, image_shape, float(mean_coverage))
     tables = [table for _, table in regions]
     windows = [[get_reference_bases_for_pileup(self._ref, c.variant, width) for c in cands] for cands, _ in regions]
     combos = [[list(alt_allele_combinations(c, pic.multi_allelic_mode)) if w else [] for c, w in zip(cands, wins)]
@@ -721,6 +740,166 @@ class ExamplesGenerator:
       if n > at:
         out[k] = (images[at:n], [(ci, combo) for _, ci, combo in plan[at:n]])
       at = n
+    self._alt_plan = []
+    return out
+
+  def _encode_trimmed_regions_on_device(self, regions, image_shape, mean_coverage: float):
+    """encode_regions_on_device where every candidate draws trimmed reads (`_draws_route`): per region the trim
+    call of _trim_region_reads; then for the BATCH one alt_align_table call over the concatenated trimmed tables,
+    one pack call whose items are row ranges (packing.pack_draws_device, keys traced back through the tables'
+    source rows: no name string), one upload of the trimmed and alt tables -- the untrimmed tables stay on the host
+    -- one encoder launch into a zeroed buffer (a missing alt image reads as zero) and one merge launch.  Items and
+    scratch slots stand in _plan_region's order, region after region."""
+    import torch  # device memory + stream only
+    from deepvariant_amd import alt_aligned_pileup_lib as aap
+    from deepvariant_amd.device_batch import DeviceBatch
+    pic = self._options.pic_options
+    so = self._options.sample_options[0]
+    width = pic.width
+    row_bytes = width * image_shape[2]
+    example_bytes = int(np.prod(image_shape))
+    channel_mode = self._alt_mode in (aap.BASE_CHANNELS, aap.DIFF_CHANNELS)
+    out = [(None, []) for _ in regions]
+    # 1. per region: the windows of its candidates, trimmed
+    trimmed, trim_ranges, row_base, key_base, windows = [], [], [], [], []
+    n_trimmed = n_keys = 0
+    row_keys = []
+    for cands, table in regions:
+      wins = [get_reference_bases_for_pileup(self._ref, c.variant, width) for c in cands]
+      windows.append(wins)
+      row_base.append(n_trimmed)
+      key_base.append(n_keys)
+      if not any(wins):
+        trimmed.append(None)
+        trim_ranges.append({})
+        continue
+      tables, ranges = self._trim_region_reads(cands, [table], [0], [table], [True] * len(cands))
+      trimmed.append(tables[0])
+      trim_ranges.append(ranges)
+      # a trimmed row's key is its source row's, kept apart from every other region's
+      row_keys.append(packing.copy_row_keys(tables[0], packing._row_keys(table)) + np.int32(n_keys))
+      n_trimmed += tables[0].n_reads
+      n_keys += table.n_reads
+    trimmed_tables = [t for t in trimmed if t is not None]
+    if not trimmed_tables:
+      return out
+    merged_trimmed = packing.merge_region_tables(trimmed_tables)
+    # 2. the batch's alt-align items in region, candidate, alt order (_realign_for_alt_images' rules), one call
+    alt_ranges, alt_table = {}, None
+    if self._alt_mode != aap.NONE and self._sample_needs_alt(so):
+      cfg = dict(getattr(self._options, 'aln_config', None) or DEFAULT_ALN_CONFIG)
+      items, targets, item_keys = [], [], []
+      for k, (cands, _) in enumerate(regions):
+        t = trimmed[k]
+        for ci, cand in enumerate(cands):
+          if (ci, 0) not in trim_ranges[k] or not aap.need_alt_alignment(pic, cand.variant):
+            continue
+          lo, hi = trim_ranges[k][(ci, 0)]
+          first_len = int(t.read_seq_off[lo + 1]) - int(t.read_seq_off[lo]) if hi > lo else 0
+          for alt in cand.variant.alternate_bases:
+            haplotype, ref_start, _ = aap.create_haplotype(self._ref, cand.variant, alt, self._half_width)
+            if len(haplotype) < width:
+              continue          # too close to the contig start: no alt-aligned pixels
+            items.append((row_base[k] + lo, hi - lo, len(targets), ref_start, first_len if first_len > 15 else 200))
+            targets.append(haplotype)
+            item_keys.append(((k, ci, alt), haplotype[:width]))
+      if items:
+        alt_table, rows = aap.alt_align_table(merged_trimmed, items, targets, cfg, device=True)
+        for (key, window), (a, b) in zip(item_keys, rows):
+          alt_ranges[key] = (a, b, window)
+        if alt_table.read_sort_pos is None:
+          alt_table.read_sort_pos = alt_table.read_pos.copy()
+        row_keys.append(packing.copy_row_keys(alt_table, np.concatenate(row_keys)))
+    # 3. the draws: reference images first, the alt images in scratch slots behind ALL examples of the batch
+    ref_windows: List[bytes] = []
+    as_bytes = lambda w: w.encode() if isinstance(w, str) else bytes(w)       # noqa: E731
+    ref_draws, alt_draws, plans, merge = [], [], [], []
+    n_alts = []
+    slot_bytes = self._max_sample_height() * row_bytes
+    for k, (cands, _) in enumerate(regions):
+      plan = []
+      for ci, cand in enumerate(cands):
+        if not windows[k][ci]:
+          continue                                       # edge of the contig
+        variant = cand.variant
+        alts = list(variant.alternate_bases)
+        ref_windows.append(as_bytes(windows[k][ci]))
+        ref_idx = len(ref_windows) - 1
+        lo, hi = trim_ranges[k][(ci, 0)]
+        cand_index = len(n_alts)
+        n_alts.append(len(alts))
+        need_alt = self._alt_mode != aap.NONE and aap.need_alt_alignment(pic, variant)
+        for combo in alt_allele_combinations(cand, pic.multi_allelic_mode):
+          mask = 0
+          for a in combo:
+            mask |= 1 << alts.index(a)
+          example = len(ref_draws)
+          ref_draws.append((cand_index, mask, row_base[k] + lo, hi - lo, ref_idx, variant.start,
+                            variant.start - self._half_width, so.pileup_height, example * example_bytes, mean_coverage))
+          if need_alt and self._sample_needs_alt(so):
+            slots = [None, None]
+            for j, alt in enumerate(combo[:2]):            # CHECK_LE(alt_combination.size(), 2)
+              if (k, ci, alt) not in alt_ranges:
+                break                                      # haplotype shorter than the window: stop
+              a, b, hap_window = alt_ranges[(k, ci, alt)]
+              ref_windows.append(as_bytes(hap_window))
+              slots[j] = len(alt_draws)
+              alt_draws.append((cand_index, mask, n_trimmed + a, b - a, len(ref_windows) - 1, variant.start,
+                                variant.start - self._half_width, so.pileup_height, len(alt_draws) * slot_bytes,
+                                mean_coverage))
+            if channel_mode and slots[0] is not None:
+              merge.append((example, 0, so.pileup_height, slots))
+          plan.append((ci, combo))
+      plans.append(plan)
+    n_examples = len(ref_draws)
+    if not n_examples:
+      return out
+    scratch0 = n_examples * example_bytes
+    draws = np.array(ref_draws + alt_draws, packing.DRAW_DTYPE)
+    draws['out_off'][n_examples:] += np.uint64(scratch0)
+    # support by integer key, the region's keys shifted like its rows' (an entry that names no read stays none)
+    first_support, n_support, key_parts, alt_parts = [], [], [], []
+    at = 0
+    for k, (cands, table) in enumerate(regions):
+      drawn = [c for c, w in zip(cands, windows[k]) if w]
+      if not drawn:
+        continue
+      first, count, support_key, support_alt = packing.support_arrays(table, drawn)
+      first_support.append(first.astype(np.int64) + at)
+      n_support.append(count)
+      key_parts.append(np.where(support_key < 0, support_key, support_key + np.int32(key_base[k])).astype(np.int32))
+      alt_parts.append(support_alt)
+      at += len(support_key)
+    n_rows = n_trimmed + (alt_table.n_reads if alt_table is not None else 0)
+    dev = torch.device('cuda', self._device)
+    with torch.cuda.device(dev):
+      stream = torch.cuda.current_stream(dev).cuda_stream
+      packed = packing.pack_draws_device(
+          np.concatenate(row_keys), n_rows, draws, n_alts, np.concatenate(first_support), np.concatenate(n_support),
+          np.concatenate(key_parts), np.concatenate(alt_parts), ref_windows_list=ref_windows, stream=stream)
+      if self._device_encoder is None:
+        self._device_encoder = _Encoder(pic, pic.width, self._device)
+      merged = packing.merge_region_tables([merged_trimmed] + ([alt_table] if alt_table is not None else []))
+      batch = packing.PackedBatch(table=merged, width=width, use_ref_aux=self._encoder_api._need_ref_aux)
+      batch.ref_windows_list = packed.ref_windows_list
+      dbatch = DeviceBatch.from_packed_regions(batch, packed, dev, pic.reference_band_height,
+                                               bool(pic.sort_by_alt_allele_support), so.pileup_height)
+      n_bytes = scratch0 + len(alt_draws) * slot_bytes
+      flat = (torch.zeros if self._alt_mode != aap.NONE else torch.empty)(n_bytes, dtype=torch.uint8, device=dev)
+      dbatch.encode(self._device_encoder, image_shape[2], flat, stream=stream)
+      if merge:
+        self._alt_plan, self._alt_scratch0 = merge, scratch0
+        self._merge_alt_channels_device(flat, image_shape)
+      # as in encode_regions_on_device: the handle's arrays live until the encoder that reads them has run
+      done = torch.cuda.Event()
+      done.record(torch.cuda.current_stream(dev))
+      self._drawing = [(e, b) for e, b in getattr(self, '_drawing', []) if not e.query()] + [(done, dbatch)]
+    images = flat[:scratch0].view([n_examples] + list(image_shape))
+    at = 0
+    for k, plan in enumerate(plans):
+      if plan:
+        out[k] = (images[at:at + len(plan)], plan)
+      at += len(plan)
     self._alt_plan = []
     return out
 

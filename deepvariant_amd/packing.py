@@ -1318,6 +1318,74 @@ def pack_regions_device(tables: Sequence['ReadTable'], candidates_per_region: Se
   return packed, plan
 
 
+# ---- items whose read list is GIVEN (dv_pack_draws_device): trimmed and alt-aligned regions draw row ranges of
+# window-cut copies, which trim_table / alt_align_table trace back to their source rows
+DRAW_DTYPE = np.dtype([('cand', np.int32), ('combo_mask', np.uint32), ('row_first', np.int32), ('n_rows', np.int32),
+                       ('ref_idx', np.uint32), ('variant_start', np.int32), ('image_start', np.int32),
+                       ('height', np.uint16), ('out_off', np.uint64), ('mean_coverage', np.float32)], align=True)
+_CAND_DTYPE = np.dtype([('start', np.int64), ('end', np.int64), ('n_alts', np.int32), ('ref_idx', np.int32),
+                        ('first_combo', np.uint32), ('n_combos', np.uint32), ('first_support', np.uint32),
+                        ('n_support', np.uint32)], align=True)
+
+
+def table_src_rows(table: 'ReadTable') -> Optional[np.ndarray]:
+  """int32 per row of a table that trim_table or alt_align_table returned: the row of THEIR input table it was
+  made from (None for any other table).  Kept next to the table like _key_ids_cache: no dataclass field, so no
+  field-for-field comparison sees it."""
+  return table.__dict__.get('_src_row_cache')
+
+
+def set_table_src_rows(table: 'ReadTable', src_row) -> None:
+  table.__dict__['_src_row_cache'] = np.ascontiguousarray(src_row, np.int32).reshape(table.n_reads)
+
+
+def copy_row_keys(table: 'ReadTable', source_keys: np.ndarray) -> np.ndarray:
+  """The integer keys of a trimmed or alt-aligned table's rows, given those of its input table's rows: no name
+  string is touched."""
+  src = table_src_rows(table)
+  if src is None:
+    raise ValueError('copy_row_keys: the table does not remember its source rows (trim_table / alt_align_table do)')
+  return np.ascontiguousarray(np.asarray(source_keys, np.int32)[src], np.int32)
+
+
+def pack_draws_stats() -> Dict[str, int]:
+  """dv_pack_draws_device_last_stats of the calling thread."""
+  s = _lib.DvPackDrawsStats()
+  _lib.check(_lib.lib().dv_pack_draws_device_last_stats(C.byref(s)))
+  return {name: int(getattr(s, name)) for name, _ in s._fields_}    # pylint: disable=protected-access
+
+
+def pack_draws_device(rows_key, n_rows: int, draws, n_alts, first_support, n_support, support_key, support_alt,
+                      ref_windows_list: Optional[List[bytes]] = None, stream=None) -> 'PackedRegions':
+  """dv_pack_draws_device (include/dvhip.h): `draws` (DRAW_DTYPE records, or tuples in its field order) are encoder
+  items whose list is rows row_first .. row_first + n_rows - 1 of a concatenated table of `n_rows` rows with integer
+  keys `rows_key` (None: every row its own key); candidate i has n_alts[i] alts and the slice first_support[i],
+  n_support[i] of support_key / support_alt.  One native call, one launch; the arrays stay on the device."""
+  lib = _lib.lib()
+  draws = np.ascontiguousarray(draws if isinstance(draws, np.ndarray) and draws.dtype == DRAW_DTYPE
+                               else np.array([tuple(d) for d in draws], DRAW_DTYPE))
+  n_alts = np.asarray(n_alts, np.int32).reshape(-1)
+  cands = np.zeros(len(n_alts), _CAND_DTYPE)
+  cands['n_alts'] = n_alts
+  cands['first_support'] = np.asarray(first_support, np.uint32).reshape(-1)
+  cands['n_support'] = np.asarray(n_support, np.uint32).reshape(-1)
+  key_arr = np.ascontiguousarray(support_key, np.int32)
+  alt_arr = np.ascontiguousarray(support_alt, np.uint8)
+  if len(key_arr) != len(alt_arr):
+    raise ValueError('pack_draws_device: support_key and support_alt differ in length')
+  if rows_key is not None:
+    rows_key = np.ascontiguousarray(rows_key, np.int32)
+    if len(rows_key) != n_rows:
+      raise ValueError('pack_draws_device: rows_key does not have one entry per row')
+  handle = C.c_void_p()
+  _lib.check(lib.dv_pack_draws_device(
+      rows_key.ctypes.data if rows_key is not None and n_rows else None, int(n_rows),
+      draws.ctypes.data if len(draws) else None, len(draws), cands.ctypes.data if len(cands) else None, len(cands),
+      key_arr.ctypes.data if len(key_arr) else None, alt_arr.ctypes.data if len(alt_arr) else None, len(key_arr),
+      C.c_void_p(stream) if stream else None, C.byref(handle)))
+  return PackedRegions(handle, len(draws), list(ref_windows_list or []), [0])
+
+
 @dataclasses.dataclass
 class PackedBatch:
   """Host image of `dv_batch` (numpy arrays), plus the ctypes view."""

@@ -536,6 +536,56 @@ typedef struct dv_pack_device_stats {
 /* What the calling thread's last dv_pack_regions_device did. */
 int dv_pack_regions_device_last_stats(dv_pack_device_stats* out);
 
+/* ---- the same handle for items whose read list is GIVEN: a row range of a table ----------
+ * A trimmed or alt-aligned region draws window-cut COPIES of its reads: every candidate owns a row range of the
+ * trimmed table and every (candidate, alt) a row range of the alt-aligned one, so there is no position query -- only
+ * the per-read rule of dv_pack_regions_device remains.  A `draw` is one encoder item: its list is the rows
+ * row_first .. row_first + n_rows - 1 of the concatenated table, in that order, and its record (reference window,
+ * starts, height, out_off, mean coverage) is the caller's -- alt images go to scratch rows behind the examples, so
+ * out_off is not item * example_bytes.
+ *   rows_key   int32 per row of the concatenated table: two rows carry equal values iff they are copies of one read
+ *              key of ONE region (the caller keeps the ids of different regions apart); NULL = every row is its own
+ *              key, and a support entry then names a row.
+ *   cands      dv_pack_candidate with only n_alts, first_support and n_support read (its slice of support_key /
+ *              support_alt); start, end, ref_idx, first_combo and n_combos are ignored -- the draw carries them.
+ * Per row r of a draw of candidate c: first_alt is the smallest support_alt among c's entries with r's key and group
+ * the largest; with no such entry first_alt = 255 and group = n_alts; list_code = 0 for 255, 1 if bit first_alt of
+ * combo_mask is set, else 2; list_group = group.  An entry whose key matches no row is ignored.
+ * Every size is known before the launch (item_list_off is the prefix sum of n_rows, max_list_len the largest n_rows):
+ * one upload, one allocation at the exact size, one launch (pack_draws_kernel, one wave per draw) and no
+ * synchronisation -- with a caller's stream the call returns without waiting and the arrays are ready in stream order;
+ * with stream NULL it waits for the library's own stream, as dv_pack_regions_device does.  Two calls give identical
+ * bytes.  The handle is dv_pack_regions_device's: dv_packed_regions_fill_batch, _download, _items and _free work on
+ * it unchanged (item_candidate / item_combo are the draws' cand / combo_mask).
+ * DV_ERR_INVALID_ARGUMENT before any device work, *out NULL: null pointers with non-zero counts or negative counts; a
+ * draw whose row range leaves [0, n_rows), whose cand is outside [0, n_cands) or whose height is 0; a candidate's
+ * support slice outside the arrays, n_alts outside [0, 32] or a support_alt >= n_alts; a combo_mask bit at or above
+ * n_alts.  More than 2^31 - 1 draws or 2^32 - 1 list entries: DV_ERR_BAD_INPUT.  No draw: DV_OK, an empty handle, no
+ * device needed.  Otherwise no device is DV_ERR_NO_DEVICE. */
+typedef struct dv_pack_draw {
+  int32_t cand;             /* index into cands */
+  uint32_t combo_mask;      /* bit i = alternate_bases[i] is in the combination */
+  int32_t row_first, n_rows;
+  uint32_t ref_idx;         /* item_ref_idx */
+  int32_t variant_start;    /* item_variant_start */
+  int32_t image_start;      /* item_image_start */
+  uint16_t height;          /* item_height (> 0) */
+  uint64_t out_off;         /* item_out_off */
+  float mean_coverage;      /* item_mean_coverage */
+} dv_pack_draw;
+
+int dv_pack_draws_device(const int32_t* rows_key, int32_t n_rows, const dv_pack_draw* draws, int64_t n_draws,
+                         const dv_pack_candidate* cands, int32_t n_cands, const int32_t* support_key,
+                         const uint8_t* support_alt, uint32_t n_support, void* stream, dv_packed_regions** out);
+typedef struct dv_pack_draws_stats {
+  int64_t draws;
+  int64_t candidates;
+  int64_t list_entries;
+  int64_t launches;
+} dv_pack_draws_stats;
+/* What the calling thread's last dv_pack_draws_device did. */
+int dv_pack_draws_device_last_stats(dv_pack_draws_stats* out);
+
 /* ---- read realigner (host only) ----------------------------------------------
  * Replaces deepvariant/realigner/fast_pass_aligner.{h,cc} (class FastPassAligner) and the
  * local aligner it links (libssw v1.2.5 through deepvariant/realigner/ssw.{h,cc}); used by
