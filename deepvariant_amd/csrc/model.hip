@@ -159,9 +159,9 @@ int enqueue_stem_a(const Pass& ps, int oi) {
   if (m->blank_on()) {
     a.blank_thr = m->blank_thr(1);
     a.blank_src = static_cast<const _Float16*>(m->d_blank_c2.ptr);
-    a.blank_need = m->blank_thr(5);
+    a.blank_need = m->blank_read_through() ? nullptr : m->blank_thr(5);
   }
-  TraceScope tr(ps.stream, std::string(m->blank_on() ? "[blank tiles copied] " : "") + "stem_a conv3x3s2 " + std::to_string(op.cin_real) + "->32 + conv3x3 32->32 (fused)",
+  TraceScope tr(ps.stream, std::string(!m->blank_on() ? "" : m->blank_read_through() ? "[blank tiles left to stem_b] " : "[blank tiles copied] ") + "stem_a conv3x3s2 " + std::to_string(op.cin_real) + "->32 + conv3x3 32->32 (fused)",
                 2.0 * n * (static_cast<double>(op.oh) * op.ow * op.kh * op.kw * op.cin_real * op.cout +
                            static_cast<double>(c2.oh) * c2.ow * 9 * 32 * 32),
                 static_cast<double>(n) * (op.ih * op.iw * op.cin_real + 2.0 * c2.oh * c2.ow * 32));
@@ -256,8 +256,13 @@ int enqueue_stem_b(const Pass& ps, int oi) {
     a.blank_thr = m->blank_thr(2);
     a.blank_src = static_cast<const _Float16*>(m->d_blank_b.ptr);
     a.blank_need = m->blank_thr(6);
+    a.blank_strip = m->blank_copy_tiles ? 0 : 1;
+    if (m->blank_read_through()) {
+      a.blank_cut = m->blank_thr(7);
+      a.blank_in = static_cast<const _Float16*>(m->d_blank_c2.ptr);
+    }
   }
-  TraceScope tr(ps.stream, std::string(m->blank_on() ? "[blank tiles copied] " : "") + "stem_b conv3x3 32->64 + maxpool3s2 + conv1x1 64->" + std::to_string(c4.cout) + " (fused)",
+  TraceScope tr(ps.stream, std::string(!m->blank_on() ? "" : m->blank_copy_tiles ? "[blank tiles copied] " : m->blank_read_through() ? "[blank rows read through, blank strip copied] " : "[blank strip copied] ") + "stem_b conv3x3 32->64 + maxpool3s2 + conv1x1 64->" + std::to_string(c4.cout) + " (fused)",
                 2.0 * n * (static_cast<double>(op.oh) * op.ow * 9 * 32 * 64 +
                            static_cast<double>(c4.oh) * c4.ow * 64 * c4.cout),
                 2.0 * n * (static_cast<double>(op.ih) * op.iw * 32 + static_cast<double>(c4.oh) * c4.ow * c4.cout));
@@ -771,9 +776,10 @@ int dv_model_create(const dv_model_desc* desc, int device, dv_model** out) {
   if (!(getenv("DV_BLANK_SKIP") != nullptr && atoi(getenv("DV_BLANK_SKIP")) == 0) &&
       m->ops[0].first_u8 && m->blank_conv4_op >= 0 && m->ops[m->blank_conv4_op].group_followers == 0 &&
       (static_cast<size_t>(desc->height) * desc->width * desc->channels) % 4 == 0) {
-    if (int rc = m->d_blank_thr.reserve(static_cast<size_t>(7) * desc->max_batch * sizeof(int))) return rc;
+    if (int rc = m->d_blank_thr.reserve(static_cast<size_t>(dv_model::kBlankThrRows) * desc->max_batch * sizeof(int))) return rc;
     DV_HIP_CHECK(hipMemset(m->d_blank_thr.ptr, 0, m->d_blank_thr.cap));
     m->blank_skip = true;
+    m->blank_copy_tiles = getenv("DV_BLANK_COPY_TILES") != nullptr && atoi(getenv("DV_BLANK_COPY_TILES")) != 0;
   }
   *out = m.release();
   return DV_OK;

@@ -125,11 +125,20 @@ struct dv_model {
   bool blank_enabled = true;      // dv_model_set_blank_skip
   bool blank_ready = false;       // the blank responses have been computed (after load_weights)
   int blank_conv4_op = -1;        // op index of the stem's 3x3 80->192
-  dv::DeviceBuffer d_blank_thr;   // int32 [7][max_batch], blank_rows_kernel + blank_need_kernel
+  dv::DeviceBuffer d_blank_thr;   // int32 [kBlankThrRows][max_batch], blank_rows_kernel + blank_need_kernel
+  static constexpr int kBlankThrRows = 8;
   dv::DeviceBuffer d_blank_conv4; // the 3x3 80->192's output (pooled when its kernel pools) for the all-blank image (one example)
   dv::DeviceBuffer d_blank_c2;    // conv2's output for the all-blank image
   dv::DeviceBuffer d_blank_b;     // stem_b's (the 1x1 64->80's) output for the all-blank image
   bool blank_on() const { return blank_ready && blank_enabled; }
+  // Where the consumers of the two inter-kernel tensors get the blank rows they read.  Default: stem_b
+  // reads conv2's blank rows straight from the blank response (stem_a copies nothing) and copies, of its own blank
+  // rows, the strip the 3x3 80->192 reads, once per example.  DV_BLANK_COPY_TILES=1 (read when the model is created):
+  // both producers copy every blank tile a consumer's computed tile touches, whole -- the earlier scheme, kept for A/B.
+  bool blank_copy_tiles = false;
+  bool blank_read_through() const {   // the stem_a -> stem_b link: both fused (the per-layer conv2 keeps copying)
+    return blank_on() && !blank_copy_tiles && ops.size() > 3 && ops[0].stem_a && ops[2].stem_b && d_blank_c2.ptr != nullptr;
+  }
   // Precise mode (round 6): every fp16 tensor of the 17x17 and 8x8 stages is stored as hi + lo fp16 pieces
   // and its consumers multiply both (K doubled, the factorised-7x7 chains run per layer) -- what it takes to hold 1e-3
   // on every long-read seed, at about +40 % of the forward.  Default: on for > 8 input channels (dv_model_create).

@@ -221,6 +221,9 @@ __global__ void preprocess_kernel(const ExtPtrs* ext, size_t in_off, _Float16* o
 // walk, which goes down to the deepest pooled threshold among the examples a 32-position fragment spans (conv row r
 // reads rows r..r+2; the walk's last row is 2 s_end).
 // (stem_b_fused / conv4_walks = 0: the consumer is a per-layer kernel that may read every row -- everything is wanted.)
+// thr row 7: cut2 = the first conv2 row the fused stem_a did not compute (its tiles of kStemA_TH rows are computed iff
+// they start above t2).  When stem_b reads the blank rows through, it takes conv2 rows >= cut2 from the blank response
+// and stem_a copies nothing (model.hip enqueue_stem_a / enqueue_stem_b).
 __global__ void blank_need_kernel(int* thr, int stride, int n, int oh2, int ph_b, int ow4, int p4, int stem_b_fused,
                                   int conv4_walks) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -232,6 +235,8 @@ __global__ void blank_need_kernel(int* thr, int stride, int n, int oh2, int ph_b
   int m5 = 0;
   for (int j = max(0, i - span); j <= min(n - 1, i + span); ++j) m5 = max(m5, min(thr[4 * stride + j], p4));
   thr[6 * stride + i] = !conv4_walks ? ph_b : m5 > 0 ? min(ph_b, 2 * m5 + 3) : 0;
+  const int t2 = max(thr[stride + i], 0);
+  thr[7 * stride + i] = min(oh2, dv::kStemA_TH * ((t2 + dv::kStemA_TH - 1) / dv::kStemA_TH));
 }
 
 __global__ __launch_bounds__(256) void blank_rows_kernel(const ExtPtrs* ext, size_t in_off, int n_hint0, int H,
@@ -263,7 +268,9 @@ __global__ __launch_bounds__(256) void blank_rows_kernel(const ExtPtrs* ext, siz
     }
     if (mine >= 0) atomicMax(&last, mine);
     __syncthreads();
-    if (last >= 0) break;   // uniform: read after the barrier
+    const int found = last;   // uniform: read after the barrier ...
+    __syncthreads();          // ... and before any wave's atomicMax of the next trip
+    if (found >= 0) break;
   }
   if (tid == 0) {
     const int r = hinted ? hinted_rows : last < 0 ? 0 : last / row_bytes + 1;

@@ -351,7 +351,8 @@ __global__ __launch_bounds__(A_THREADS, 2) void stem_a_kernel(StemAArgs p) {
       int nb_, yb, xb;
       tile_origin(tt, nb_, yb, xb);
       if (yb < p.blank_thr[nb_]) break;
-      if (yb < p.blank_need[nb_]) copy_blank_tile(nb_, yb, xb);   // (else: nobody reads this tile)
+      // (else: nobody reads this tile from here -- no blank_need: stem_b takes the blank rows from the blank response itself)
+      if (p.blank_need != nullptr && yb < p.blank_need[nb_]) copy_blank_tile(nb_, yb, xb);
       tt += gridDim.x;
     }
     return tt;
@@ -533,6 +534,8 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
 
   // ---- per-thread constants ----------------------------------------------------------------
   unsigned prel[B_PASSES];   // patch piece -> byte offset relative to the tile origin
+  unsigned prow = 0;         // its patch row, 6 bits per pass (read-through of blank rows, dma_round)
+  static_assert(B_PTH <= 64 && 6 * B_PASSES <= 32, "the patch rows of all passes pack into one register");
 #pragma unroll
   for (int ps = 0; ps < B_PASSES; ++ps) {
     const int e = ps * B_THREADS + tid;
@@ -541,6 +544,7 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
     prel[ps] = e < B_PT_PIECES
                    ? static_cast<unsigned>(((g * p.ig.hp + row) * p.ig.wp + col) * 16)
                    : 0x80000000u;
+    prow |= (e < B_PT_PIECES ? static_cast<unsigned>(row) : 0u) << (6 * ps);
   }
   // conv3: fragments wave and wave + B_WAVES of the tile
   unsigned b3[2], c3dst[2];
@@ -588,11 +592,29 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
   auto patch_soff = [&](int py0, int px0) {
     return static_cast<unsigned>(((2 * py0 - 1 + p.ig.halo) * p.ig.wp + 2 * px0 - 1 + p.ig.halo) * 16);
   };
-  auto dma_round = [&](int ps, const __amdgpu_buffer_rsrc_t rsrc, unsigned soff, unsigned buf_off) {
+  // Blank rows read through (StemBArgs::blank_cut): the all-blank image's conv2 output has the image's geometry, so a
+  // piece of patch row >= rcut (the tile's first row that stem_a neither computed nor copied) comes from the same
+  // offset under the blank descriptor.  A granule spans about three patch rows: the lanes on either side of rcut issue
+  // their own DMA under complementary masks, and each lands at the granule's base + lane * 16 as before.
+  const __amdgpu_buffer_rsrc_t rblank = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<_Float16*>(p.blank_cut != nullptr ? p.blank_in : p.in), 0, p.in_img_bytes, 0x00020000);
+  auto patch_rcut = [&](int n, int py0) {   // workgroup-uniform
+    return p.blank_cut != nullptr ? p.blank_cut[n] - (2 * py0 - 1) : 0x7fffffff;
+  };
+  auto dma_round = [&](int ps, const __amdgpu_buffer_rsrc_t rsrc, unsigned soff, unsigned buf_off, int rcut) {
     const unsigned g0 = static_cast<unsigned>((ps * B_WAVES + wave_u) * 1024);
     if (g0 < static_cast<unsigned>(B_PT_BYTES)) {  // wave-uniform
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsrc, (__attribute__((address_space(3))) void*)(smem + buf_off + g0), 16, prel[ps], soff, 0, 0);
+      auto* dst = (__attribute__((address_space(3))) void*)(smem + buf_off + g0);
+      unsigned rows = prow;
+      asm volatile("" : "+v"(rows));   // the row is extracted here, not once per pass outside the tile loop (five registers)
+      if (static_cast<int>((rows >> (6 * ps)) & 63u) < rcut) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, dst, 16, prel[ps], soff, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rblank, dst, 16, prel[ps], soff, 0, 0);
+        // two DMAs under complementary lane masks: keeps the branches from being merged into one DMA with a per-lane
+        // descriptor (a readfirstlane loop)
+        asm volatile("");
+      }
     }
   };
 
@@ -623,13 +645,47 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
       if (at[k] != 0xffffffffu) dst[at[k]] = v[k];
     }
   };
+  // blank_strip: only rows [row0, row1) of the blank rows are read by the consumer -- one strip over all tile columns,
+  // copied by the workgroup that passes the first tile of the example's first blank tile row
+  auto copy_blank_strip = [&](int nb_, int row0, int row1) {
+    const uint4_t* src = reinterpret_cast<const uint4_t*>(p.blank_src);
+    uint4_t* dst = reinterpret_cast<uint4_t*>(p.out) +
+                   static_cast<size_t>(nb_) * p.og.groups * ogstride;
+    const int per_group = (row1 - row0) * p.PW;
+    const int total = (p.Cout4 + 7) / 8 * per_group;
+    constexpr int kPer = 3;   // pieces per thread and trip: all loads, then all stores
+    for (int e0 = 0; e0 < total; e0 += kPer * B_THREADS) {   // uniform
+      uint4_t v[kPer];
+      unsigned at[kPer];
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        const int e = e0 + k * B_THREADS + tid;
+        const int g = e / per_group, r = e - g * per_group;
+        const int yy = r / p.PW, xx = r - yy * p.PW;
+        at[k] = e < total ? static_cast<unsigned>(g) * ogstride +
+                                static_cast<unsigned>((row0 + yy + p.og.halo) * p.og.wp + xx + p.og.halo)
+                          : 0xffffffffu;
+        if (at[k] != 0xffffffffu) v[k] = src[at[k]];
+      }
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        if (at[k] != 0xffffffffu) dst[at[k]] = v[k];
+      }
+    }
+  };
   auto next_tile = [&](int tt) {
     if (p.blank_thr == nullptr) return tt;
     while (tt < p.total_tiles) {
       int nb_, pyb, pxb;
       tile_coords(tt, nb_, pyb, pxb);
-      if (pyb < p.blank_thr[nb_]) break;
-      if (pyb < p.blank_need[nb_]) copy_blank_tile(nb_, pyb, pxb);   // (else: nobody reads this tile)
+      const int thr = p.blank_thr[nb_];
+      if (pyb < thr) break;
+      const int need = p.blank_need[nb_];   // (at or below it: nobody reads this tile)
+      if (p.blank_strip) {
+        if (pxb == 0 && pyb < thr + B_PH && pyb < need) copy_blank_strip(nb_, pyb, need);
+      } else if (pyb < need) {
+        copy_blank_tile(nb_, pyb, pxb);
+      }
       tt += gridDim.x;
     }
     return tt;
@@ -641,8 +697,9 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
     tile_coords(t, n, py0, px0);
     const __amdgpu_buffer_rsrc_t r0 = patch_desc(n);
     const unsigned so0 = patch_soff(py0, px0);
+    const int rc0 = patch_rcut(n, py0);
 #pragma unroll
-    for (int ps = 0; ps < B_PASSES; ++ps) dma_round(ps, r0, so0, 0);
+    for (int ps = 0; ps < B_PASSES; ++ps) dma_round(ps, r0, so0, 0, rc0);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   unsigned long long ph[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -665,6 +722,7 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
     // +1.2 k cycles per tile -- the issue slots then sit in the MFMA-free pool phase.
     const __amdgpu_buffer_rsrc_t rn = patch_desc(more ? nn : n);
     const unsigned son = patch_soff(pyn, pxn);
+    const int rcn = patch_rcut(more ? nn : n, pyn);
     DV_PHASE(0)
 
     // ---- conv3 (3x3 'same', 32 -> 64) on this wave's two fragments -> LDS ---------------------
@@ -681,7 +739,7 @@ __global__ __launch_bounds__(B_THREADS, 2) void stem_b_kernel(StemBArgs p) {
             acc_lo, acc_up,
             [&](int sI) {
               if (m == 0 && more && sI % 3 == 0 && sI / 3 < B_PASSES) {
-                dma_round(sI / 3, rn, son, buf ^ B_PT_BYTES);
+                dma_round(sI / 3, rn, son, buf ^ B_PT_BYTES, rcn);
               }
             });
         if (c3ok[m]) {   // the last fragment's surplus lanes have no slot in the tile

@@ -48,7 +48,8 @@ struct StemAArgs {
   const int* blank_thr;
   const _Float16* blank_src;
   // blank_need[n] = conv2 rows of example n that stem_b's computed tiles read: blank tiles below that row are not
-  // even copied -- nothing reads them (the tensor keeps whatever an earlier forward left there)
+  // even copied -- nothing reads them (the tensor keeps whatever an earlier forward left there).  NULL = no blank tile
+  // is copied at all: the consumer is stem_b reading the blank rows through (StemBArgs::blank_cut).
   const int* blank_need;
 };
 
@@ -90,6 +91,15 @@ struct StemBArgs {
   const int* blank_thr;
   const _Float16* blank_src;
   const int* blank_need;  // rows of example n the 3x3 80->192's walk reads (see StemAArgs::blank_need)
+  // Read-through of the input's blank rows: blank_cut[n] = first conv2 row of example n that the fused stem_a did not
+  // compute (and, with StemAArgs::blank_need = NULL, did not copy either); the patch loader takes rows >= blank_cut[n]
+  // from blank_in, the all-blank image's conv2 output (one example, `ig`), instead of from `in`.  NULL = every row of
+  // `in` that a computed tile reads is valid.
+  const int* blank_cut;
+  const _Float16* blank_in;
+  // 1: of the blank rows below the last computed tile row only [that row, blank_need[n]) are copied from blank_src,
+  // once per example as one strip over all tile columns; 0: every blank tile that starts above blank_need[n] is copied whole
+  int blank_strip;
 };
 
 void launch_stem_a(const StemAArgs& a, int blocks, hipStream_t stream);

@@ -1463,6 +1463,9 @@ int dv_model_infer(dv_model* m, const uint8_t* images, int n, float* probs,
  * precomputed response instead of multiplying -- bit-identical to the dense path (tests/test_hip_blank_skip.py), so
  * probabilities are unchanged; only the executed work depends on the images' depth.  `enabled` = 0 runs the dense path
  * (bench.py reports both); the environment variable DV_BLANK_SKIP=0 does the same for a whole process.
+ * DV_BLANK_COPY_TILES=1 (read by dv_model_create) makes the two fused stem kernels copy every blank tile their consumer
+ * touches, whole, instead of letting stem_b read conv2's blank rows from the response itself and copy one strip per
+ * image -- the same bits either way (tests/test_hip_blank_readthrough.py); kept for A/B runs.
  * dv_model_blank_thresholds: what the last forward's scan found for its first n examples, out[k * n + i] with
  * k = 0 first all-zero row, 1..4 the first blank-determined row of conv2 / stem_b / the 3x3 80->192 / its pooled
  * output (bench.py derives the executed FLOPs from them); DV_ERR_UNSUPPORTED when the model does not skip. */
