@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     'dv_alt_align_device_last_stats',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
+    'dv_debruijn_paths_batch', 'dv_debruijn_paths_batch_device', 'dv_debruijn_paths_free', 'dv_debruijn_paths_last_stats',
     'dv_debruijn_device_last_stats', 'dv_debruijn_from_compact', 'dv_realign_regions', 'dv_realign_result_free', 'dv_phase_reads',
     'dv_phase_reads_batch', 'dv_phase_reads_batch_device', 'dv_phase_device_last_stats',
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
@@ -328,6 +329,23 @@ class DvDebruijnDeviceStats(C.Structure):
               ('launches', C.c_int64), ('windows_rejected', C.c_int64)]
 
 
+# include/dvhip.h: what the device form of pruning and path enumeration covers (a call with a larger max_num_paths, and
+# a window whose haplotypes' text is longer, are computed by the host code inside the same call)
+DV_DEBRUIJN_DEVICE_MAX_PATHS = 1024
+DV_DEBRUIJN_DEVICE_MAX_HAP_BYTES = 262144
+DV_DEBRUIJN_PATHS_OK, DV_DEBRUIJN_PATHS_NO_GRAPH, DV_DEBRUIJN_PATHS_TOO_MANY = 0, 1, 2
+
+
+class DvDebruijnPaths(C.Structure):
+  _fields_ = [('k', C.POINTER(C.c_int32)), ('status', C.POINTER(C.c_int32)), ('hap_first', C.POINTER(C.c_int32)),
+              ('hap_off', C.POINTER(C.c_int64)), ('hap_text', C.POINTER(C.c_char))]
+
+
+class DvDebruijnPathsStats(C.Structure):
+  _fields_ = [('windows', C.c_int64), ('windows_on_host', C.c_int64), ('paths', C.c_int64), ('hap_bytes', C.c_int64),
+              ('launches', C.c_int64), ('bytes_down', C.c_int64)]
+
+
 class DvRealignRegion(C.Structure):
   _fields_ = [('bases', C.c_void_p), ('quals', C.c_void_p), ('n_bases', C.c_int64), ('read_seq_off', C.c_void_p),
               ('read_mapq', C.c_void_p), ('read_start', C.c_void_p), ('read_end', C.c_void_p),
@@ -588,6 +606,11 @@ def lib():
     l.dv_debruijn_compact_free.argtypes = [C.c_void_p]
     l.dv_debruijn_compact_free.restype = None
     l.dv_debruijn_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_debruijn_paths_batch.argtypes = l.dv_debruijn_compact_batch.argtypes
+    l.dv_debruijn_paths_batch_device.argtypes = l.dv_debruijn_compact_batch_device.argtypes
+    l.dv_debruijn_paths_free.argtypes = [C.c_void_p]
+    l.dv_debruijn_paths_free.restype = None
+    l.dv_debruijn_paths_last_stats.argtypes = [C.c_void_p]
     l.dv_debruijn_from_compact.argtypes = ([C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7)

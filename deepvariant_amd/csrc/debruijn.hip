@@ -1,6 +1,7 @@
 // debruijn.hip -- the realigner's local assembly up to pruning (debruijn_graph.cpp: DeBruijnGraph::build's choice of
 // k, the constructor, has_cycle) for every window of a batch in one kernel launch, and the C entry points
-// dv_debruijn_compact_batch / dv_debruijn_compact_batch_device / dv_debruijn_from_compact.
+// dv_debruijn_compact_batch / dv_debruijn_compact_batch_device / dv_debruijn_from_compact; behind that kernel, pruning
+// and the candidate haplotypes themselves in a second launch (dv_debruijn_paths_batch / dv_debruijn_paths_batch_device).
 //
 // Contract: DeBruijnGraph::build up to, but not including, prune / prune_lite, restated without the maps.  For a
 // window with reference bytes ref (raw, never upper-cased), reads (upper-cased by the call), options o:
@@ -43,6 +44,27 @@
 // LDS.  Every loop is bounded: a probe sequence by the table's size (then the window's
 // overflow flag is set and the host builds it), the peel by vertices + 1 rounds, a chain by the vertex count, an
 // edge list by the edge count, the k loop by the schedule; no workgroup waits for another.
+//
+// Pruning and path enumeration (dv_debruijn_paths_batch_device): debruijn_paths_kernel, launched on the same stream
+// right behind debruijn_kernel with the same grid, works on a window's tables while they are still in its scratch
+// slice (vkey, ekey, ew, the per-vertex edge lists head / enext, slot_of for the source and the sink, the bytes) and
+// on debruijn_kernel's header; debruijn_paths.h has the rule (prune + candidate_haplotypes as a closed form, pruning
+// on) and its serial pieces.  Per window: (a) one pass over the edge table counts every vertex's alive out-edges
+// (`pending`) and threads every alive edge on its target's in-edge list (inhead / innext); the sink's out-edges are
+// left out, a walk ends there.  (b) cnt[] by a reverse peel: the vertices with nothing pending form the first
+// worklist (the sink with cnt 1, dead ends with 0); a thread that resolves a vertex decrements its predecessors, sums
+// a predecessor's count over its out-edges when it brings it to zero (saturating at max_num_paths + 1: all its targets
+// are resolved by then, so the sum does not depend on who computes it), follows the first such predecessor itself and
+// appends the others to the list for the next round.  (c) T = cnt[source]; T > max_num_paths: status "too many".
+// (d) one lane per walk number, striding by the workgroup: a first pass unranks each walk for its length, the lengths
+// are scanned (a chunk per thread, the 256 chunk sums by one thread) into offsets inside the window's haplotype slice,
+// a second pass unranks again and writes the bytes.  Nothing depends on slot numbers but the tables' own links, so
+// the bytes are a pure function of the input.  The paths tables (cnt, pending, inhead, the worklist, innext) are
+// appended to the window's slice.  Every loop is bounded here too: the peel by vertices + 1 rounds, a chain by the
+// vertex count, an edge list by the edge count, the choice of a walk's next edge by the edge count, a walk by the
+// vertex count.  A window whose peel does not resolve every vertex, whose walk runs out of its bound or finds no
+// edge, or whose text passes its slice gets status "host" and is computed there: termination and every store's
+// bound hold for a cyclic or inconsistent table as well.  No workgroup waits for another.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -50,10 +72,12 @@
 #include <string>
 
 #include "debruijn_device.h"
+#include "debruijn_paths.h"
 #include "device_round_trip.h"
 
 static_assert(sizeof(dv_debruijn_device_stats) == 48, "dv_debruijn_device_stats layout");
 static_assert(sizeof(dv_debruijn_window) == 16, "dv_debruijn_window layout");
+static_assert(sizeof(dv_debruijn_paths_stats) == 48, "dv_debruijn_paths_stats layout");
 
 namespace {
 
@@ -84,9 +108,10 @@ struct Params {
   int min_k, max_k, step_k, min_mapq, min_base_quality, max_vertices, max_edges;
 };
 
-// a window's slice: P | ekey | nb | sid | slot_of | vkey | indeg | head | work | ew | eocc | enext
-size_t slice_bytes(size_t n, size_t vcap, size_t ecap) {
-  return dv::align16(8 * (n + 1) + 8 * ecap + 4 * (3 * n + 4 * vcap + 3 * ecap));
+// a window's slice: P | ekey | nb | sid | slot_of | vkey | indeg | head | work | ew | eocc | enext, and for the paths
+// kernel behind them: cnt | pending | inhead | pwork | innext
+size_t slice_bytes(size_t n, size_t vcap, size_t ecap, bool paths = false) {
+  return dv::align16(8 * (n + 1) + 8 * ecap + 4 * (3 * n + 4 * vcap + 3 * ecap) + (paths ? 4 * (4 * vcap + ecap) : 0));
 }
 
 __device__ inline uint32_t ld(const uint32_t* p) {
@@ -385,6 +410,231 @@ __global__ __launch_bounds__(kThreads) void debruijn_kernel(const uint8_t* __res
   }
 }
 
+// ---- pruning and path enumeration
+
+constexpr int32_t kPathsHost = 3;          // a window's status on the device only: the host computes it
+
+struct PathsHeader {       // what a window's workgroup reports
+  int32_t status, k, n_paths, n_bytes;
+};
+
+struct PathsParams {
+  int min_edge_weight, max_num_paths;
+  int lens_per_window;     // entries of a window in the length pool: min(max_num_paths, kDebruijnMaxPaths)
+  int max_hap_bytes;       // bytes of a window's haplotype slice
+};
+
+__device__ inline void st(uint32_t* p, uint32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kThreads) void debruijn_paths_kernel(const uint8_t* __restrict__ bases,
+                                                                  const Item* __restrict__ items,
+                                                                  const Header* __restrict__ headers,
+                                                                  const PathsParams prm, uint8_t* __restrict__ scratch,
+                                                                  uint32_t* __restrict__ lens_pool,
+                                                                  uint8_t* __restrict__ text_pool,
+                                                                  PathsHeader* __restrict__ out) {
+  __shared__ uint32_t s_len[dv::kDebruijnMaxPaths], s_off[dv::kDebruijnMaxPaths], s_sum[kThreads];
+  __shared__ uint32_t s_wcount, s_resolved, s_fail, s_total;
+  const Item it = items[blockIdx.x];
+  const Header hd = headers[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int N = it.n_bytes, R = it.ref_len, k = hd.k;
+  const uint32_t vcap = static_cast<uint32_t>(it.vcap), ecap = static_cast<uint32_t>(it.ecap);
+  const uint32_t n_vertices = static_cast<uint32_t>(hd.n_vertices), n_edges = static_cast<uint32_t>(hd.n_edges);
+  auto report = [&](int32_t status, uint32_t n_paths, uint32_t n_bytes) {
+    if (tid == 0) {
+      out[blockIdx.x] = PathsHeader{status, status == kPathsHost ? 0 : k, static_cast<int32_t>(n_paths),
+                                    static_cast<int32_t>(n_bytes)};
+    }
+  };
+  // the header is the same for every thread, so these returns are the whole workgroup's
+  if (hd.overflow != 0) return report(kPathsHost, 0, 0);
+  if (k == 0) return report(DV_DEBRUIJN_PATHS_NO_GRAPH, 0, 0);
+  if (k < 0 || k >= R || n_vertices > vcap || n_edges > ecap) return report(kPathsHost, 0, 0);
+  // the slice as debruijn_kernel laid it out, then the tables of this kernel
+  const uint8_t* seq = bases + it.bytes_off;
+  uint8_t* sp = scratch + it.scratch_off + 8 * (static_cast<size_t>(N) + 1);
+  const unsigned long long* ekey = reinterpret_cast<const unsigned long long*>(sp);
+  sp += 8 * static_cast<size_t>(ecap);
+  const uint32_t* slot_of = reinterpret_cast<const uint32_t*>(sp) + 2 * static_cast<size_t>(N);
+  const uint32_t* vkey = slot_of + N;
+  const uint32_t* head = vkey + 2 * static_cast<size_t>(vcap);
+  const uint32_t* ew = head + 2 * static_cast<size_t>(vcap);
+  const uint32_t* enext = ew + 2 * static_cast<size_t>(ecap);
+  uint32_t* cnt = const_cast<uint32_t*>(enext) + ecap;
+  uint32_t* pending = cnt + vcap;
+  uint32_t* inhead = pending + vcap;
+  uint32_t* pwork = inhead + vcap;
+  uint32_t* innext = pwork + vcap;
+
+  const uint32_t cap = dv::paths::count_cap(prm.max_num_paths);
+  const uint32_t source = slot_of[0], sink = slot_of[R - k];
+  if (source >= vcap || sink >= vcap) return report(kPathsHost, 0, 0);
+  auto alive = [&](uint32_t e) {
+    const uint32_t w = ld(&ew[e]);
+    return dv::paths::edge_alive(w & ~kRefBit, (w & kRefBit) != 0, prm.min_edge_weight);
+  };
+  for (uint32_t i = tid; i < vcap; i += kThreads) {
+    cnt[i] = i == sink ? 1u : 0u;
+    pending[i] = 0;
+    inhead[i] = kNone;
+  }
+  if (tid == 0) s_wcount = s_resolved = s_fail = s_total = 0;
+  __syncthreads();
+  // ---- (a) alive edges: pending out-edges per vertex, in-edge lists per target
+  for (uint32_t i = tid; i < ecap; i += kThreads) {
+    const unsigned long long key = ld(&ekey[i]);
+    if (key == kNoEdge) continue;
+    const uint32_t from = static_cast<uint32_t>(key >> 32), to = static_cast<uint32_t>(key);
+    if (from == sink || from >= vcap || to >= vcap || !alive(i)) continue;
+    atomicAdd(&pending[from], 1u);
+    innext[i] = atomicExch(&inhead[to], i);
+  }
+  __syncthreads();
+  // ---- (b) cnt[] by a reverse peel from the vertices with nothing pending
+  for (uint32_t i = tid; i < vcap; i += kThreads) {
+    if (ld(&vkey[i]) != kNone && ld(&pending[i]) == 0) {
+      const uint32_t w = atomicAdd(&s_wcount, 1u);
+      if (w < vcap) pwork[w] = i;
+    }
+  }
+  uint32_t begin = 0, resolved = 0;
+  for (uint32_t round = 0; round <= n_vertices; ++round) {
+    const uint32_t end = min(agreed(&s_wcount), vcap);
+    if (begin == end) break;
+    for (uint32_t w = begin + tid; w < end; w += kThreads) {
+      uint32_t v = pwork[w];
+      for (uint32_t steps = 0; v != kNone && steps <= n_vertices; ++steps) {
+        ++resolved;
+        uint32_t next = kNone;
+        uint32_t e = ld(&inhead[v]);
+        for (uint32_t seen = 0; e != kNone && e < ecap && seen <= n_edges; ++seen) {
+          const uint32_t u = static_cast<uint32_t>(ld(&ekey[e]) >> 32);
+          if (atomicSub(&pending[u], 1u) == 1u) {
+            // every target of u is resolved, and its count stored before its resolver came here
+            __threadfence();
+            uint32_t sum = 0;
+            uint32_t f = ld(&head[u]);
+            for (uint32_t seen2 = 0; f != kNone && f < ecap && seen2 <= n_edges; ++seen2) {
+              const uint32_t to = static_cast<uint32_t>(ld(&ekey[f]));
+              if (to < vcap && alive(f)) sum = dv::paths::saturating_add(sum, ld(&cnt[to]), cap);
+              f = ld(&enext[f]);
+            }
+            st(&cnt[u], sum);
+            __threadfence();
+            if (next == kNone) {
+              next = u;
+            } else {
+              const uint32_t w2 = atomicAdd(&s_wcount, 1u);
+              if (w2 < vcap) pwork[w2] = u;
+            }
+          }
+          e = ld(&innext[e]);
+        }
+        v = next;
+      }
+    }
+    begin = end;
+  }
+  atomicAdd(&s_resolved, resolved);
+  if (agreed(&s_resolved) != n_vertices) return report(kPathsHost, 0, 0);
+  // ---- (c) the number of walks
+  const uint32_t T = ld(&cnt[source]);
+  if (T >= cap) return report(DV_DEBRUIJN_PATHS_TOO_MANY, 0, 0);
+  if (T == 0 || T > static_cast<uint32_t>(prm.lens_per_window) || T > static_cast<uint32_t>(dv::kDebruijnMaxPaths)) {
+    return report(kPathsHost, 0, 0);
+  }
+  // ---- (d) walk number r, unranked: its length; with dst also its bytes, never past dst[limit).  0: no such walk.
+  auto walk = [&](uint32_t r, uint8_t* dst, uint32_t limit) -> uint32_t {
+    uint32_t v = source, len = static_cast<uint32_t>(k);
+    if (dst) {
+      if (len > limit) return 0;
+      for (uint32_t j = 0; j < len; ++j) dst[j] = seq[j];
+    }
+    for (uint32_t steps = 0; v != sink; ++steps) {
+      if (steps >= n_vertices) return 0;
+      int after = dv::paths::kNoByte, byte = 0;
+      uint32_t chosen = kNone;
+      for (uint32_t rounds = 0; rounds <= n_edges; ++rounds) {
+        int best = dv::paths::kPastBytes;
+        uint32_t best_to = kNone;
+        uint32_t e = ld(&head[v]);
+        for (uint32_t seen = 0; e != kNone && e < ecap && seen <= n_edges; ++seen) {
+          const uint32_t to = static_cast<uint32_t>(ld(&ekey[e]));
+          if (to < vcap && alive(e)) {
+            const uint32_t at = ld(&vkey[to]) + static_cast<uint32_t>(k) - 1u;
+            const int b = at < static_cast<uint32_t>(N) ? seq[at] : 0;
+            if (dv::paths::next_in_order(after, b, best)) {
+              best = b;
+              best_to = to;
+            }
+          }
+          e = ld(&enext[e]);
+        }
+        if (best_to == kNone) break;                     // out of edges
+        if (dv::paths::take_edge(&r, ld(&cnt[best_to]))) {
+          chosen = best_to;
+          byte = best;
+          break;
+        }
+        after = best;
+      }
+      if (chosen == kNone) return 0;
+      if (dst) {
+        if (len >= limit) return 0;
+        dst[len] = static_cast<uint8_t>(byte);
+      }
+      ++len;
+      v = chosen;
+    }
+    return len;
+  };
+  for (uint32_t r = tid; r < T; r += kThreads) {
+    const uint32_t len = walk(r, nullptr, 0);
+    if (len == 0) s_fail = 1;
+    s_len[r] = len;
+  }
+  __syncthreads();
+  // offsets: a chunk of walk numbers per thread, the chunk sums scanned by one thread
+  {
+    const uint32_t chunk = (T + kThreads - 1) / kThreads;
+    const uint32_t lo = min(tid * chunk, T), hi = min(lo + chunk, T);
+    uint32_t sum = 0;
+    for (uint32_t r = lo; r < hi; ++r) sum += s_len[r];    // <= 1024 walks of at most 8192 + k bytes each
+    s_sum[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t carry = 0;
+      for (int t = 0; t < kThreads; ++t) {
+        const uint32_t own = s_sum[t];
+        s_sum[t] = carry;
+        carry += own;
+      }
+      s_total = carry;
+    }
+    __syncthreads();
+    uint32_t at = s_sum[tid];
+    for (uint32_t r = lo; r < hi; ++r) {
+      s_off[r] = at;
+      at += s_len[r];
+    }
+  }
+  if (agreed(&s_fail) != 0) return report(kPathsHost, 0, 0);
+  const uint32_t total = agreed(&s_total);
+  if (total > static_cast<uint32_t>(prm.max_hap_bytes)) return report(kPathsHost, 0, 0);
+  uint8_t* text = text_pool + static_cast<size_t>(blockIdx.x) * static_cast<size_t>(prm.max_hap_bytes);
+  uint32_t* lens = lens_pool + static_cast<size_t>(blockIdx.x) * static_cast<size_t>(prm.lens_per_window);
+  for (uint32_t r = tid; r < T; r += kThreads) {
+    const uint32_t len = s_len[r];
+    if (walk(r, text + s_off[r], len) != len) s_fail = 1;
+    lens[r] = len;
+  }
+  if (agreed(&s_fail) != 0) return report(kPathsHost, 0, 0);
+  report(DV_DEBRUIJN_PATHS_OK, T, total);
+}
+
 uint32_t pow2_at_least(uint32_t x) {
   uint32_t p = 64;
   while (p < x) p <<= 1;
@@ -441,6 +691,108 @@ void to_compact(const dv::AssemblyWindow& w, const Header& h, const uint32_t* vk
   }
 }
 
+// The windows of a call as launch items.  A window over the limits known before the launch is left to the host.
+struct Plan {
+  std::vector<Item> items;
+  std::vector<size_t> item_window;      // an item's window
+  std::vector<size_t> order;            // the items in launch order: the heaviest first, early workgroups start first
+  std::vector<size_t> on_host;          // the windows without an item
+  int64_t n_bytes = 0, n_entries = 0, scratch_bytes = 0, vout = 0, eout = 0;
+};
+
+// pools: room for the winning graphs in the output pools; paths: the paths kernel's tables in every slice
+Plan plan_windows(const std::vector<dv::AssemblyWindow>& windows, bool pools, bool paths) {
+  constexpr int64_t kScratchBudget = int64_t{2} << 30;      // bytes of table scratch per call
+  // the paths kernel's haplotype slices are downloaded whole: 1 GiB of them per call
+  const size_t max_items = paths ? (size_t{1} << 30) / static_cast<size_t>(dv::kDebruijnMaxHapBytes) : windows.size();
+  Plan p;
+  for (size_t wi = 0; wi < windows.size(); ++wi) {
+    const dv::AssemblyWindow& w = windows[wi];
+    int64_t n = static_cast<int64_t>(w.ref.size());
+    for (const dv::AssemblyRead& r : w.reads) n += static_cast<int64_t>(r.bases.size());
+    if (n > dv::kDebruijnMaxBases || p.items.size() >= max_items) {
+      p.on_host.push_back(wi);
+      continue;
+    }
+    Item it;
+    it.n_bytes = static_cast<int32_t>(n);
+    it.ref_len = static_cast<int32_t>(w.ref.size());
+    it.n_seqs = static_cast<int32_t>(w.reads.size()) + 1;
+    it.vcap = static_cast<int32_t>(std::min(pow2_at_least(2u * dv::kDebruijnMaxVertices), pow2_at_least(it.n_bytes)));
+    it.ecap = static_cast<int32_t>(std::min(pow2_at_least(2u * dv::kDebruijnMaxEdges), pow2_at_least(it.n_bytes)));
+    it.vmax = pools ? std::min(dv::kDebruijnMaxVertices, it.n_bytes) : 0;
+    it.emax = pools ? std::min(dv::kDebruijnMaxEdges, it.n_bytes) : 0;
+    const int64_t slice = static_cast<int64_t>(slice_bytes(static_cast<size_t>(n), it.vcap, it.ecap, paths));
+    if (p.scratch_bytes + slice > kScratchBudget || p.n_bytes + n >= (int64_t{1} << 30)) {
+      p.on_host.push_back(wi);
+      continue;
+    }
+    it.bytes_off = p.n_bytes;
+    it.scratch_off = p.scratch_bytes;
+    it.vout_off = p.vout;
+    it.eout_off = p.eout;
+    it.seq_table = static_cast<int32_t>(p.n_entries);
+    p.items.push_back(it);
+    p.item_window.push_back(wi);
+    p.n_bytes += n;
+    p.n_entries += it.n_seqs + 1;
+    p.scratch_bytes += slice;
+    p.vout += it.vmax;
+    p.eout += it.emax;
+  }
+  p.order.resize(p.items.size());
+  for (size_t x = 0; x < p.order.size(); ++x) p.order[x] = x;
+  std::stable_sort(p.order.begin(), p.order.end(),
+                   [&](size_t a, size_t b) { return p.items[a].n_bytes > p.items[b].n_bytes; });
+  return p;
+}
+
+// the upload image of a plan: items | offsets | mapq | bases | quals
+struct UploadImage {
+  size_t items, off, mapq, bases, quals;
+  explicit UploadImage(const Plan& p, dv::Layout* up)
+      : items(up->add(p.items.size() * sizeof(Item))),
+        off(up->add(static_cast<size_t>(p.n_entries) * sizeof(int32_t))),
+        mapq(up->add(static_cast<size_t>(p.n_entries))),
+        bases(up->add(static_cast<size_t>(p.n_bytes))),
+        quals(up->add(static_cast<size_t>(p.n_bytes))) {}
+};
+
+void stage_windows(const std::vector<dv::AssemblyWindow>& windows, const Plan& p, const UploadImage& image,
+                   const dv::RoundTrip& rt) {
+  Item* up_items = rt.host_up<Item>(image.items);
+  int32_t* up_off = rt.host_up<int32_t>(image.off);
+  uint8_t* up_mapq = rt.host_up<uint8_t>(image.mapq);
+  for (size_t x = 0; x < p.items.size(); ++x) {
+    const Item& it = p.items[p.order[x]];
+    up_items[x] = it;
+    const dv::AssemblyWindow& w = windows[p.item_window[p.order[x]]];
+    uint8_t* b = rt.host_up<uint8_t>(image.bases) + it.bytes_off;
+    uint8_t* q = rt.host_up<uint8_t>(image.quals) + it.bytes_off;
+    int32_t* offs = up_off + it.seq_table;
+    uint8_t* mq = up_mapq + it.seq_table;
+    std::memcpy(b, w.ref.data(), w.ref.size());
+    std::memset(q, 0, w.ref.size());
+    int32_t at = static_cast<int32_t>(w.ref.size());
+    offs[0] = 0;
+    offs[1] = at;
+    mq[0] = 0;
+    for (size_t r = 0; r < w.reads.size(); ++r) {
+      const dv::AssemblyRead& read = w.reads[r];
+      const size_t len = read.bases.size();
+      for (size_t i = 0; i < len; ++i) {                 // the contract's upper-casing
+        const char c = read.bases[i];
+        b[at + i] = static_cast<uint8_t>(c >= 'a' && c <= 'z' ? c - 'a' + 'A' : c);
+      }
+      if (len) std::memcpy(q + at, read.quals, len);
+      at += static_cast<int32_t>(len);
+      offs[r + 2] = at;
+      mq[r + 1] = static_cast<uint8_t>(std::min(std::max(read.mapq, 0), 255));
+    }
+    mq[w.reads.size() + 1] = 0;
+  }
+}
+
 }  // namespace
 
 namespace dv {
@@ -463,111 +815,34 @@ void compact_on_host(const std::vector<AssemblyWindow>& windows, const DeBruijnO
 int compact_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijnOptions& options, void* stream_in,
                       std::vector<CompactGraph>* out, AssemblyStats* stats) {
   out->assign(windows.size(), CompactGraph());
-  constexpr int64_t kScratchBudget = int64_t{2} << 30;      // bytes of table scratch per call
-  std::vector<Item> items;
-  std::vector<size_t> item_window;
-  std::vector<size_t> on_host;
-  int64_t n_bytes = 0, n_entries = 0, scratch_bytes = 0, vout = 0, eout = 0;
-  for (size_t wi = 0; wi < windows.size(); ++wi) {
-    const AssemblyWindow& w = windows[wi];
-    int64_t n = static_cast<int64_t>(w.ref.size());
-    for (const AssemblyRead& r : w.reads) n += static_cast<int64_t>(r.bases.size());
-    if (n > kDebruijnMaxBases) {
-      on_host.push_back(wi);
-      continue;
-    }
-    Item it;
-    it.n_bytes = static_cast<int32_t>(n);
-    it.ref_len = static_cast<int32_t>(w.ref.size());
-    it.n_seqs = static_cast<int32_t>(w.reads.size()) + 1;
-    it.vcap = static_cast<int32_t>(std::min(pow2_at_least(2u * kDebruijnMaxVertices), pow2_at_least(it.n_bytes)));
-    it.ecap = static_cast<int32_t>(std::min(pow2_at_least(2u * kDebruijnMaxEdges), pow2_at_least(it.n_bytes)));
-    it.vmax = std::min(kDebruijnMaxVertices, it.n_bytes);
-    it.emax = std::min(kDebruijnMaxEdges, it.n_bytes);
-    const int64_t slice = static_cast<int64_t>(slice_bytes(static_cast<size_t>(n), it.vcap, it.ecap));
-    if (scratch_bytes + slice > kScratchBudget || n_bytes + n >= (int64_t{1} << 30)) {
-      on_host.push_back(wi);
-      continue;
-    }
-    it.bytes_off = n_bytes;
-    it.scratch_off = scratch_bytes;
-    it.vout_off = vout;
-    it.eout_off = eout;
-    it.seq_table = static_cast<int32_t>(n_entries);
-    items.push_back(it);
-    item_window.push_back(wi);
-    n_bytes += n;
-    n_entries += it.n_seqs + 1;
-    scratch_bytes += slice;
-    vout += it.vmax;
-    eout += it.emax;
-  }
+  Plan plan = plan_windows(windows, /*pools=*/true, /*paths=*/false);
   if (stats) {
     stats->windows += static_cast<int64_t>(windows.size());
-    stats->windows_on_host += static_cast<int64_t>(on_host.size());
+    stats->windows_on_host += static_cast<int64_t>(plan.on_host.size());
   }
-  if (!items.empty()) {
-    // the heaviest windows first: early workgroups start first
-    std::vector<size_t> order(items.size());
-    for (size_t x = 0; x < order.size(); ++x) order[x] = x;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return items[a].n_bytes > items[b].n_bytes; });
-    const size_t n_items = items.size();
+  if (!plan.items.empty()) {
+    const size_t n_items = plan.items.size();
     Layout up, down;
-    // upload image: items | offsets | mapq | bases | quals
-    const size_t o_items = up.add(n_items * sizeof(Item));
-    const size_t o_off = up.add(static_cast<size_t>(n_entries) * sizeof(int32_t));
-    const size_t o_mapq = up.add(static_cast<size_t>(n_entries));
-    const size_t o_bases = up.add(static_cast<size_t>(n_bytes));
-    const size_t o_quals = up.add(static_cast<size_t>(n_bytes));
+    const UploadImage image(plan, &up);
     // download image: headers | vertex keys | edges
     const size_t o_headers = down.add(n_items * sizeof(Header));
-    const size_t o_vout = down.add(static_cast<size_t>(vout) * sizeof(uint32_t));
-    const size_t o_eout = down.add_last(static_cast<size_t>(eout) * sizeof(uint4));
+    const size_t o_vout = down.add(static_cast<size_t>(plan.vout) * sizeof(uint32_t));
+    const size_t o_eout = down.add_last(static_cast<size_t>(plan.eout) * sizeof(uint4));
     static thread_local RoundTrip rt;     // its scratch: the windows' tables
     if (int rc = rt.begin("de Bruijn assembly: no HIP device (the device route has no CPU fallback)", stream_in,
-                          up.bytes(), down.bytes(), static_cast<size_t>(scratch_bytes))) {
+                          up.bytes(), down.bytes(), static_cast<size_t>(plan.scratch_bytes))) {
       return rc;
     }
-    Item* up_items = rt.host_up<Item>(o_items);
-    int32_t* up_off = rt.host_up<int32_t>(o_off);
-    uint8_t* up_mapq = rt.host_up<uint8_t>(o_mapq);
-    for (size_t x = 0; x < n_items; ++x) {
-      const Item& it = items[order[x]];
-      up_items[x] = it;
-      const AssemblyWindow& w = windows[item_window[order[x]]];
-      uint8_t* b = rt.host_up<uint8_t>(o_bases) + it.bytes_off;
-      uint8_t* q = rt.host_up<uint8_t>(o_quals) + it.bytes_off;
-      int32_t* offs = up_off + it.seq_table;
-      uint8_t* mq = up_mapq + it.seq_table;
-      std::memcpy(b, w.ref.data(), w.ref.size());
-      std::memset(q, 0, w.ref.size());
-      int32_t at = static_cast<int32_t>(w.ref.size());
-      offs[0] = 0;
-      offs[1] = at;
-      mq[0] = 0;
-      for (size_t r = 0; r < w.reads.size(); ++r) {
-        const AssemblyRead& read = w.reads[r];
-        const size_t len = read.bases.size();
-        for (size_t i = 0; i < len; ++i) {                 // the contract's upper-casing
-          const char c = read.bases[i];
-          b[at + i] = static_cast<uint8_t>(c >= 'a' && c <= 'z' ? c - 'a' + 'A' : c);
-        }
-        if (len) std::memcpy(q + at, read.quals, len);
-        at += static_cast<int32_t>(len);
-        offs[r + 2] = at;
-        mq[r + 1] = static_cast<uint8_t>(std::min(std::max(read.mapq, 0), 255));
-      }
-      mq[w.reads.size() + 1] = 0;
-    }
+    stage_windows(windows, plan, image, rt);
     if (int rc = rt.upload(up.bytes())) return rc;
     {
       ProfileScope prof(kProfOther, rt.stream());
       const Params prm{options.min_k, options.max_k, options.step_k, options.min_mapq, options.min_base_quality,
                        kDebruijnMaxVertices, kDebruijnMaxEdges};
       hipLaunchKernelGGL(debruijn_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, rt.stream(),
-                         rt.dev_up<const uint8_t>(o_bases), rt.dev_up<const uint8_t>(o_quals),
-                         rt.dev_up<const int32_t>(o_off), rt.dev_up<const uint8_t>(o_mapq),
-                         rt.dev_up<const Item>(o_items), prm, static_cast<uint8_t*>(rt.d_scratch.ptr),
+                         rt.dev_up<const uint8_t>(image.bases), rt.dev_up<const uint8_t>(image.quals),
+                         rt.dev_up<const int32_t>(image.off), rt.dev_up<const uint8_t>(image.mapq),
+                         rt.dev_up<const Item>(image.items), prm, static_cast<uint8_t*>(rt.d_scratch.ptr),
                          rt.dev_down<uint32_t>(o_vout), rt.dev_down<uint4>(o_eout), rt.dev_down<Header>(o_headers));
       DV_HIP_CHECK(hipGetLastError());
     }
@@ -577,12 +852,12 @@ int compact_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijn
     const uint32_t* vkeys = rt.host_down<uint32_t>(o_vout);
     const uint4* edges = rt.host_down<uint4>(o_eout);
     for (size_t x = 0; x < n_items; ++x) {
-      const Item& it = items[order[x]];
-      const size_t wi = item_window[order[x]];
+      const Item& it = plan.items[plan.order[x]];
+      const size_t wi = plan.item_window[plan.order[x]];
       const Header& h = headers[x];
       if (stats) stats->kmers += static_cast<int64_t>(h.kmers);
       if (h.overflow || h.n_vertices < 0 || h.n_vertices > it.vmax || h.n_edges < 0 || h.n_edges > it.emax) {
-        on_host.push_back(wi);
+        plan.on_host.push_back(wi);
         if (stats) stats->windows_on_host += 1;
         continue;
       }
@@ -590,9 +865,137 @@ int compact_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijn
       to_compact(windows[wi], h, vkeys + it.vout_off, edges + it.eout_off, &(*out)[wi]);
     }
   }
-  for (size_t wi : on_host) {
+  for (size_t wi : plan.on_host) {
     DeBruijnGraph::build_compact(windows[wi].ref, windows[wi].reads, options, &(*out)[wi]);
     if (stats) stats->k_tries += (*out)[wi].k_tries;
+  }
+  return DV_OK;
+}
+
+PathsStats& last_paths_stats() {
+  static thread_local PathsStats stats;
+  return stats;
+}
+
+bool device_paths_enabled() { return env_switch("DV_REALIGN_DEVICE_PATHS", false); }
+
+void paths_of_window(const AssemblyWindow& window, const DeBruijnOptions& options, WindowPaths* out) {
+  *out = WindowPaths();
+  const std::unique_ptr<DeBruijnGraph> graph = DeBruijnGraph::build(window.ref, window.reads, options);
+  if (!graph) return;
+  out->k = graph->kmer_size();
+  out->haplotypes = graph->candidate_haplotypes();
+  out->status = out->haplotypes.empty() ? DV_DEBRUIJN_PATHS_TOO_MANY : DV_DEBRUIJN_PATHS_OK;
+}
+
+int paths_on_device(const std::vector<AssemblyWindow>& windows, const DeBruijnOptions& options, void* stream_in,
+                    bool compute_on_host, std::vector<WindowPaths>* out, PathsStats* stats, AssemblyStats* assembly) {
+  out->assign(windows.size(), WindowPaths());
+  // what the kernel covers: the closed form needs pruning, and a window's lengths have kDebruijnMaxPaths places
+  const bool covered = !options.disable_graph_pruning && options.max_num_paths <= kDebruijnMaxPaths;
+  Plan plan;
+  if (covered) {
+    plan = plan_windows(windows, /*pools=*/false, /*paths=*/true);
+  } else {
+    for (size_t wi = 0; wi < windows.size(); ++wi) plan.on_host.push_back(wi);
+  }
+  if (stats) stats->windows += static_cast<int64_t>(windows.size());
+  if (assembly) {
+    assembly->windows += static_cast<int64_t>(windows.size());
+    assembly->windows_on_host += static_cast<int64_t>(plan.on_host.size());
+  }
+  if (!plan.items.empty()) {
+    const size_t n_items = plan.items.size();
+    const size_t lens_per_window = static_cast<size_t>(std::max(1, std::min(options.max_num_paths, kDebruijnMaxPaths)));
+    Layout up, down;
+    const UploadImage image(plan, &up);
+    // download image: the graph kernel's headers | this kernel's | haplotype lengths | haplotype text slices
+    const size_t o_headers = down.add(n_items * sizeof(Header));
+    const size_t o_paths = down.add(n_items * sizeof(PathsHeader));
+    const size_t o_lens = down.add(n_items * lens_per_window * sizeof(uint32_t));
+    const size_t o_text = down.add_last(n_items * static_cast<size_t>(kDebruijnMaxHapBytes));
+    static thread_local RoundTrip rt;     // its scratch: the windows' tables, both kernels'
+    if (int rc = rt.begin("de Bruijn paths: no HIP device (the device route has no CPU fallback)", stream_in, up.bytes(),
+                          down.bytes(), static_cast<size_t>(plan.scratch_bytes))) {
+      return rc;
+    }
+    stage_windows(windows, plan, image, rt);
+    if (int rc = rt.upload(up.bytes())) return rc;
+    {
+      ProfileScope prof(kProfOther, rt.stream());
+      const Params prm{options.min_k, options.max_k, options.step_k, options.min_mapq, options.min_base_quality,
+                       kDebruijnMaxVertices, kDebruijnMaxEdges};
+      // no room in the pools (vmax = emax = 0): the graph stays in the slices, the header still counts it
+      hipLaunchKernelGGL(debruijn_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, rt.stream(),
+                         rt.dev_up<const uint8_t>(image.bases), rt.dev_up<const uint8_t>(image.quals),
+                         rt.dev_up<const int32_t>(image.off), rt.dev_up<const uint8_t>(image.mapq),
+                         rt.dev_up<const Item>(image.items), prm, static_cast<uint8_t*>(rt.d_scratch.ptr),
+                         rt.dev_down<uint32_t>(o_lens), rt.dev_down<uint4>(o_text), rt.dev_down<Header>(o_headers));
+      DV_HIP_CHECK(hipGetLastError());
+      const PathsParams pp{options.min_edge_weight, options.max_num_paths, static_cast<int>(lens_per_window),
+                           kDebruijnMaxHapBytes};
+      hipLaunchKernelGGL(debruijn_paths_kernel, dim3(static_cast<unsigned>(n_items)), dim3(kThreads), 0, rt.stream(),
+                         rt.dev_up<const uint8_t>(image.bases), rt.dev_up<const Item>(image.items),
+                         rt.dev_down<const Header>(o_headers), pp, static_cast<uint8_t*>(rt.d_scratch.ptr),
+                         rt.dev_down<uint32_t>(o_lens), rt.dev_down<uint8_t>(o_text), rt.dev_down<PathsHeader>(o_paths));
+      DV_HIP_CHECK(hipGetLastError());
+    }
+    if (int rc = rt.finish(down.bytes())) return rc;
+    if (stats) {
+      stats->launches += 2;
+      stats->bytes_down += static_cast<int64_t>(down.bytes());
+    }
+    if (assembly) assembly->launches += 1;
+    const Header* headers = rt.host_down<Header>(o_headers);
+    const PathsHeader* paths = rt.host_down<PathsHeader>(o_paths);
+    for (size_t x = 0; x < n_items; ++x) {
+      const size_t wi = plan.item_window[plan.order[x]];
+      const Header& h = headers[x];
+      const PathsHeader& ph = paths[x];
+      WindowPaths& w = (*out)[wi];
+      if (assembly) assembly->kmers += static_cast<int64_t>(h.kmers);
+      // nothing is sized or indexed by a value the device returned without a check
+      bool ok = !h.overflow && ph.status >= DV_DEBRUIJN_PATHS_OK && ph.status <= DV_DEBRUIJN_PATHS_TOO_MANY && ph.k == h.k;
+      if (ok && ph.status == DV_DEBRUIJN_PATHS_OK) {
+        ok = ph.n_paths >= 1 && static_cast<size_t>(ph.n_paths) <= lens_per_window && ph.n_bytes >= 0 &&
+             ph.n_bytes <= kDebruijnMaxHapBytes && ph.k > 0;
+        const uint32_t* lens = rt.host_down<uint32_t>(o_lens) + x * lens_per_window;
+        int64_t sum = 0;
+        for (int32_t r = 0; ok && r < ph.n_paths; ++r) sum += lens[r];
+        ok = ok && sum == ph.n_bytes;
+        if (ok) {
+          const char* text = rt.host_down<char>(o_text) + x * static_cast<size_t>(kDebruijnMaxHapBytes);
+          w.haplotypes.reserve(static_cast<size_t>(ph.n_paths));
+          for (int32_t r = 0; r < ph.n_paths; ++r) {
+            w.haplotypes.emplace_back(text, lens[r]);
+            text += lens[r];
+          }
+        }
+      } else if (ok) {
+        ok = (ph.status == DV_DEBRUIJN_PATHS_NO_GRAPH) == (ph.k == 0);
+      }
+      if (!ok) {
+        w = WindowPaths();
+        plan.on_host.push_back(wi);
+        if (h.overflow && assembly) assembly->windows_on_host += 1;
+        continue;
+      }
+      w.k = ph.k;
+      w.status = ph.status;
+      if (assembly) assembly->k_tries += h.k_tries;
+      if (stats) {
+        stats->paths += static_cast<int64_t>(w.haplotypes.size());
+        stats->hap_bytes += ph.status == DV_DEBRUIJN_PATHS_OK ? ph.n_bytes : 0;
+      }
+    }
+  }
+  if (stats) stats->windows_on_host += static_cast<int64_t>(plan.on_host.size());
+  for (size_t wi : plan.on_host) {
+    if (compute_on_host) {
+      paths_of_window(windows[wi], options, &(*out)[wi]);
+    } else {
+      (*out)[wi].on_host = true;
+    }
   }
   return DV_OK;
 }
@@ -619,9 +1022,10 @@ dv::DeBruijnOptions options_of(const dv_debruijn_options& o) {
   return opt;
 }
 
+template <class Result, class Arrays>
 int parse(const char* who, int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
           const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows, const dv_debruijn_options* o,
-          dv_debruijn_compact_result** out, dv_debruijn_compact* arrays, Batch* b) {
+          Result** out, Arrays* arrays, Batch* b) {
   const std::string name(who);
   if (out) *out = nullptr;
   if (!out || !arrays || !o || n_seqs < 0 || n_windows < 0 || (n_seqs > 0 && (!seq_off || !mapq)) ||
@@ -704,6 +1108,37 @@ void publish(const std::vector<dv::CompactGraph>& graphs, dv_debruijn_compact_re
 
 }  // namespace
 
+struct dv_debruijn_paths_result {
+  std::vector<int32_t> k, status, hap_first;
+  std::vector<int64_t> hap_off;
+  std::string hap_text;
+};
+
+namespace {
+
+void publish_paths(const std::vector<dv::WindowPaths>& paths, dv_debruijn_paths_result** out, dv_debruijn_paths* arrays) {
+  auto res = std::make_unique<dv_debruijn_paths_result>();
+  res->hap_first.assign(1, 0);
+  res->hap_off.assign(1, 0);
+  for (const dv::WindowPaths& w : paths) {
+    res->k.push_back(w.k);
+    res->status.push_back(w.status);
+    for (const std::string& h : w.haplotypes) {
+      res->hap_text += h;
+      res->hap_off.push_back(static_cast<int64_t>(res->hap_text.size()));
+    }
+    res->hap_first.push_back(static_cast<int32_t>(res->hap_off.size() - 1));
+  }
+  arrays->k = res->k.data();
+  arrays->status = res->status.data();
+  arrays->hap_first = res->hap_first.data();
+  arrays->hap_off = res->hap_off.data();
+  arrays->hap_text = res->hap_text.data();
+  *out = res.release();
+}
+
+}  // namespace
+
 extern "C" {
 
 int dv_debruijn_compact_batch(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
@@ -747,6 +1182,60 @@ int dv_debruijn_compact_batch_device(int32_t n_seqs, const char* bases, const ui
 }
 
 void dv_debruijn_compact_free(dv_debruijn_compact_result* r) { delete r; }
+
+int dv_debruijn_paths_batch(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                            const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                            const dv_debruijn_options* options, dv_debruijn_paths_result** out,
+                            dv_debruijn_paths* arrays) {
+  return dv::guarded("dv_debruijn_paths_batch", [&]() -> int {
+    Batch b;
+    if (int rc = parse("dv_debruijn_paths_batch", n_seqs, bases, quals, seq_off, mapq, n_windows, windows, options, out,
+                       arrays, &b)) {
+      return rc;
+    }
+    std::vector<dv::WindowPaths> paths(b.windows.size());
+    for (size_t w = 0; w < paths.size(); ++w) dv::paths_of_window(b.windows[w], b.options, &paths[w]);
+    publish_paths(paths, out, arrays);
+    return DV_OK;
+  });
+}
+
+int dv_debruijn_paths_batch_device(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                                   const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                                   const dv_debruijn_options* options, void* stream, dv_debruijn_paths_result** out,
+                                   dv_debruijn_paths* arrays) {
+  return dv::guarded("dv_debruijn_paths_batch_device", [&]() -> int {
+    dv::last_paths_stats() = dv::PathsStats();
+    Batch b;
+    if (int rc = parse("dv_debruijn_paths_batch_device", n_seqs, bases, quals, seq_off, mapq, n_windows, windows,
+                       options, out, arrays, &b)) {
+      return rc;
+    }
+    // no look for a device here: a call without device work (no windows, or none the kernel covers) needs none, and
+    // the round trip reports DV_ERR_NO_DEVICE when there is some
+    std::vector<dv::WindowPaths> paths;
+    if (int rc = dv::paths_on_device(b.windows, b.options, stream, /*compute_on_host=*/true, &paths,
+                                     &dv::last_paths_stats(), nullptr)) {
+      return rc;
+    }
+    publish_paths(paths, out, arrays);
+    return DV_OK;
+  });
+}
+
+void dv_debruijn_paths_free(dv_debruijn_paths_result* r) { delete r; }
+
+int dv_debruijn_paths_last_stats(dv_debruijn_paths_stats* out) {
+  if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_debruijn_paths_last_stats: null");
+  const dv::PathsStats& s = dv::last_paths_stats();
+  out->windows = s.windows;
+  out->windows_on_host = s.windows_on_host;
+  out->paths = s.paths;
+  out->hap_bytes = s.hap_bytes;
+  out->launches = s.launches;
+  out->bytes_down = s.bytes_down;
+  return DV_OK;
+}
 
 int dv_debruijn_device_last_stats(dv_debruijn_device_stats* out) {
   if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_debruijn_device_last_stats: null");

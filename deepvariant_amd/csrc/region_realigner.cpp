@@ -24,6 +24,8 @@
 // With DV_REALIGN_DEVICE_ASSEMBLY=1 the device route's phase 1 becomes 1a, the batch's window list; 1b, once, the
 // graph of every window in one kernel launch (debruijn.hip), choice of k and cycle test included; 1c, one task per
 // window: DeBruijnGraph::from_compact (which prunes), candidate_haplotypes and the comparison with the reference.
+// With DV_REALIGN_DEVICE_PATHS=1 on top of that, 1b also prunes and enumerates on the device (its paths kernel) and 1c
+// is the comparison alone; a window the device hands back is built by its task as the host route builds it.
 // The read assignment and the result arrays are the same code for both routes.
 //
 // Tasks are independent (each builds its own graph / aligner; the aligner's scratch buffers are
@@ -218,6 +220,7 @@ int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_region
     dv::last_traceback_stats() = dv::TracebackStats();
     dv::last_fast_pass_stats() = dv::FastPassStats();
     dv::last_assembly_stats() = dv::AssemblyStats();
+    dv::last_paths_stats() = dv::PathsStats();
     const DeviceRoute device{stream, stats};
     return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
   } catch (const std::bad_alloc&) {
@@ -313,6 +316,28 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     parallel_tasks(longest_first(cost), n_threads, [&](int t) {
       const dv::AssemblyWindow aw = assembly_window(windows[t]);
       keep_haplotypes(windows[t], dv::DeBruijnGraph::build(aw.ref, aw.reads, dbg).get(), aw.ref);
+    });
+  } else if (dv::device_paths_enabled()) {
+    // 1a: the batch's window list
+    const std::vector<int> by_cost = longest_first(cost);
+    std::vector<dv::AssemblyWindow> assembly(windows.size());
+    parallel_tasks(by_cost, n_threads, [&](int t) { assembly[t] = assembly_window(windows[t]); });
+    // 1b: graphs, pruning and haplotypes of all windows of all regions in one device call
+    std::vector<dv::WindowPaths> paths;
+    if (int rc = dv::paths_on_device(assembly, dbg, device->stream, /*compute_on_host=*/false, &paths,
+                                     &dv::last_paths_stats(), &dv::last_assembly_stats())) {
+      return rc;
+    }
+    // 1c: the comparison with the reference; a window the device handed back is built here, as the host route does
+    parallel_tasks(by_cost, n_threads, [&](int t) {
+      const dv::AssemblyWindow& aw = assembly[t];
+      if (paths[t].on_host) {
+        keep_haplotypes(windows[t], dv::DeBruijnGraph::build(aw.ref, aw.reads, dbg).get(), aw.ref);
+        return;
+      }
+      std::vector<std::string>& haps = paths[t].haplotypes;
+      if (haps.empty() || (haps.size() == 1 && haps[0] == aw.ref)) return;
+      windows[t].haplotypes = std::move(haps);
     });
   } else {
     // 1a: the batch's window list

@@ -4,7 +4,9 @@ the C ABI: build(ref, reads, options) -> DeBruijnGraph or None; .kmer_size,
 
 compact_batch / compact_batch_device return the graphs of many windows before pruning as integer arrays (the "compact
 form" of include/dvhip.h) -- the host's own constructor, or one kernel launch of csrc/debruijn.hip -- and from_compact
-turns one back into the object build returns."""
+turns one back into the object build returns.  paths_batch / paths_batch_device return the windows' candidate
+haplotypes themselves: build + candidate_haplotypes per window on the host, or the graph launch and the paths launch
+of csrc/debruijn.hip."""
 from __future__ import annotations
 
 import ctypes as C
@@ -79,8 +81,9 @@ def _native_options(options: DeBruijnGraphOptions) -> '_lib.DvDebruijnOptions':
                                 int(bool(options.disable_graph_pruning)))
 
 
-def _compact_call(windows, options, device, stream=0):
-  """windows: (ref, reads) pairs.  One sequence table: per window its reference, then its reads."""
+def _sequence_table(windows):
+  """windows: (ref, reads) pairs.  One sequence table: per window its reference, then its reads.  -> the leading
+  arguments of the batch entry points (n_seqs .. windows) and the arrays they point into."""
   pieces, quals, lengths, mapq, descs = [], [], [], [], []
   for ref, reads in windows:
     first = len(lengths)
@@ -103,16 +106,21 @@ def _compact_call(windows, options, device, stream=0):
   np.cumsum(lengths, out=seq_off[1:])
   mapq = np.array(mapq, np.uint8)
   table = (_lib.DvDebruijnWindow * max(1, len(descs)))(*descs)
+  args = [len(lengths), bases.ctypes.data, quality.ctypes.data, seq_off.ctypes.data, mapq.ctypes.data, len(descs), table]
+  return args, (bases, quality, seq_off, mapq, table)
+
+
+def _compact_call(windows, options, device, stream=0):
+  args, keep = _sequence_table(windows)                  # pylint: disable=unused-variable
   opt = _native_options(options)
   handle, out = C.c_void_p(), _lib.DvDebruijnCompact()
-  args = [len(lengths), bases.ctypes.data, quality.ctypes.data, seq_off.ctypes.data, mapq.ctypes.data, len(descs), table,
-          C.byref(opt)]
+  args.append(C.byref(opt))
   if device:
     _lib.check(_lib.lib().dv_debruijn_compact_batch_device(*args, stream, C.byref(handle), C.byref(out)))
   else:
     _lib.check(_lib.lib().dv_debruijn_compact_batch(*args, C.byref(handle), C.byref(out)))
   try:
-    n = len(descs)
+    n = len(windows)
     view = lambda ptr, lo, hi: (np.ctypeslib.as_array(ptr, shape=(hi,))[lo:hi].copy() if hi > lo       # noqa: E731
                                 else np.zeros(0, np.int32))
     k = view(out.k, 0, n)
@@ -145,6 +153,48 @@ def compact_batch_device(windows: Sequence, options: DeBruijnGraphOptions, strea
   stats = _lib.DvDebruijnDeviceStats()
   _lib.check(_lib.lib().dv_debruijn_device_last_stats(C.byref(stats)))
   return graphs, stats
+
+
+def _paths_call(windows, options, device, stream=0):
+  args, keep = _sequence_table(windows)                  # pylint: disable=unused-variable
+  opt = _native_options(options)
+  handle, out = C.c_void_p(), _lib.DvDebruijnPaths()
+  args.append(C.byref(opt))
+  if device:
+    _lib.check(_lib.lib().dv_debruijn_paths_batch_device(*args, stream, C.byref(handle), C.byref(out)))
+  else:
+    _lib.check(_lib.lib().dv_debruijn_paths_batch(*args, C.byref(handle), C.byref(out)))
+  try:
+    n = len(windows)
+    first = np.ctypeslib.as_array(out.hap_first, shape=(n + 1,))
+    off = np.ctypeslib.as_array(out.hap_off, shape=(int(first[n]) + 1,))
+    text = C.string_at(out.hap_text, int(off[-1])) if off[-1] else b''
+    result = []
+    for w in range(n):
+      haps = [text[off[h]:off[h + 1]].decode() for h in range(int(first[w]), int(first[w + 1]))]
+      result.append((int(out.k[w]), int(out.status[w]), haps))
+    return result
+  finally:
+    _lib.lib().dv_debruijn_paths_free(handle)
+
+
+def paths_batch(windows: Sequence, options: DeBruijnGraphOptions):
+  """Per window of `windows` ((ref, reads) pairs) -> (k, status, [haplotypes]) from the host code: what
+  build(ref, reads, options) gives -- kmer_size and candidate_haplotypes(), in its order.  status is
+  _lib.DV_DEBRUIJN_PATHS_OK, _NO_GRAPH (build returns None; k = 0) or _TOO_MANY (more than max_num_paths walks)."""
+  return _paths_call(list(windows), options, device=False)
+
+
+def paths_batch_device(windows: Sequence, options: DeBruijnGraphOptions, stream: int = 0, with_stats: bool = False):
+  """The same from the device: the graph launch and the paths launch of csrc/debruijn.hip over all windows; identical
+  results.  with_stats: -> (results, _lib.DvDebruijnPathsStats of the call).  Raises DvError(DV_ERR_NO_DEVICE) without a
+  GPU when there is device work."""
+  result = _paths_call(list(windows), options, device=True, stream=stream)
+  if not with_stats:
+    return result
+  stats = _lib.DvDebruijnPathsStats()
+  _lib.check(_lib.lib().dv_debruijn_paths_last_stats(C.byref(stats)))
+  return result, stats
 
 
 def from_compact(ref: str, reads: Sequence, options: DeBruijnGraphOptions,

@@ -320,6 +320,8 @@ class RealignJob:
                                    # DV_REALIGN_DEVICE_FASTPASS=1 moved the fast pass to the device)
     self.assembly_stats = None     # _lib.DvDebruijnDeviceStats of the call, device route only (all zero unless
                                    # DV_REALIGN_DEVICE_ASSEMBLY=1 moved phase 1's graphs to the device)
+    self.paths_stats = None        # _lib.DvDebruijnPathsStats of the call, device route only (all zero unless
+                                   # DV_REALIGN_DEVICE_PATHS=1 moved pruning and path enumeration there as well)
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -372,6 +374,9 @@ class RealignJob:
       assembly = _lib.DvDebruijnDeviceStats()
       _lib.check(_lib.lib().dv_debruijn_device_last_stats(C.byref(assembly)))
       self.assembly_stats = assembly
+      paths = _lib.DvDebruijnPathsStats()
+      _lib.check(_lib.lib().dv_debruijn_paths_last_stats(C.byref(paths)))
+      self.paths_stats = paths
     else:
       _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
                                                C.byref(out)))

@@ -1013,6 +1013,54 @@ int dv_debruijn_from_compact(const char* ref, int64_t ref_len, const uint8_t* ba
                              const int32_t* edge_is_ref, const int32_t* edge_seq, const int32_t* edge_pos,
                              dv_debruijn_graph** out);
 
+/* The candidate haplotypes of many windows in one call: what dv_debruijn_build + dv_debruijn_haplotypes give per
+ * window, as text.  The arguments are dv_debruijn_compact_batch's.  status[w] is 0: the window's haplotypes follow,
+ * exactly candidate_haplotypes()'s and in its order ([reference] when the graph has one walk); 1: no graph
+ * (dv_debruijn_build returns NULL; k[w] = 0); 2: more than max_num_paths walks, no haplotypes.  Window w's haplotypes
+ * are numbers [hap_first[w], hap_first[w + 1]); haplotype h is hap_text[hap_off[h], hap_off[h + 1]). */
+typedef struct dv_debruijn_paths {     /* views into the result; valid until dv_debruijn_paths_free */
+  const int32_t* k;                /* [n_windows] the winning k, 0 for no graph */
+  const int32_t* status;           /* [n_windows] DV_DEBRUIJN_PATHS_* */
+  const int32_t* hap_first;        /* [n_windows + 1] into hap_off */
+  const int64_t* hap_off;          /* [n_haps + 1] into hap_text */
+  const char* hap_text;
+} dv_debruijn_paths;
+#define DV_DEBRUIJN_PATHS_OK 0
+#define DV_DEBRUIJN_PATHS_NO_GRAPH 1
+#define DV_DEBRUIJN_PATHS_TOO_MANY 2
+typedef struct dv_debruijn_paths_result dv_debruijn_paths_result;
+/* Host code: DeBruijnGraph::build and candidate_haplotypes per window.  The reference of the device form. */
+int dv_debruijn_paths_batch(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                            const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                            const dv_debruijn_options* options, dv_debruijn_paths_result** out,
+                            dv_debruijn_paths* arrays);
+void dv_debruijn_paths_free(dv_debruijn_paths_result* r);
+/* The same from the device (csrc/debruijn.hip): one upload, the graph launch and one paths launch behind it with a
+ * workgroup per window each -- pruning, the count of source -> sink walks and the walks' text in lexicographic order
+ * --, one download of per-window headers and haplotype slices (no vertex or edge pools) and one synchronisation on
+ * `stream` (NULL = a non-blocking stream the library owns); identical arrays.  Not an error, but computed by the host
+ * code inside the call and counted in windows_on_host: a window the graph kernel hands back (the limits above), a
+ * window whose haplotypes' text passes DV_DEBRUIJN_DEVICE_MAX_HAP_BYTES, and every window of a call with
+ * disable_graph_pruning set or max_num_paths above DV_DEBRUIJN_DEVICE_MAX_PATHS.  Errors as
+ * dv_debruijn_compact_batch_device; DV_ERR_NO_DEVICE only when there is device work. */
+#define DV_DEBRUIJN_DEVICE_MAX_PATHS 1024
+#define DV_DEBRUIJN_DEVICE_MAX_HAP_BYTES 262144
+int dv_debruijn_paths_batch_device(int32_t n_seqs, const char* bases, const uint8_t* quals, const int64_t* seq_off,
+                                   const uint8_t* mapq, int32_t n_windows, const dv_debruijn_window* windows,
+                                   const dv_debruijn_options* options, void* stream, dv_debruijn_paths_result** out,
+                                   dv_debruijn_paths* arrays);
+typedef struct dv_debruijn_paths_stats {
+  int64_t windows;           /* windows asked for */
+  int64_t windows_on_host;   /* of them computed by the host code (see above) */
+  int64_t paths;             /* haplotypes the device produced */
+  int64_t hap_bytes;         /* their text */
+  int64_t launches;          /* kernel launches, the graph kernel's included */
+  int64_t bytes_down;        /* size of the download */
+} dv_debruijn_paths_stats;
+/* What the calling thread's last dv_debruijn_paths_batch_device or dv_realign_regions_device did with the paths (all
+ * zero when the latter did not use them: DV_REALIGN_DEVICE_PATHS unset). */
+int dv_debruijn_paths_last_stats(dv_debruijn_paths_stats* out);
+
 /* ---- the window realigner over many regions in one call (host only, threaded) -----
  * Replaces the body of Realigner.realign_reads (deepvariant/realigner/realigner.py:795-855) for a
  * BATCH of calling regions whose candidate windows are already selected: per window the reads
@@ -1083,7 +1131,11 @@ void dv_realign_result_free(dv_realign_result* r);
  * DV_REALIGN_DEVICE_ASSEMBLY=1, read at each call as well, moves phase 1's graph building there: the windows of all
  * regions go through one dv_debruijn_compact_batch_device-style launch, and the host threads prune and enumerate
  * from the compact graphs (dv_debruijn_from_compact's code); unset or 0 each window is built on a host thread.
- * dv_debruijn_device_last_stats reports it. */
+ * dv_debruijn_device_last_stats reports it.
+ * DV_REALIGN_DEVICE_PATHS=1, read at each call and honoured only together with DV_REALIGN_DEVICE_ASSEMBLY=1, also
+ * prunes and enumerates there (dv_debruijn_paths_batch_device's kernels): the host threads only compare a window's
+ * haplotypes with its reference, and build the windows the device hands back.  dv_debruijn_paths_last_stats reports
+ * it. */
 int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
                               void* stream, dv_realign_result** out, dv_realign_output* arrays,
                               dv_realign_device_stats* stats);

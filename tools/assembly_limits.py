@@ -1,5 +1,6 @@
 """The largest de Bruijn graphs of the realigner's windows, for DV_DEBRUIJN_DEVICE_MAX_* (include/dvhip.h): per window
-the vertices and edges of the winning k's graph before pruning and the bases of the reference plus the reads, over
+the vertices and edges of the winning k's graph before pruning, the bases of the reference plus the reads, and (for
+DV_DEBRUIJN_DEVICE_MAX_HAP_BYTES) the number of candidate haplotypes and the sum of their lengths, over
 the chr20 golden batch, the ten NA12878 regions of tests/test_hip_realigner_fast_pass.py and the 100-region batch of
 tools/realign_bench.py.  Host code only (dv_debruijn_compact_batch; the windows come from the CPU allele counter of
 the tests), so it runs without a GPU.  Prints one JSON line.
@@ -89,7 +90,12 @@ def main():
     for name, (ref, tables, regions) in batches.items():
       windows = _windows_of(ref, tables, regions)
       graphs = debruijn_graph.compact_batch(windows, R.realigner_config().dbg_config)
+      # for DV_DEBRUIJN_DEVICE_MAX_HAP_BYTES: the haplotypes of a window, candidate_haplotypes()'s own
+      paths = debruijn_graph.paths_batch(windows, R.realigner_config().dbg_config)
       result[name] = {
+          'max_paths': max([len(h) for _, _, h in paths], default=0),
+          'max_hap_bytes': max([sum(len(s) for s in h) for _, _, h in paths], default=0),
+          'over_max_num_paths': sum(status == 2 for _, status, _ in paths),
           'windows': len(windows), 'no_graph': sum(g.k == 0 for g in graphs),
           'max_vertices': max([len(g.vertex_seq) for g in graphs], default=0),
           'max_edges': max([len(g.edge_from) for g in graphs], default=0),

@@ -12,7 +12,10 @@ Where it has the device fast pass, `device_fast_pass` is one more alternating ar
 trace-back on the host, against `device` with both switches 0; its (haplotype, read) pairs and diagonal cells are in
 `stats`.  Where it has the device assembly, `device_assembly` (DV_REALIGN_DEVICE_ASSEMBLY=1, the other two switches 0:
 phase 1's graphs in one launch of csrc/debruijn.hip) and `device_all` (all three switches 1) alternate with them too;
-windows, k-mer occurrences hashed and k values tried are in `stats`.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
+windows, k-mer occurrences hashed and k values tried are in `stats`.  Where it has the device paths, `device_all_paths`
+(all four switches 1: DV_REALIGN_DEVICE_PATHS=1 on top of `device_all`, pruning and the haplotypes from the device too)
+is one more arm, compared with `device_all`; its windows, haplotypes and download size are in `stats`, next to the
+size of `device_all`'s download of the graphs' pools.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
 measures an older checkout.  Kernel time is not measured here: run this under
 `rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
 `cells` by local_align_sweeps' time per call (fast_pass_kernel: `fast_pass_cells`, with DV_REALIGN_DEVICE_FASTPASS=1
@@ -96,6 +99,8 @@ def main(argv=None):
   has_assembly = hasattr(_lib, 'DvDebruijnDeviceStats')
   switch, fast_pass_switch = 'DV_REALIGN_DEVICE_TRACEBACK', 'DV_REALIGN_DEVICE_FASTPASS'
   assembly_switch = 'DV_REALIGN_DEVICE_ASSEMBLY'
+  has_paths = hasattr(_lib, 'DvDebruijnPathsStats')
+  paths_switch = 'DV_REALIGN_DEVICE_PATHS'
   if has_device:
     routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
               'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
@@ -106,16 +111,21 @@ def main(argv=None):
     if has_assembly:
       routes['device_assembly'] = routes['device']
       routes['device_all'] = routes['device']
+    if has_paths:
+      routes['device_all_paths'] = routes['device']
   else:
     routes = {'host': R.Realigner(R.realigner_config(), ref)}
 
   def run(route):
     if has_traceback:
-      os.environ[switch] = '1' if route in ('device_traceback', 'device_all') else '0'   # read by the library at each call
+      # read by the library at each call
+      os.environ[switch] = '1' if route in ('device_traceback', 'device_all', 'device_all_paths') else '0'
     if has_fast_pass:
-      os.environ[fast_pass_switch] = '1' if route in ('device_fast_pass', 'device_all') else '0'
+      os.environ[fast_pass_switch] = '1' if route in ('device_fast_pass', 'device_all', 'device_all_paths') else '0'
     if has_assembly:
-      os.environ[assembly_switch] = '1' if route in ('device_assembly', 'device_all') else '0'
+      os.environ[assembly_switch] = '1' if route in ('device_assembly', 'device_all', 'device_all_paths') else '0'
+    if has_paths:
+      os.environ[paths_switch] = '1' if route == 'device_all_paths' else '0'
     gc.collect()
     t0 = time.perf_counter()
     job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
@@ -161,6 +171,15 @@ def main(argv=None):
     result['stats'].update({'assembly_windows': asm.windows, 'assembly_windows_on_host': asm.windows_on_host,
                             'assembly_kmers': asm.kmers, 'assembly_k_tries': asm.k_tries,
                             'assembly_launches': asm.launches, 'assembly_windows_rejected': asm.windows_rejected})
+  if has_paths:
+    _, _, got, job = run('device_all_paths')
+    assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device paths differ'
+    ps, asm = job.paths_stats, job.assembly_stats
+    assert job.device_stats.launches == 1 and job.fast_pass_stats.launches == 1
+    assert ps.launches == 2 and ps.windows == asm.windows > 0 and ps.windows_on_host == 0 and asm.windows_rejected == 0
+    result['stats'].update({'paths_windows': ps.windows, 'paths_windows_on_host': ps.windows_on_host,
+                            'paths_haplotypes': ps.paths, 'paths_hap_bytes': ps.hap_bytes,
+                            'paths_launches': ps.launches, 'paths_bytes_down': ps.bytes_down})
   for threads in [int(t) for t in args.threads.split(',')]:
     R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
     runs = {route: [] for route in routes if not args.arms or route in args.arms.split(',')}
@@ -191,6 +210,11 @@ def main(argv=None):
         entry[arm + '_over_device_native'] = round(entry[arm]['native_call_ms'] / entry['device']['native_call_ms'], 4)
         entry[arm + '_median_below_device_min'] = (entry[arm]['native_call_ms'] <
                                                    min(entry['device']['native_call_runs_ms']))
+    if 'device_all_paths' in entry and 'device_all' in entry:
+      entry['device_all_paths_over_device_all_native'] = round(entry['device_all_paths']['native_call_ms'] /
+                                                               entry['device_all']['native_call_ms'], 4)
+      entry['device_all_paths_median_below_device_all_min'] = (entry['device_all_paths']['native_call_ms'] <
+                                                               min(entry['device_all']['native_call_runs_ms']))
     result['threads'][str(threads)] = entry
   line = json.dumps(result)
   print(line)
