@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
     'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
+    'dv_select_windows_batch', 'dv_windows_arrays', 'dv_windows_free',
 ]
 
 
@@ -439,6 +440,16 @@ class DvCandidateOptions(C.Structure):
               ('track_ref_reads', C.c_int32), ('positions_only', C.c_int32)]
 
 
+class DvWindowOptions(C.Structure):
+  # include/dvhip.h dv_window_options: the coefficients are C floats, the boundary a double (as the reference compares)
+  _fields_ = [('model_type', C.c_int32), ('min_num_supporting_reads', C.c_int32), ('max_num_supporting_reads', C.c_int32),
+              ('min_allele_support', C.c_int32), ('enable_strict_insertion_filter', C.c_int32),
+              ('bias', C.c_float), ('coeff_soft_clip', C.c_float), ('coeff_substitution', C.c_float),
+              ('coeff_insertion', C.c_float), ('coeff_deletion', C.c_float), ('coeff_reference', C.c_float),
+              ('min_windows_distance', C.c_int32), ('decision_boundary', C.c_double),
+              ('want_debug', C.c_int32), ('reserved', C.c_int32)]
+
+
 class DvCandidateSite(C.Structure):
   _fields_ = [('offset', C.c_int32), ('ref_count', C.c_int32), ('total', C.c_int32),
               ('first_allele', C.c_int32), ('n_alleles', C.c_int32)]
@@ -641,6 +652,11 @@ def lib():
     l.dv_candidates_arrays.argtypes = [C.c_void_p] * 6
     l.dv_candidates_free.argtypes = [C.c_void_p]
     l.dv_candidates_free.restype = None
+    l.dv_select_windows_batch.argtypes = [C.c_int32] + [C.c_void_p] * 7
+    l.dv_windows_arrays.restype = C.c_int64
+    l.dv_windows_arrays.argtypes = [C.c_void_p] * 5
+    l.dv_windows_free.argtypes = [C.c_void_p]
+    l.dv_windows_free.restype = None
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -204,6 +204,7 @@ class AlleleCounter:
     self._gvcf = None            # (GvcfOptions.key(), dv_gvcf_block records) of the last gVCF pass
     self._cand = None            # (CandidateOptions.key(), sites, alleles, event words) of the last candidate pass
     self._cand_positions = None  # (CandidateOptions.key(), offsets) of the last positions-only pass
+    self._windows = None         # (window key, starts, ends, candidate mask, scores) of the last window pass
 
   # ---- the reference's interface
   def interval_length(self) -> int:
@@ -217,6 +218,7 @@ class AlleleCounter:
       raise ValueError('reads were handed over as a packed table; add() cannot be mixed in')
     self._reads.append(read)
     self._counts = self._alleles = self._events = self._gvcf = self._cand = self._cand_positions = None
+    self._windows = None
 
   def add_table(self, table: packing.ReadTable):
     """All reads of the region at once, already packed (packing.ReadTable.from_bam / from_reads)."""
@@ -224,6 +226,7 @@ class AlleleCounter:
       raise ValueError('add() was used; add_table() cannot be mixed in')
     self._table = table
     self._counts = self._alleles = self._events = self._gvcf = self._cand = self._cand_positions = None
+    self._windows = None
 
   def _ensure(self):
     if self._events is None:
@@ -352,7 +355,8 @@ class AlleleCounter:
     self._take(handle, ctx)
 
   @staticmethod
-  def run_batch(counters: Sequence['AlleleCounter'], gvcf=None, call=None) -> None:
+  def run_batch(counters: Sequence['AlleleCounter'], gvcf=None, call=None, windows=None,
+                window_debug: bool = False) -> None:
     """Counts for several counters (a batch of calling regions, each with its reads added) in ONE
     dv_count_alleles_batch call: one upload, kernels back to back, two synchronisations for the
     whole batch.  Afterwards every counter answers as if it had counted alone.  With `gvcf`
@@ -360,7 +364,17 @@ class AlleleCounter:
     pass (dv_count_alleles_gvcf_batch) and `gvcf_blocks(gvcf)` answers without another launch.  With
     `call` (variant_calling.CandidateOptions) so are the candidates (dv_call_candidates_batch):
     `candidates(call)` / `candidate_positions(call)` then answer without another launch; a
-    positions-only pass leaves the counters uncounted."""
+    positions-only pass leaves the counters uncounted.  With `windows` (the realigner's
+    WindowSelectorOptions) the realigner's windows are selected in the same way
+    (dv_select_windows_batch): `windows(options)` then answers without another launch, nothing but the
+    windows comes home and the counters stay uncounted (`window_debug`: the candidate mask and the scores
+    come too, for `windows(options, want_debug=True)`)."""
+    if windows is not None:
+      if gvcf is not None or call is not None:
+        raise ValueError('the window pass runs on its own')
+      key = _window_key(windows, window_debug)
+      AlleleCounter._run_window_batch([c for c in counters if not c._has_windows(key)], windows, window_debug)   # pylint: disable=protected-access
+      return
     if call is not None:
       todo = [c for c in counters if not c._has_candidates(call) or                   # pylint: disable=protected-access
               (gvcf is not None and (c._gvcf is None or c._gvcf[0] != gvcf.key()))]   # pylint: disable=protected-access
@@ -510,6 +524,61 @@ class AlleleCounter:
           lib.dv_gvcf_blocks_free(C.c_void_p(b))
         if d:
           lib.dv_candidates_free(C.c_void_p(d))
+
+  def _has_windows(self, key) -> bool:
+    if self._windows is None:
+      return False
+    have = self._windows[0]
+    # a pass that also brought the mask and the scores answers for one that did not
+    return have == key or (not key[-1] and have[:-1] == key[:-1])
+
+  @staticmethod
+  def _run_window_batch(todo: Sequence['AlleleCounter'], config, want_debug: bool = False) -> None:
+    if not todo:
+      return
+    requests = [c._request() for c in todo]                # pylint: disable=protected-access
+    n = len(todo)
+    keys = [AlleleCounter._read_key_ids(r[3][0].keys) for r in requests]
+    key = _window_key(config, want_debug)
+    wopt = _window_options_struct(config, want_debug)
+    batches = (C.c_void_p * n)(*[C.addressof(r[0]) for r in requests])
+    options = (C.c_void_p * n)(*[C.addressof(r[1]) for r in requests])
+    key_ptrs = (C.c_void_p * n)(*[k.ctypes.data if k is not None else None for k in keys])
+    handles = (C.c_void_p * n)()
+    lib = _lib.lib()
+    _lib.check(lib.dv_select_windows_batch(n, batches, options, key_ptrs, C.byref(wopt), None, handles, None))
+    try:
+      for c, h in zip(todo, handles):
+        starts, ends, mask, scores = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n_windows = int(lib.dv_windows_arrays(C.c_void_p(h), C.byref(starts), C.byref(ends), C.byref(mask),
+                                              C.byref(scores)))
+
+        def array(pointer, count, dtype):
+          return (np.frombuffer(C.string_at(pointer, count * np.dtype(dtype).itemsize), dtype) if count and pointer
+                  else np.zeros(0, dtype))
+        length = c._end - c._start                         # pylint: disable=protected-access
+        mask_arr = score_arr = None
+        if want_debug:
+          words = array(mask, (length + 31) // 32, '<u4')
+          mask_arr = np.unpackbits(words.view(np.uint8), bitorder='little')[:length].astype(bool)
+          score_arr = array(scores, length, '<u4')
+        c._windows = (key, array(starts, n_windows, '<i8'), array(ends, n_windows, '<i8'), mask_arr, score_arr)  # pylint: disable=protected-access
+    finally:
+      for h in handles:
+        if h:
+          lib.dv_windows_free(C.c_void_p(h))
+
+  def windows(self, config, want_debug: bool = False):
+    """select_windows' candidates and windows from the device (window_select.hip), for the realigner's
+    WindowSelectorOptions `config`, over this counter's interval: -> (starts, ends) in contig coordinates, end
+    exclusive, unclamped -- computed now unless run_batch(windows=...) already did with these options.  With
+    `want_debug` -> (starts, ends, candidate mask [interval_length] bool, scores [interval_length] uint32: the
+    float32 scores' bit patterns, or for the VARIANT_READS model the counts)."""
+    key = _window_key(config, want_debug)
+    if not self._has_windows(key):
+      AlleleCounter._run_window_batch([self], config, want_debug)
+    _, starts, ends, mask, scores = self._windows
+    return (starts, ends, mask, scores) if want_debug else (starts, ends)
 
   def candidate_positions(self, call) -> List[int]:
     """CallPositionsFromAlleleCounts from the device: the absolute positions CallVariant will return a
@@ -704,6 +773,24 @@ class AlleleCounter:
     np.add.at(out, lo[ok], 1)
     np.add.at(out, hi[ok], -1)
     return np.cumsum(out)[:n]
+
+
+def _window_fields(config):
+  model = config.window_selector_model
+  vr, lin = model.variant_reads_model, model.allele_count_linear_model
+  return (int(model.model_type), int(vr.min_num_supporting_reads), int(vr.max_num_supporting_reads),
+          int(config.min_allele_support), int(bool(config.enable_strict_insertion_filter)),
+          float(lin.bias), float(lin.coeff_soft_clip), float(lin.coeff_substitution), float(lin.coeff_insertion),
+          float(lin.coeff_deletion), float(lin.coeff_reference), int(config.min_windows_distance),
+          float(lin.decision_boundary))
+
+
+def _window_key(config, want_debug: bool) -> tuple:
+  return _window_fields(config) + (bool(want_debug),)
+
+
+def _window_options_struct(config, want_debug: bool) -> '_lib.DvWindowOptions':
+  return _lib.DvWindowOptions(*_window_fields(config), int(bool(want_debug)), 0)
 
 
 # ---------------------------------------------------------------- NormalizeCigar (host)

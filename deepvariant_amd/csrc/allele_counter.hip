@@ -664,6 +664,76 @@ int candidates_from_counts(const dv_allele_counts* c, const dv_allele_counter_op
   return DV_OK;
 }
 
+// The window pass over a region's host counts: the candidate pass' image, with the window kernels' descriptor,
+// scratch and records behind it.
+int windows_from_counts(const dv_allele_counts* c, const dv_allele_counter_options* o, const dv_batch* b,
+                        const int32_t* keys, const dv_window_options* wo, hipStream_t stream, dv_windows** out) {
+  static thread_local CountsBuffers buf;
+  auto res = std::make_unique<dv_windows>();
+  if (c->length == 0) {
+    *out = res.release();
+    return DV_OK;
+  }
+  if (c->length > 0x7fffffff - 2) return dv::fail(DV_ERR_INVALID_ARGUMENT, "interval too long for the window pass");
+  CountsImage im = lay_counts_image(sizeof(dv::CandRegion), c, b, keys);
+  const size_t n_reads = static_cast<size_t>(b->n_reads);
+  const bool table_on_host = b->memory == DV_MEM_HOST && n_reads > 0;
+  const size_t o_wdesc = im.lay.add(sizeof(dv::WindowRegion));
+  const size_t o_seq = table_on_host ? im.lay.add((n_reads + 1) * sizeof(uint32_t)) : 0;
+  const size_t o_bases = table_on_host ? im.lay.add(b->n_bases) : 0;
+  const size_t up_bytes = im.lay.bytes();
+  const size_t n_win_cap = dv::win_cap(im.len, wo->min_windows_distance), n_mask = dv::mask_words(im.len);
+  const size_t o_scr = im.lay.add(dv::cand_scratch_ints(im.len, im.n_ev) * sizeof(int32_t));
+  const size_t o_wscr = im.lay.add(dv::win_scratch_ints(im.len, im.n_ev) * sizeof(int32_t));
+  const size_t o_win = im.lay.add(n_win_cap * 2 * sizeof(int64_t));
+  const size_t o_score = im.lay.add(static_cast<size_t>(im.len) * sizeof(uint32_t));
+  const size_t o_mask = im.lay.add(n_mask * sizeof(uint32_t));
+  if (int rc = buf.stage.reserve(up_bytes)) return rc;
+  if (int rc = buf.d_img.reserve_on_current_device(im.lay.bytes())) return rc;
+  uint8_t* dev = static_cast<uint8_t*>(buf.d_img.ptr);
+  const CountsOnDevice counts = stage_counts(im, c, o, keys, buf.stage.ptr, dev);
+  if (table_on_host) {
+    std::memcpy(buf.stage.ptr + o_seq, b->read_seq_off, (n_reads + 1) * sizeof(uint32_t));
+    std::memcpy(buf.stage.ptr + o_bases, b->bases, b->n_bases);
+  }
+  const dv::CandRegion g = cand_region(counts, table_on_host ? dev + o_bases : b->bases,
+                                       table_on_host ? at<const uint32_t>(dev, o_seq) : b->read_seq_off,
+                                       at<int32_t>(dev, o_scr), nullptr, nullptr, nullptr, nullptr);
+  const bool debug = wo->want_debug != 0;
+  const dv::WindowRegion w{o->interval_start, at<int32_t>(dev, o_wscr), at<int64_t>(dev, o_win),
+                           at<int32_t>(dev, im.words + 4), debug ? at<uint32_t>(dev, o_mask) : nullptr,
+                           debug ? at<uint32_t>(dev, o_score) : nullptr};
+  std::memcpy(buf.stage.ptr + im.desc, &g, sizeof(g));
+  std::memcpy(buf.stage.ptr + o_wdesc, &w, sizeof(w));
+  if (int rc = upload_counts_image(buf, up_bytes, o_scr, o_win - o_scr, stream)) return rc;
+  if (int rc = dv::window_launch(at<const dv::CandRegion>(dev, im.desc), at<const dv::WindowRegion>(dev, o_wdesc), 1,
+                                 im.n_ev, wo, nullptr, stream)) {
+    return rc;
+  }
+  int32_t n_windows = 0;
+  if (int rc = download_record_counts(buf, im, &n_windows, 1, stream)) return rc;
+  std::vector<int64_t> pairs(static_cast<size_t>(n_windows) * 2);
+  if (n_windows) {
+    DV_HIP_CHECK(hipMemcpyAsync(pairs.data(), dev + o_win, pairs.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+  }
+  if (debug) {
+    res->scores.resize(static_cast<size_t>(im.len));
+    res->mask.resize(n_mask);
+    DV_HIP_CHECK(hipMemcpyAsync(res->scores.data(), dev + o_score, res->scores.size() * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, stream));
+    DV_HIP_CHECK(hipMemcpyAsync(res->mask.data(), dev + o_mask, n_mask * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  }
+  DV_HIP_CHECK(hipStreamSynchronize(stream));
+  res->starts.resize(static_cast<size_t>(n_windows));
+  res->ends.resize(static_cast<size_t>(n_windows));
+  for (size_t i = 0; i < res->starts.size(); ++i) {
+    res->starts[i] = pairs[2 * i];
+    res->ends[i] = pairs[2 * i + 1];
+  }
+  *out = res.release();
+  return DV_OK;
+}
+
 // ---- the batch entry point's steps, in the order count_batch takes them
 
 // What one call asked for.
@@ -674,29 +744,33 @@ struct BatchRequest {
   const int32_t* const* read_keys;
   const dv_gvcf_options* gv;           // null: no gVCF pass
   const dv_candidate_options* co;      // null: no candidate pass
-  bool pos_only;                       // positions only: neither counts nor events come back
+  const dv_window_options* wo;         // null: no window pass
+  bool pos_only;                       // positions or windows only: neither counts nor events come back
   hipStream_t stream;
   const char* who;
   const int32_t* keys_of(int32_t k) const { return read_keys ? read_keys[k] : nullptr; }
 };
 
 // The caller's result arrays.  Until release() every result in them is this guard's: on an error exit -- the
-// DV_HIP_CHECK returns included -- none is left allocated and every entry is null.  With positions_only the
-// counts of a region that went alone live in own_out and never reach the caller.
+// DV_HIP_CHECK returns included -- none is left allocated and every entry is null.  With positions_only (or a
+// window pass without counts_out) the counts of a region that went alone live in own_out and never reach the caller.
 struct BatchResults {
   int32_t n = 0;
   dv_allele_counts** out = nullptr;
   dv_gvcf_blocks** gout = nullptr;     // null without the pass
   dv_candidates** cout = nullptr;
+  dv_windows** wout = nullptr;
   std::vector<dv_allele_counts*> own_out;
   bool released = false;
 
-  void take(int32_t count, dv_allele_counts** counts, dv_gvcf_blocks** blocks, dv_candidates** candidates) {
-    n = count, out = counts, gout = blocks, cout = candidates;
+  void take(int32_t count, dv_allele_counts** counts, dv_gvcf_blocks** blocks, dv_candidates** candidates,
+            dv_windows** windows) {
+    n = count, out = counts, gout = blocks, cout = candidates, wout = windows;
     for (int32_t k = 0; k < n; ++k) {
       out[k] = nullptr;
       if (gout) gout[k] = nullptr;
       if (cout) cout[k] = nullptr;
+      if (wout) wout[k] = nullptr;
     }
   }
   void release() { released = true; }
@@ -709,23 +783,27 @@ struct BatchResults {
       if (!released || !own_out.empty()) drop(out[k]);
       if (!released && gout) drop(gout[k]);
       if (!released && cout) drop(cout[k]);
+      if (!released && wout) drop(wout[k]);
     }
   }
 };
 
 // Everything that can be refused before any device work; hands the result arrays to `results`.
 int check_batch(const BatchRequest& rq, dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout,
-                BatchResults* results) {
+                dv_windows** wout, BatchResults* results) {
   const std::string name(rq.who);
   const int32_t n = rq.n;
   if (rq.pos_only && n > 0) {
     results->own_out.assign(static_cast<size_t>(n), nullptr);
     out = results->own_out.data();
   }
-  if (n < 0 || (n > 0 && (!rq.reads || !rq.options || !out || (rq.gv && !gout) || (rq.co && !cout)))) {
+  if (n < 0 || (n > 0 && (!rq.reads || !rq.options || !out || (rq.gv && !gout) || (rq.co && !cout) || (rq.wo && !wout)))) {
     return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": null");
   }
-  results->take(n, out, rq.gv ? gout : nullptr, rq.co ? cout : nullptr);
+  results->take(n, out, rq.gv ? gout : nullptr, rq.co ? cout : nullptr, rq.wo ? wout : nullptr);
+  if (rq.wo) {
+    if (int rc = dv::window_check_options(rq.wo, rq.who)) return rc;
+  }
   if (rq.gv) {
     if (int rc = dv::gvcf_check_options(rq.gv, rq.who)) return rc;
   }
@@ -745,6 +823,9 @@ int check_batch(const BatchRequest& rq, dv_allele_counts** out, dv_gvcf_blocks**
     if (rq.co && o->interval_end - o->interval_start > 0x7fffffff - 2) {
       return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": interval too long for the candidate pass");
     }
+    if (rq.wo && o->interval_end - o->interval_start > 0x7fffffff - 2) {
+      return dv::fail(DV_ERR_INVALID_ARGUMENT, name + ": interval too long for the window pass");
+    }
   }
   return DV_OK;
 }
@@ -755,6 +836,7 @@ struct BatchBuffers {
   dv::DeviceBuffer d_up, d_res, d_ev;
   dv::DeviceBuffer d_gscr, d_gblk, d_gpack;                              // gVCF: scratch, records, packed records
   dv::DeviceBuffer d_cscr, d_csite, d_call, d_cword, d_cpsite, d_cpall;  // candidates: scratch, sites, alleles, words, packed
+  dv::DeviceBuffer d_wscr, d_wwin, d_wpack, d_wscore, d_wmask;           // windows: scratch, windows, packed, scores, masks
 
   // everything but h_second, whose size the first download tells
   int reserve(const dv::BatchPlan& p) {
@@ -778,6 +860,14 @@ struct BatchBuffers {
       if (int rc = d_cpall.reserve_on_current_device(evs * sizeof(dv_candidate_allele))) return rc;
       if (int rc = d_cword.reserve_on_current_device(evs * sizeof(int32_t))) return rc;
     }
+    if (p.win.n) {
+      const size_t windows = std::max<size_t>(p.win.windows, 1) * 2 * sizeof(int64_t);
+      if (int rc = d_wscr.reserve_on_current_device(p.win.scratch_ints * sizeof(int32_t))) return rc;
+      if (int rc = d_wwin.reserve_on_current_device(windows)) return rc;
+      if (int rc = d_wpack.reserve_on_current_device(windows)) return rc;
+      if (int rc = d_wscore.reserve_on_current_device(sites * sizeof(uint32_t))) return rc;
+      if (int rc = d_wmask.reserve_on_current_device(std::max<size_t>(p.win.mask_words, 1) * sizeof(uint32_t))) return rc;
+    }
     return DV_OK;
   }
 };
@@ -800,7 +890,7 @@ void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, 
   std::memcpy(host + p.up.ref, o->ref_bases, static_cast<size_t>(o->n_ref_bases));
   if (p.mask_words) build_candidate_mask(o, p.len, at<uint32_t>(host, p.up.mask));
   if (p.has_keys) std::memcpy(host + p.up.keys, rq.keys_of(k), nr * 4);
-  if (p.gv.slot < 0 && p.cd.slot < 0) return;
+  if (p.gv.slot < 0 && p.cd.slot < 0 && p.win.slot < 0) return;
   void* dup = buf.d_up.ptr;
   const CountsOnDevice c{at<const int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off,
                          static_cast<const dv_allele_event*>(buf.d_ev.ptr) + p.ev_off,
@@ -814,6 +904,20 @@ void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, 
         static_cast<dv_candidate_allele*>(buf.d_call.ptr) + p.ev_off, static_cast<int32_t*>(buf.d_cword.ptr) + p.ev_off,
         at<int32_t>(buf.d_res.ptr, plan.n_cand_at) + static_cast<size_t>(k) * 2);
     std::memcpy(host + plan.cd.desc_up + static_cast<size_t>(p.cd.slot) * sizeof(g), &g, sizeof(g));
+  }
+  if (p.win.slot >= 0) {
+    // the grouping kernels of the candidate pass work in the first part of the region's scratch and emit nothing
+    int32_t* scratch = static_cast<int32_t*>(buf.d_wscr.ptr) + p.win.scratch_off;
+    const dv::CandRegion g = cand_region(c, at<const uint8_t>(dup, p.up.bases), at<const uint32_t>(dup, p.up.seq_off),
+                                         scratch, nullptr, nullptr, nullptr, nullptr);
+    const bool debug = rq.wo->want_debug != 0;
+    const dv::WindowRegion w{o->interval_start, scratch + dv::cand_scratch_ints(p.len, p.cap),
+                             static_cast<int64_t*>(buf.d_wwin.ptr) + 2 * p.win.window_off,
+                             at<int32_t>(buf.d_res.ptr, plan.n_win_at) + k,
+                             debug ? static_cast<uint32_t*>(buf.d_wmask.ptr) + p.win.mask_off : nullptr,
+                             debug ? static_cast<uint32_t*>(buf.d_wscore.ptr) + p.cnt_off : nullptr};
+    std::memcpy(host + plan.win.cand_desc_up + static_cast<size_t>(p.win.slot) * sizeof(g), &g, sizeof(g));
+    std::memcpy(host + plan.win.desc_up + static_cast<size_t>(p.win.slot) * sizeof(w), &w, sizeof(w));
   }
   if (p.gv.slot >= 0) {
     const dv::GvcfRegion g = gvcf_region(c, rq.gv, static_cast<int32_t*>(buf.d_gscr.ptr) + p.gv.scratch_off,
@@ -858,6 +962,7 @@ int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const Ba
     if (int rc = dv::gvcf_table_on_device(rq.gv, d_table, stream)) return rc;
   }
   if (plan.cd.n) DV_HIP_CHECK(hipMemsetAsync(buf.d_cscr.ptr, 0, plan.cd.scratch_ints * sizeof(int32_t), stream));
+  if (plan.win.n) DV_HIP_CHECK(hipMemsetAsync(buf.d_wscr.ptr, 0, plan.win.scratch_ints * sizeof(int32_t), stream));
   for (int32_t k = 0; k < rq.n; ++k) {
     if (plan.regions[k].batched) launch_count(batch_count_args(rq, plan, k, buf), rq.reads[k]->n_reads, stream);
   }
@@ -877,6 +982,14 @@ int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const Ba
       return rc;
     }
   }
+  if (plan.win.n) {
+    // window selection reads the same counts and events
+    if (int rc = dv::window_launch(at<const dv::CandRegion>(buf.d_up.ptr, plan.win.cand_desc_up),
+                                   at<const dv::WindowRegion>(buf.d_up.ptr, plan.win.desc_up), plan.win.n, plan.max_cap,
+                                   rq.wo, static_cast<int64_t*>(buf.d_wpack.ptr), stream)) {
+      return rc;
+    }
+  }
   return DV_OK;
 }
 
@@ -885,8 +998,9 @@ int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const Ba
 int download_first(const BatchRequest& rq, const dv::BatchPlan& plan, const BatchBuffers& buf) {
   if (rq.pos_only) {
     DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr, buf.d_res.ptr, plan.counts_at, hipMemcpyDeviceToHost, rq.stream));
-    DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr + plan.n_cand_at, at<uint8_t>(buf.d_res.ptr, plan.n_cand_at),
-                                plan.res_bytes - plan.n_cand_at, hipMemcpyDeviceToHost, rq.stream));
+    const size_t records_at = rq.co ? plan.n_cand_at : plan.n_win_at;      // the record counts behind the counts
+    DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr + records_at, at<uint8_t>(buf.d_res.ptr, records_at),
+                                plan.res_bytes - records_at, hipMemcpyDeviceToHost, rq.stream));
   } else {
     DV_HIP_CHECK(hipMemcpyAsync(buf.h_down.ptr, buf.d_res.ptr, plan.res_bytes, hipMemcpyDeviceToHost, rq.stream));
   }
@@ -908,6 +1022,11 @@ int allocate_results(const BatchRequest& rq, const dv::BatchPlan& plan, const dv
       results->cout[k] = new dv_candidates();
       results->cout[k]->sites.resize(r.n_sites);
       if (!rq.pos_only) results->cout[k]->alleles.resize(r.n_alleles);
+    }
+    if (rq.wo) {
+      results->wout[k] = new dv_windows();
+      results->wout[k]->starts.resize(r.n_windows);
+      results->wout[k]->ends.resize(r.n_windows);
     }
     if (rq.pos_only) continue;
     auto res = std::make_unique<dv_allele_counts>();
@@ -954,12 +1073,23 @@ int download_second(const BatchRequest& rq, const dv::BatchPlan& plan, const dv:
     DV_HIP_CHECK(hipMemcpyAsync(host + second.blocks_at, buf->d_gpack.ptr, second.packed_blocks * sizeof(dv_gvcf_block),
                                 hipMemcpyDeviceToHost, stream));
   }
+  if (second.packed_windows) {
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.windows_at, buf->d_wpack.ptr, second.packed_windows * 2 * sizeof(int64_t),
+                                hipMemcpyDeviceToHost, stream));
+  }
+  if (rq.wo && rq.wo->want_debug && plan.win.n) {
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.scores_at, buf->d_wscore.ptr, plan.cnt_ints * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, stream));
+    DV_HIP_CHECK(hipMemcpyAsync(host + second.masks_at, buf->d_wmask.ptr, plan.win.mask_words * sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, stream));
+  }
   DV_HIP_CHECK(hipStreamSynchronize(stream));
   return DV_OK;
 }
 
 // Out of the second image into the kept regions' results; the events are put in order.
-void unpack(const BatchRequest& rq, const dv::SecondImage& second, const BatchBuffers& buf, BatchResults* results) {
+void unpack(const BatchRequest& rq, const dv::BatchPlan& plan, const dv::SecondImage& second, const BatchBuffers& buf,
+            BatchResults* results) {
   const uint8_t* host = buf.h_second.ptr;
   for (int32_t k = 0; k < rq.n; ++k) {
     const dv::SecondImage::Region& r = second.regions[k];
@@ -969,6 +1099,22 @@ void unpack(const BatchRequest& rq, const dv::SecondImage& second, const BatchBu
       if (r.n_sites) std::memcpy(cand->sites.data(), host + r.sites_at, r.n_sites * sizeof(dv_candidate_site));
       if (r.n_alleles && !rq.pos_only) {
         std::memcpy(cand->alleles.data(), host + r.alleles_at, r.n_alleles * sizeof(dv_candidate_allele));
+      }
+    }
+    if (rq.wo) {
+      dv_windows* win = results->wout[k];
+      const dv::RegionPlan& p = plan.regions[k];
+      for (size_t i = 0; i < r.n_windows; ++i) {
+        std::memcpy(&win->starts[i], host + r.windows_at + 2 * i * sizeof(int64_t), sizeof(int64_t));
+        std::memcpy(&win->ends[i], host + r.windows_at + (2 * i + 1) * sizeof(int64_t), sizeof(int64_t));
+      }
+      if (rq.wo->want_debug) {
+        win->scores.resize(static_cast<size_t>(p.len));
+        win->mask.resize(dv::mask_words(p.len));
+        std::memcpy(win->scores.data(), host + second.scores_at + p.cnt_off * sizeof(uint32_t),
+                    win->scores.size() * sizeof(uint32_t));
+        std::memcpy(win->mask.data(), host + second.masks_at + p.win.mask_off * sizeof(uint32_t),
+                    win->mask.size() * sizeof(uint32_t));
       }
     }
     if (rq.pos_only) continue;
@@ -994,6 +1140,12 @@ int run_alone(const BatchRequest& rq, const dv::SecondImage& second, const dv_gv
     if (rq.co) {
       if (int rc = candidates_from_counts(results->out[k], rq.options[k], rq.reads[k], rq.keys_of(k), rq.co, rq.stream,
                                           &results->cout[k])) {
+        return rc;
+      }
+    }
+    if (rq.wo) {
+      if (int rc = windows_from_counts(results->out[k], rq.options[k], rq.reads[k], rq.keys_of(k), rq.wo, rq.stream,
+                                       &results->wout[k])) {
         return rc;
       }
     }
@@ -1101,14 +1253,17 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
 // behind the counting kernels and its records come back with the events.  Without `gv` nothing differs.
 // With `co` set dv_call_candidates_batch: the candidate pass (candidates.hip) is queued behind the counting
 // kernels in the same way; with positions_only neither counts nor events come back (`out` is not used).
+// With `wo` set dv_select_windows_batch: the window pass (window_select.hip) likewise; without `out` only the
+// windows come back.
 static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                        const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
-                       dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout, void* stream_v,
-                       const char* who) {
-  const BatchRequest rq{n, reads, options, read_keys, gv, co, co && co->positions_only, static_cast<hipStream_t>(stream_v), who};
+                       const dv_window_options* wo, dv_allele_counts** out, dv_gvcf_blocks** gout, dv_candidates** cout,
+                       dv_windows** wout, void* stream_v, const char* who) {
+  const BatchRequest rq{n, reads, options, read_keys, gv, co, wo, (co && co->positions_only) || (wo && !out),
+                        static_cast<hipStream_t>(stream_v), who};
   BatchResults results;              // frees whatever it holds on every return but the last
-  if (int rc = check_batch(rq, out, gout, cout, &results)) return rc;
-  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, read_keys, gv, co);
+  if (int rc = check_batch(rq, out, gout, cout, wout, &results)) return rc;
+  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, read_keys, gv, co, wo);
   dv::SecondImage second;            // of no region yet: which regions the batch has answered
   second.regions.resize(plan.regions.size());
   const dv_gvcf_site* d_table = nullptr;
@@ -1119,10 +1274,11 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     if (int rc = download_first(rq, plan, buf)) return rc;
     second = dv::second_image(plan, at<const uint32_t>(buf.h_down.ptr, plan.counters_at),
                               at<const int32_t>(buf.h_down.ptr, plan.n_blocks_at),
-                              at<const int32_t>(buf.h_down.ptr, plan.n_cand_at), rq.pos_only);
+                              at<const int32_t>(buf.h_down.ptr, plan.n_cand_at), rq.pos_only,
+                              at<const int32_t>(buf.h_down.ptr, plan.n_win_at), wo && wo->want_debug);
     if (int rc = allocate_results(rq, plan, second, buf, &results)) return rc;
     if (int rc = download_second(rq, plan, second, &buf)) return rc;
-    unpack(rq, second, buf, &results);
+    unpack(rq, plan, second, buf, &results);
   }
   if (int rc = run_alone(rq, second, d_table, &results)) return rc;
   results.release();
@@ -1131,14 +1287,15 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
 
 int dv_count_alleles_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                            dv_allele_counts** out, void* stream_v) {
-  return count_batch(n, reads, options, nullptr, nullptr, nullptr, out, nullptr, nullptr, stream_v, "dv_count_alleles_batch");
+  return count_batch(n, reads, options, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, nullptr, stream_v,
+                     "dv_count_alleles_batch");
 }
 
 int dv_count_alleles_gvcf_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                                 const int32_t* const* read_keys, const dv_gvcf_options* gvcf,
                                 dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out, void* stream) {
   if (!gvcf) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_alleles_gvcf_batch: gvcf options are null");
-  return count_batch(n, reads, options, read_keys, gvcf, nullptr, counts_out, blocks_out, nullptr, stream,
+  return count_batch(n, reads, options, read_keys, gvcf, nullptr, nullptr, counts_out, blocks_out, nullptr, nullptr, stream,
                      "dv_count_alleles_gvcf_batch");
 }
 
@@ -1147,9 +1304,29 @@ int dv_call_candidates_batch(int32_t n, const dv_batch* const* reads, const dv_a
                              const dv_gvcf_options* gvcf, dv_allele_counts** counts_out, dv_gvcf_blocks** blocks_out,
                              dv_candidates** candidates_out, void* stream) {
   if (!candidate_options) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_call_candidates_batch: candidate options are null");
-  return count_batch(n, reads, options, read_keys, gvcf, candidate_options, counts_out, blocks_out, candidates_out, stream,
-                     "dv_call_candidates_batch");
+  return count_batch(n, reads, options, read_keys, gvcf, candidate_options, nullptr, counts_out, blocks_out, candidates_out,
+                     nullptr, stream, "dv_call_candidates_batch");
 }
+
+int dv_select_windows_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                            const int32_t* const* read_keys, const dv_window_options* window_options,
+                            dv_allele_counts** counts_out, dv_windows** windows_out, void* stream) {
+  if (!window_options) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_select_windows_batch: window options are null");
+  return count_batch(n, reads, options, read_keys, nullptr, nullptr, window_options, counts_out, nullptr, nullptr,
+                     windows_out, stream, "dv_select_windows_batch");
+}
+
+int64_t dv_windows_arrays(const dv_windows* w, const int64_t** starts, const int64_t** ends,
+                          const uint32_t** candidate_mask, const uint32_t** scores) {
+  if (!w) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_windows_arrays: null");
+  if (starts) *starts = w->starts.data();
+  if (ends) *ends = w->ends.data();
+  if (candidate_mask) *candidate_mask = w->mask.empty() ? nullptr : w->mask.data();
+  if (scores) *scores = w->scores.empty() ? nullptr : w->scores.data();
+  return static_cast<int64_t>(w->starts.size());
+}
+
+void dv_windows_free(dv_windows* w) { delete w; }
 
 int64_t dv_candidates_arrays(const dv_candidates* c, const dv_candidate_site** sites,
                              const dv_candidate_allele** alleles, int32_t* n_alleles, const int32_t** event_words,

@@ -8,6 +8,7 @@
 #include "candidates.h"
 #include "device_round_trip.h"
 #include "gvcf.h"
+#include "window_select.h"
 
 namespace dv {
 
@@ -45,6 +46,11 @@ struct RegionPlan {
     int slot = -1;
     size_t scratch_off = 0;                       // in ints; sites lie at cnt_off, alleles and words at ev_off
   } cd;
+  struct Win {
+    int slot = -1;
+    size_t scratch_off = 0;                       // in ints: the candidate kernels' scratch, then the window kernels'
+    size_t window_off = 0, mask_off = 0;          // in windows / mask words; scores lie at cnt_off
+  } win;
 };
 
 struct BatchPlan {
@@ -54,7 +60,8 @@ struct BatchPlan {
   size_t cnt_ints = 0, ev_total = 0;
   uint32_t max_cap = 0;                           // over the regions of either pass
   // the result image: counters [n][4] | counts | gVCF record counts [n] | candidate site and allele counts [n][2]
-  size_t counters_at = 0, counts_at = 0, n_blocks_at = 0, n_cand_at = 0, res_bytes = 0;
+  // | window counts [n]
+  size_t counters_at = 0, counts_at = 0, n_blocks_at = 0, n_cand_at = 0, n_win_at = 0, res_bytes = 0;
   struct Gvcf {
     int n = 0;
     size_t desc_up = 0;                           // the GvcfRegion descriptors in the staging image
@@ -66,11 +73,17 @@ struct BatchPlan {
     size_t desc_up = 0;                           // the CandRegion descriptors
     size_t scratch_ints = 0;
   } cd;
+  struct Win {
+    int n = 0;
+    size_t cand_desc_up = 0, desc_up = 0;         // the CandRegion and the WindowRegion descriptors, slot by slot
+    size_t scratch_ints = 0, windows = 0, mask_words = 0;
+  } win;
 };
 
-// `gv` / `co`: the optional passes (null = off).  read_keys may be null, and so may each of its entries.
+// `gv` / `co` / `wo`: the optional passes (null = off).  read_keys may be null, and so may each of its entries.
 inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
-                            const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co) {
+                            const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
+                            const dv_window_options* wo = nullptr) {
   BatchPlan plan;
   plan.regions.resize(static_cast<size_t>(n > 0 ? n : 0));
   Layout up;
@@ -102,15 +115,24 @@ inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_al
     p.cap = first_event_cap(b, n_refs);
     p.ev_off = plan.ev_total;
     plan.ev_total += p.cap;
-    if ((gv || co) && read_keys && read_keys[k]) {
+    if ((gv || co || wo) && read_keys && read_keys[k]) {
       p.has_keys = true;
       p.up.keys = up.add(nr * 4);
     }
-    if (gv || co) plan.max_cap = std::max(plan.max_cap, p.cap);
+    if (gv || co || wo) plan.max_cap = std::max(plan.max_cap, p.cap);
     if (co) {
       p.cd.slot = plan.cd.n++;
       p.cd.scratch_off = plan.cd.scratch_ints;
       plan.cd.scratch_ints += cand_scratch_ints(p.len, p.cap);
+    }
+    if (wo) {
+      p.win.slot = plan.win.n++;
+      p.win.scratch_off = plan.win.scratch_ints;
+      plan.win.scratch_ints += cand_scratch_ints(p.len, p.cap) + win_scratch_ints(p.len, p.cap);
+      p.win.window_off = plan.win.windows;
+      plan.win.windows += win_cap(p.len, wo->min_windows_distance);
+      p.win.mask_off = plan.win.mask_words;
+      plan.win.mask_words += mask_words(p.len);
     }
     if (gv) {
       p.gv.slot = plan.gv.n++;
@@ -123,21 +145,27 @@ inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_al
   }
   if (plan.gv.n) plan.gv.desc_up = up.add(static_cast<size_t>(plan.gv.n) * sizeof(GvcfRegion));
   if (plan.cd.n) plan.cd.desc_up = up.add(static_cast<size_t>(plan.cd.n) * sizeof(CandRegion));
+  if (plan.win.n) {
+    plan.win.cand_desc_up = up.add(static_cast<size_t>(plan.win.n) * sizeof(CandRegion));
+    plan.win.desc_up = up.add(static_cast<size_t>(plan.win.n) * sizeof(WindowRegion));
+  }
   plan.up_bytes = up.bytes();
   // the image's end is its last section's, unpadded
   Layout res;
   auto section = [&res](size_t bytes, bool last) { return last ? res.add_last(bytes) : res.add(bytes); };
   const size_t regions = plan.regions.size();
   plan.counters_at = res.add(regions * 4 * sizeof(uint32_t));
-  plan.counts_at = section(plan.cnt_ints * sizeof(int32_t), !gv && !co);
-  if (gv) plan.n_blocks_at = section(regions * sizeof(int32_t), !co);
-  if (co) plan.n_cand_at = res.add_last(regions * 2 * sizeof(int32_t));
+  plan.counts_at = section(plan.cnt_ints * sizeof(int32_t), !gv && !co && !wo);
+  if (gv) plan.n_blocks_at = section(regions * sizeof(int32_t), !co && !wo);
+  if (co) plan.n_cand_at = section(regions * 2 * sizeof(int32_t), !wo);
+  if (wo) plan.n_win_at = res.add_last(regions * sizeof(int32_t));
   plan.res_bytes = res.bytes();
   return plan;
 }
 
 // Where the second download lies in its pinned image, from the numbers the first one brought: region by region the
-// events, then the packed gVCF records, the event words region by region, the packed sites and the packed alleles.
+// events, then the packed gVCF records, the event words region by region, the packed sites and the packed alleles,
+// then the packed windows and -- with want_debug -- the scores and candidate masks of all batched regions.
 // The device packs the records of EVERY region that was planned into a pass, the overflowed ones' included (their
 // events exceeded `cap`; they go alone afterwards and `kept` is false): those records are skipped, not dropped.
 // Nothing here is padded: the image is read with memcpy only.
@@ -147,17 +175,22 @@ struct SecondImage {
     size_t n_events = 0, events_at = 0, words_at = 0;
     size_t n_blocks = 0, blocks_at = 0;
     size_t n_sites = 0, sites_at = 0, n_alleles = 0, alleles_at = 0;
+    size_t n_windows = 0, windows_at = 0;
   };
   std::vector<Region> regions;
   size_t packed_blocks = 0, blocks_at = 0;        // records of all regions of the pass, and where they start
   size_t packed_sites = 0, sites_at = 0;
   size_t packed_alleles = 0, alleles_at = 0;
+  size_t packed_windows = 0, windows_at = 0;      // two int64 each
+  size_t scores_at = 0, masks_at = 0;             // want_debug: [cnt_ints] words and [win.mask_words] words
   size_t bytes = 0;
 };
 
-// counters: [n][4] as the kernel leaves them; n_blocks: [n] (gVCF pass on); n_cand: [n][2] (candidate pass on).
+// counters: [n][4] as the kernel leaves them; n_blocks: [n] (gVCF pass on); n_cand: [n][2] (candidate pass on);
+// n_win: [n] (window pass on).
 inline SecondImage second_image(const BatchPlan& plan, const uint32_t* counters, const int32_t* n_blocks,
-                                const int32_t* n_cand, bool positions_only) {
+                                const int32_t* n_cand, bool positions_only, const int32_t* n_win = nullptr,
+                                bool window_debug = false) {
   SecondImage s;
   const size_t n = plan.regions.size();
   s.regions.resize(n);
@@ -173,6 +206,7 @@ inline SecondImage second_image(const BatchPlan& plan, const uint32_t* counters,
     if (p.gv.slot >= 0) s.packed_blocks += r.n_blocks = static_cast<size_t>(n_blocks[k]);
     if (p.cd.slot >= 0) s.packed_sites += r.n_sites = static_cast<size_t>(n_cand[2 * k]);
     if (p.cd.slot >= 0) s.packed_alleles += r.n_alleles = static_cast<size_t>(n_cand[2 * k + 1]);
+    if (p.win.slot >= 0) s.packed_windows += r.n_windows = static_cast<size_t>(n_win[k]);
   }
   s.blocks_at = lay.add_last(s.packed_blocks * sizeof(dv_gvcf_block));
   for (size_t k = 0; k < n; ++k) {                // the event words
@@ -181,8 +215,11 @@ inline SecondImage second_image(const BatchPlan& plan, const uint32_t* counters,
   }
   s.sites_at = lay.add_last(s.packed_sites * sizeof(dv_candidate_site));
   s.alleles_at = lay.add_last(positions_only ? 0 : s.packed_alleles * sizeof(dv_candidate_allele));
+  s.windows_at = lay.add_last(s.packed_windows * 2 * sizeof(int64_t));
+  s.scores_at = lay.add_last(window_debug ? plan.cnt_ints * sizeof(uint32_t) : 0);
+  s.masks_at = lay.add_last(window_debug ? plan.win.mask_words * sizeof(uint32_t) : 0);
   s.bytes = lay.bytes();
-  size_t blocks_at = s.blocks_at, sites_at = s.sites_at, alleles_at = s.alleles_at;
+  size_t blocks_at = s.blocks_at, sites_at = s.sites_at, alleles_at = s.alleles_at, windows_at = s.windows_at;
   for (SecondImage::Region& r : s.regions) {      // each region's records within the packed ones (none: nothing moves)
     r.blocks_at = blocks_at;
     r.sites_at = sites_at;
@@ -190,6 +227,8 @@ inline SecondImage second_image(const BatchPlan& plan, const uint32_t* counters,
     blocks_at += r.n_blocks * sizeof(dv_gvcf_block);
     sites_at += r.n_sites * sizeof(dv_candidate_site);
     alleles_at += r.n_alleles * sizeof(dv_candidate_allele);
+    r.windows_at = windows_at;
+    windows_at += r.n_windows * 2 * sizeof(int64_t);
   }
   return s;
 }

@@ -48,6 +48,10 @@ int cand_launch(const CandRegion* d_regions, int32_t n, uint32_t max_events,
                 const dv_candidate_options* c, dv_candidate_site* packed_sites, dv_candidate_allele* packed_alleles,
                 hipStream_t stream);
 
+// The first three launches only (link, resolve, group), for a pass that reads the standing flags, the positions'
+// good non-reference totals and the allele groups out of the scratch (cand_slices.h): window_select.hip.
+int cand_group_launch(const CandRegion* d_regions, int32_t n, uint32_t max_events, hipStream_t stream);
+
 }  // namespace dv
 
 #endif  // DV_CANDIDATES_H_

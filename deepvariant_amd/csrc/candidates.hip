@@ -20,6 +20,7 @@
 // division and comparison per allele, so the selection equals the host restatement's exactly.
 #include <algorithm>
 
+#include "cand_slices.h"
 #include "candidates.h"
 #include "event_lists.h"
 
@@ -39,24 +40,8 @@ __device__ __forceinline__ uint32_t type_of(const dv_allele_event& ev) { return 
 __device__ __forceinline__ uint32_t length_of(const dv_allele_event& ev) { return ev.length_type & 0x0fffffffu; }
 __device__ __forceinline__ bool low_quality(const dv_allele_event& ev) { return (ev.length_type >> 31) != 0; }
 
-// scratch slices (dv::cand_scratch_ints)
-struct Slices {
-  int32_t *head, *alt, *nsel;                    // per position
-  int32_t *next, *stands, *rep, *count, *sel;    // per event
-};
-__device__ __forceinline__ Slices slices(const dv::CandRegion& g) {
-  const size_t len = static_cast<size_t>(g.len), cap = g.event_cap;
-  Slices s;
-  s.head = g.scratch;
-  s.alt = s.head + len;
-  s.nsel = s.alt + len;
-  s.next = s.nsel + len;
-  s.stands = s.next + cap;
-  s.rep = s.stands + cap;
-  s.count = s.rep + cap;
-  s.sel = s.count + cap;
-  return s;
-}
+using Slices = dv::CandSlices;
+__device__ __forceinline__ Slices slices(const dv::CandRegion& g) { return dv::cand_slices(g); }
 
 __device__ __forceinline__ uint32_t n_events(const dv::CandRegion& g) {
   const uint32_t n = *g.n_events;
@@ -285,6 +270,20 @@ int cand_check_options(const dv_candidate_options* c, const char* who) {
       !(c->min_fraction_indels >= 0.0f)) {
     return fail(DV_ERR_INVALID_ARGUMENT, name + ": candidate thresholds must be >= 0");
   }
+  return DV_OK;
+}
+
+int cand_group_launch(const CandRegion* d_regions, int32_t n, uint32_t max_events, hipStream_t stream) {
+  if (n <= 0 || max_events == 0) return DV_OK;
+  const unsigned ev_blocks =
+      static_cast<unsigned>(std::min<int64_t>((static_cast<int64_t>(max_events) + kThreads - 1) / kThreads, 1024));
+  const dim3 ev_grid(ev_blocks, static_cast<unsigned>(n));
+  const dv_candidate_options none{};           // the selection (sel, nsel) is of no use to the caller
+  ProfileScope prof(kProfOther, stream);
+  hipLaunchKernelGGL(cand_link_kernel, ev_grid, dim3(kThreads), 0, stream, d_regions);
+  hipLaunchKernelGGL(cand_resolve_kernel, ev_grid, dim3(kThreads), 0, stream, d_regions);
+  hipLaunchKernelGGL(cand_group_kernel, ev_grid, dim3(kThreads), 0, stream, d_regions, none);
+  DV_HIP_CHECK(hipGetLastError());
   return DV_OK;
 }
 

@@ -12,6 +12,7 @@ numpy.  There is no CPU counting path."""
 from __future__ import annotations
 
 import dataclasses
+import os
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -234,6 +235,12 @@ def select_windows(config: WindowSelectorOptions, ref_reader, reads: Sequence, r
   return _candidates_to_windows(config, candidates, region.reference_name)
 
 
+def windows_on_device() -> bool:
+  """DV_WINDOWS_DEVICE=1: `select_windows_of_tables` scores the positions and merges the windows on the device,
+  behind the allele counter.  Off by default."""
+  return os.environ.get('DV_WINDOWS_DEVICE', '') == '1'
+
+
 def select_windows_of_tables(config: WindowSelectorOptions, ref_reader, tables: Sequence, regions: Sequence[T.Range]
                              ) -> List[List[T.Range]]:
   """`select_windows` for the packed read tables of several calling regions: the regions' allele
@@ -247,6 +254,13 @@ def select_windows_of_tables(config: WindowSelectorOptions, ref_reader, tables: 
     if table.n_reads:
       jobs.append((k, region) + _make_counter(config, ref_reader, (), region, table=table))
   run_batch = getattr(allelecounter.AlleleCounter, 'run_batch', None)
+  if windows_on_device() and run_batch is not None:
+    # candidates and windows on the device too (window_select.hip): only the windows come home
+    run_batch([job[2] for job in jobs], windows=config)
+    for k, region, counter, _ in jobs:
+      starts, ends = counter.windows(config)
+      out[k] = [utils.make_range(region.reference_name, int(s), int(e)) for s, e in zip(starts, ends)]
+    return out
   if run_batch is not None:
     run_batch([job[2] for job in jobs])
   for k, region, counter, expanded in jobs:

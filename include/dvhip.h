@@ -1415,6 +1415,58 @@ int64_t dv_candidates_arrays(const dv_candidates* c, const dv_candidate_site** s
                              uint32_t* n_events);
 void dv_candidates_free(dv_candidates* c);
 
+/* ---- realigner window selection (device) ----------------------------------------
+ * select_windows of the reference's deepvariant/realigner/window_selector.py:40-238 over
+ * VariantReadsWindowSelectorCandidates / AlleleCountLinearWindowSelectorCandidates
+ * (window_selector.cc:101-207), computed behind the allele counter from the counts and events where
+ * they lie on the device.  Per interval position the later event of one read key stands (as for the
+ * candidate caller).  A standing event at offset i covers [i, i+1) (substitution, REFERENCE),
+ * [i+1-n, i+1+n) (insertion or soft clip of n bases) or [i+1, i+1+n) (deletion of n bases), clipped
+ * to the interval.
+ *   VARIANT_READS: a good-quality non-REFERENCE standing event adds 1 over its footprint when its
+ *     allele (type, text) has >= min_allele_support good events and, with
+ *     enable_strict_insertion_filter and an insertion of at most one base,
+ *     (double)((float)count / (float)total) >= 0.08, total = the position's good non-REFERENCE
+ *     standing events + ref_supporting_read_count.  Candidate: min <= count <= max.
+ *   ALLELE_COUNT_LINEAR: float32, summed in the reference's order, one round-to-nearest operation
+ *     per step: score[j] = (float)bias; + coeff[type] for every standing event (low-quality and
+ *     REFERENCE ones included) of positions i < j that covers j, in ascending i and within one
+ *     position in the order of the first event of each read key; + (float)ref_count[j] *
+ *     coeff_reference; + the same for positions i >= j.  Candidate: (double)score > decision_boundary.
+ * Candidates more than 2 * min_windows_distance apart start a new window; a window is
+ * [first - d, last + d) in contig coordinates, not clamped to the contig. */
+#define DV_WINDOW_MODEL_VARIANT_READS 1
+#define DV_WINDOW_MODEL_ALLELE_COUNT_LINEAR 2
+
+typedef struct dv_window_options {
+  int32_t model_type;                 /* DV_WINDOW_MODEL_* */
+  int32_t min_num_supporting_reads, max_num_supporting_reads;   /* VARIANT_READS; max >= min whatever the model */
+  int32_t min_allele_support;
+  int32_t enable_strict_insertion_filter;
+  float bias, coeff_soft_clip, coeff_substitution, coeff_insertion, coeff_deletion, coeff_reference;
+  int32_t min_windows_distance;       /* d, >= 0 */
+  double decision_boundary;
+  int32_t want_debug;                 /* also bring home the candidate mask and the scores (for tests) */
+  int32_t reserved;
+} dv_window_options;
+
+typedef struct dv_windows dv_windows;   /* owns the host copies of one region's result */
+
+/* The windows of every region from one device pass behind the counting kernels.  read_keys as for
+ * dv_count_alleles_gvcf_batch.  windows_out[k] receives region k's windows (freed with
+ * dv_windows_free).  counts_out may be NULL: then neither counts nor events come home, only the
+ * windows; otherwise it is filled as by dv_count_alleles_batch.  An unknown model type, max < min
+ * or a negative distance is DV_ERR_INVALID_ARGUMENT; on an error no result is left allocated. */
+int dv_select_windows_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
+                            const int32_t* const* read_keys, const dv_window_options* window_options,
+                            dv_allele_counts** counts_out, dv_windows** windows_out, void* stream);
+/* -> the number of windows; starts / ends in contig coordinates, end exclusive.  With want_debug,
+ * candidate_mask holds one bit per interval position (bit p & 31 of word p >> 5) and scores one word
+ * per position: the float32 score, or for VARIANT_READS the count as int32; both NULL otherwise. */
+int64_t dv_windows_arrays(const dv_windows* w, const int64_t** starts, const int64_t** ends,
+                          const uint32_t** candidate_mask, const uint32_t** scores);
+void dv_windows_free(dv_windows* w);
+
 /* CRC32C (Castagnoli) as used by TFRecord framing
  * (third_party/nucleus/io/example_writer.cc:88-104 via tensorflow::io::RecordWriter). */
 uint32_t dv_crc32c(const uint8_t* data, size_t n);

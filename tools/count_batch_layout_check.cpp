@@ -2,7 +2,9 @@
 // against a transcription of the hand-kept offset arithmetic they replaced in allele_counter.hip's batch entry point:
 // every offset and total of the staging image, the result image and the second download, over region counts {0, 1, 3},
 // table sizes and interval lengths from {0, 1, 15, 16, 17, 1000}, with and without candidate positions, read keys, the
-// gVCF pass, the candidate pass and positions_only, and every subset of regions overflowing its first guess.
+// gVCF pass, the candidate pass, positions_only and the window pass (with and without counts, at window distances 0
+// and 80, with and without the debug arrays), and every subset of regions overflowing its first guess.  The window
+// pass' sections came after the hand-kept arithmetic: they are held against a second statement of them here.
 // Host arithmetic only: no HIP call is made and no device is needed.  Not part of the library's build:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Iinclude -Ideepvariant_amd/csrc \
 //       tools/count_batch_layout_check.cpp -o /tmp/count_batch_layout_check && /tmp/count_batch_layout_check
@@ -31,6 +33,8 @@ struct OldPlan {
   int gv_slot = -1;
   int cd_slot = -1;
   size_t cscr_off = 0;
+  int win_slot = -1;
+  size_t wscr_off = 0, wwin_off = 0, wmask_off = 0;
 };
 
 struct OldTotals {
@@ -41,11 +45,13 @@ struct OldTotals {
   uint32_t max_cap = 0;
   size_t desc_up = 0, cdesc_up = 0;
   size_t ctr_bytes = 0, nblk_off = 0, ncand_off = 0, res_bytes = 0;
+  int n_win = 0;
+  size_t wscr_ints = 0, win_total = 0, wmask_total = 0, wcdesc_up = 0, wdesc_up = 0, nwin_off = 0;
 };
 
 OldTotals old_plan(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                    const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
-                   std::vector<OldPlan>* plan) {
+                   const dv_window_options* wo, std::vector<OldPlan>* plan) {
   OldTotals t;
   plan->assign(static_cast<size_t>(n), OldPlan());
   for (int32_t k = 0; k < n; ++k) {
@@ -75,7 +81,7 @@ OldTotals old_plan(int32_t n, const dv_batch* const* reads, const dv_allele_coun
     p.cap = b->n_cigar + b->n_bases / 16 + 4096 + static_cast<uint32_t>(std::min<size_t>(n_candidate_refs * 64, 1u << 24));
     p.ev_off = t.ev_total;
     t.ev_total += p.cap;
-    if ((gv || co) && read_keys && read_keys[k]) {
+    if ((gv || co || wo) && read_keys && read_keys[k]) {
       p.key_up = t.up_bytes;
       t.up_bytes += align16(nr * 4);
     }
@@ -84,6 +90,20 @@ OldTotals old_plan(int32_t n, const dv_batch* const* reads, const dv_allele_coun
       ++t.n_cd;
       p.cscr_off = t.cscr_ints;
       t.cscr_ints += dv::cand_scratch_ints(p.len, p.cap);
+      t.max_cap = std::max(t.max_cap, p.cap);
+    }
+    if (wo) {
+      p.win_slot = t.n_win;
+      ++t.n_win;
+      p.wscr_off = t.wscr_ints;
+      // the candidate kernels' eight slices, then two per position, six per event and the record count
+      t.wscr_ints += 3 * static_cast<size_t>(p.len) + 5 * static_cast<size_t>(p.cap) + 2 * static_cast<size_t>(p.len) +
+                     6 * static_cast<size_t>(p.cap) + 4;
+      p.wwin_off = t.win_total;
+      const int64_t step = 2 * static_cast<int64_t>(wo->min_windows_distance) + 1;
+      t.win_total += static_cast<size_t>((p.len + step - 1) / step);
+      p.wmask_off = t.wmask_total;
+      t.wmask_total += static_cast<size_t>((p.len + 31) / 32);
       t.max_cap = std::max(t.max_cap, p.cap);
     }
     if (gv) {
@@ -101,11 +121,17 @@ OldTotals old_plan(int32_t n, const dv_batch* const* reads, const dv_allele_coun
   if (t.n_gv) t.up_bytes += align16(static_cast<size_t>(t.n_gv) * sizeof(dv::GvcfRegion));
   t.cdesc_up = t.up_bytes;
   if (t.n_cd) t.up_bytes += align16(static_cast<size_t>(t.n_cd) * sizeof(dv::CandRegion));
+  t.wcdesc_up = t.up_bytes;
+  if (t.n_win) t.up_bytes += align16(static_cast<size_t>(t.n_win) * sizeof(dv::CandRegion));
+  t.wdesc_up = t.up_bytes;
+  if (t.n_win) t.up_bytes += align16(static_cast<size_t>(t.n_win) * sizeof(dv::WindowRegion));
   t.ctr_bytes = align16(static_cast<size_t>(n) * 4 * sizeof(uint32_t));
   t.nblk_off = align16(t.ctr_bytes + t.cnt_ints * sizeof(int32_t));
   t.res_bytes = gv ? t.nblk_off + static_cast<size_t>(n) * sizeof(int32_t) : t.ctr_bytes + t.cnt_ints * sizeof(int32_t);
   t.ncand_off = align16(t.res_bytes);
   if (co) t.res_bytes = t.ncand_off + static_cast<size_t>(n) * 2 * sizeof(int32_t);
+  t.nwin_off = align16(t.res_bytes);
+  if (wo) t.res_bytes = t.nwin_off + static_cast<size_t>(n) * sizeof(int32_t);
   return t;
 }
 
@@ -113,15 +139,17 @@ OldTotals old_plan(int32_t n, const dv_batch* const* reads, const dv_allele_coun
 struct OldSecond {
   struct Region {
     bool kept = false;
-    size_t n_ev = 0, ev_at = 0, words_at = 0, sites_at = 0, alleles_at = 0, blocks_at = 0;
+    size_t n_ev = 0, ev_at = 0, words_at = 0, sites_at = 0, alleles_at = 0, blocks_at = 0, windows_at = 0;
   };
   std::vector<Region> regions;
   size_t packed_blocks = 0, packed_at = 0, words_at = 0, packed_sites = 0, sites_at = 0, packed_alleles = 0,
          alleles_at = 0, ev_bytes = 0;
+  size_t packed_windows = 0, windows_at = 0, scores_at = 0, masks_at = 0;
 };
 
 OldSecond old_second(int32_t n, std::vector<OldPlan> plan, const uint32_t* ctrs, const int32_t* nblk, const int32_t* ncand,
-                     bool gv, bool co, bool pos_only) {
+                     bool gv, bool co, bool pos_only, const int32_t* nwin, bool win_debug, size_t cnt_ints,
+                     size_t wmask_total) {
   OldSecond s;
   s.regions.resize(static_cast<size_t>(n));
   size_t ev_bytes = 0;
@@ -157,6 +185,17 @@ OldSecond old_second(int32_t n, std::vector<OldPlan> plan, const uint32_t* ctrs,
   ev_bytes += s.packed_sites * sizeof(dv_candidate_site);
   s.alleles_at = ev_bytes;
   if (!pos_only) ev_bytes += s.packed_alleles * sizeof(dv_candidate_allele);
+  s.windows_at = ev_bytes;
+  for (int32_t k = 0; k < n; ++k) {
+    if (plan[k].win_slot < 0) continue;
+    s.regions[k].windows_at = s.windows_at + s.packed_windows * 16;
+    s.packed_windows += static_cast<size_t>(nwin[k]);
+  }
+  ev_bytes += s.packed_windows * 16;
+  s.scores_at = ev_bytes;
+  if (win_debug) ev_bytes += cnt_ints * 4;
+  s.masks_at = ev_bytes;
+  if (win_debug) ev_bytes += wmask_total * 4;
   s.ev_bytes = ev_bytes;
   // the copies' walk
   size_t at = 0, wat = s.words_at;
@@ -204,12 +243,13 @@ long mismatches = 0, cases = 0;
   } while (0)
 
 void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
-             const int32_t* const* keys, const dv_gvcf_options* gv, const dv_candidate_options* co, unsigned overflowed) {
+             const int32_t* const* keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
+             const dv_window_options* wo, bool with_counts, unsigned overflowed) {
   ++cases;
-  const bool pos_only = co && co->positions_only;
+  const bool pos_only = (co && co->positions_only) || (wo && !with_counts);
   std::vector<OldPlan> old;
-  const OldTotals t = old_plan(n, reads, options, keys, gv, co, &old);
-  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, keys, gv, co);
+  const OldTotals t = old_plan(n, reads, options, keys, gv, co, wo, &old);
+  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, keys, gv, co, wo);
   SAME(plan.regions.size(), old.size());
   SAME(plan.n_batched, t.n_batched);
   SAME(plan.up_bytes, t.up_bytes);
@@ -233,6 +273,15 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
     SAME(plan.cd.scratch_ints, t.cscr_ints);
     if (t.n_cd) SAME(plan.cd.desc_up, t.cdesc_up);
   }
+  SAME(plan.win.n, t.n_win);
+  if (wo) {
+    SAME(plan.n_win_at, t.nwin_off);
+    SAME(plan.win.scratch_ints, t.wscr_ints);
+    SAME(plan.win.windows, t.win_total);
+    SAME(plan.win.mask_words, t.wmask_total);
+    if (t.n_win) SAME(plan.win.cand_desc_up, t.wcdesc_up);
+    if (t.n_win) SAME(plan.win.desc_up, t.wdesc_up);
+  }
   for (size_t k = 0; k < old.size(); ++k) {
     const dv::RegionPlan& p = plan.regions[k];
     const OldPlan& q = old[k];
@@ -250,7 +299,7 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
     SAME(p.up.ref, q.up[7]);
     SAME(p.mask_words, q.mask_words);
     if (q.mask_words) SAME(p.up.mask, q.up[8]);
-    const bool has_keys = (gv || co) && keys && keys[k];
+    const bool has_keys = (gv || co || wo) && keys && keys[k];
     SAME(p.has_keys, has_keys);
     if (has_keys) SAME(p.up.keys, q.key_up);
     SAME(p.cnt_off, q.cnt_off);
@@ -262,10 +311,17 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
       SAME(p.gv.block_off, q.blk_off);
     }
     if (co) SAME(p.cd.scratch_off, q.cscr_off);
+    SAME(p.win.slot, q.win_slot);
+    if (wo) {
+      SAME(p.win.scratch_off, q.wscr_off);
+      SAME(p.win.window_off, q.wwin_off);
+      SAME(p.win.mask_off, q.wmask_off);
+    }
   }
   // what the first download would bring: event counts within or beyond the first guess, some records everywhere
   std::vector<uint32_t> ctrs(static_cast<size_t>(n) * 4 + 4, 0);
   std::vector<int32_t> nblk(static_cast<size_t>(n) + 1, 0), ncand(static_cast<size_t>(n) * 2 + 2, 0);
+  std::vector<int32_t> nwin(static_cast<size_t>(n) + 1, 0);
   for (int32_t k = 0; k < n; ++k) {
     const uint32_t cap = old[k].cap;
     ctrs[4 * k] = (overflowed >> k) & 1 ? cap + 1 + 7 * k : (cap / 3 + 5 * k) % (cap + 1);
@@ -274,9 +330,12 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
     nblk[k] = 2 + 3 * k;
     ncand[2 * k] = k == 2 ? 0 : 5 + k;
     ncand[2 * k + 1] = 11 - 4 * k;
+    nwin[k] = k == 1 ? 0 : 4 - k;
   }
-  const OldSecond s = old_second(n, old, ctrs.data(), nblk.data(), ncand.data(), gv != nullptr, co != nullptr, pos_only);
-  const dv::SecondImage im = dv::second_image(plan, ctrs.data(), nblk.data(), ncand.data(), pos_only);
+  const bool win_debug = wo && wo->want_debug;
+  const OldSecond s = old_second(n, old, ctrs.data(), nblk.data(), ncand.data(), gv != nullptr, co != nullptr, pos_only,
+                                 nwin.data(), win_debug, t.cnt_ints, t.wmask_total);
+  const dv::SecondImage im = dv::second_image(plan, ctrs.data(), nblk.data(), ncand.data(), pos_only, nwin.data(), win_debug);
   SAME(im.regions.size(), s.regions.size());
   SAME(im.bytes, s.ev_bytes);
   SAME(im.packed_blocks, s.packed_blocks);
@@ -285,6 +344,12 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
   if (s.packed_blocks) SAME(im.blocks_at, s.packed_at);
   if (s.packed_sites) SAME(im.sites_at, s.sites_at);
   if (s.packed_alleles && !pos_only) SAME(im.alleles_at, s.alleles_at);
+  SAME(im.packed_windows, s.packed_windows);
+  if (s.packed_windows) SAME(im.windows_at, s.windows_at);
+  if (win_debug) {
+    SAME(im.scores_at, s.scores_at);
+    SAME(im.masks_at, s.masks_at);
+  }
   for (size_t k = 0; k < s.regions.size(); ++k) {
     const dv::SecondImage::Region& r = im.regions[k];
     const OldSecond::Region& q = s.regions[k];
@@ -298,6 +363,10 @@ void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_op
       SAME(r.n_alleles, ncand[2 * k + 1]);
       SAME(r.sites_at, q.sites_at);
       if (!pos_only) SAME(r.alleles_at, q.alleles_at);
+    }
+    if (old[k].win_slot >= 0) {
+      SAME(r.n_windows, nwin[k]);
+      SAME(r.windows_at, q.windows_at);
     }
     if (!q.kept || pos_only) continue;
     SAME(r.n_events, q.n_ev);
@@ -316,11 +385,21 @@ int main() {
   gvcf.right_padding = 0;
   dv_candidate_options calls{}, positions{};
   positions.positions_only = 1;
+  dv_window_options near{}, far{}, debug{};
+  near.model_type = far.model_type = debug.model_type = DV_WINDOW_MODEL_ALLELE_COUNT_LINEAR;
+  far.min_windows_distance = 80;
+  debug.min_windows_distance = 4;
+  debug.want_debug = 1;
   struct Mode {
     const dv_gvcf_options* gv;
     const dv_candidate_options* co;
+    const dv_window_options* wo;
+    bool with_counts;
   };
-  const Mode modes[5] = {{nullptr, nullptr}, {&gvcf, nullptr}, {nullptr, &calls}, {&gvcf, &calls}, {nullptr, &positions}};
+  const Mode modes[9] = {{nullptr, nullptr, nullptr, true}, {&gvcf, nullptr, nullptr, true}, {nullptr, &calls, nullptr, true},
+                         {&gvcf, &calls, nullptr, true}, {nullptr, &positions, nullptr, true},
+                         {nullptr, nullptr, &near, false}, {nullptr, nullptr, &far, false}, {nullptr, nullptr, &debug, false},
+                         {nullptr, nullptr, &debug, true}};
   for (int n : {0, 1, 3}) {
     for (int combo = 0; combo < 6 * 6 * 6 * 6; ++combo) {
       for (int n_positions = 0; n_positions < 2; ++n_positions) {
@@ -352,7 +431,7 @@ int main() {
           }
           for (const Mode& m : modes) {
             for (unsigned overflowed = 0; overflowed < (1u << n); ++overflowed) {
-              compare(n, reads, options, with_keys ? keys : nullptr, m.gv, m.co, overflowed);
+              compare(n, reads, options, with_keys ? keys : nullptr, m.gv, m.co, m.wo, m.with_counts, overflowed);
             }
           }
         }
