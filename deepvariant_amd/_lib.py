@@ -69,7 +69,7 @@ ABI_SYMBOLS = [
     'dv_count_alleles', 'dv_count_alleles_batch', 'dv_allele_counts_arrays', 'dv_allele_counts_free', 'dv_merge_alt_channels',
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
     'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
-    'dv_select_windows_batch', 'dv_windows_arrays', 'dv_windows_free',
+    'dv_select_windows_batch', 'dv_windows_arrays', 'dv_windows_free', 'dv_count_batch_last_stats',
 ]
 
 
@@ -450,6 +450,12 @@ class DvWindowOptions(C.Structure):
               ('want_debug', C.c_int32), ('reserved', C.c_int32)]
 
 
+class DvCountBatchStats(C.Structure):
+  # include/dvhip.h dv_count_batch_stats
+  _fields_ = [('regions', C.c_int32), ('regions_batched', C.c_int32), ('regions_alone', C.c_int32),
+              ('count_launches', C.c_int32), ('count_workgroups', C.c_int64)]
+
+
 class DvCandidateSite(C.Structure):
   _fields_ = [('offset', C.c_int32), ('ref_count', C.c_int32), ('total', C.c_int32),
               ('first_allele', C.c_int32), ('n_alleles', C.c_int32)]
@@ -657,6 +663,7 @@ def lib():
     l.dv_windows_arrays.argtypes = [C.c_void_p] * 5
     l.dv_windows_free.argtypes = [C.c_void_p]
     l.dv_windows_free.restype = None
+    l.dv_count_batch_last_stats.argtypes = [C.c_void_p]
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -20,7 +20,9 @@ only the candidate positions' alleles are built here; variant_calling.VariantCal
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -40,6 +42,23 @@ CANDIDATE_SITE_DTYPE = np.dtype([('offset', '<i4'), ('ref_count', '<i4'), ('tota
 CANDIDATE_ALLELE_DTYPE = np.dtype([('length_type', '<u4'), ('count', '<i4'), ('read', '<u4'),
                                    ('read_offset', '<u4')])   # dv_candidate_allele
 EVENT_UNCALLED, EVENT_OVERWRITTEN = -1, -2                  # DV_CANDIDATE_EVENT_*
+
+
+BatchStats = collections.namedtuple('BatchStats', 'regions regions_batched regions_alone count_launches count_workgroups')
+
+
+def count_one_launch() -> bool:
+  """DV_COUNT_ONE_LAUNCH=1: every batch entry point (`run_batch` in all its forms) counts its batched regions in one
+  kernel launch instead of one launch per region.  The library reads the switch at each call; results do not depend
+  on it.  Off by default."""
+  return os.environ.get('DV_COUNT_ONE_LAUNCH', '') == '1'
+
+
+def last_batch_stats() -> BatchStats:
+  """dv_count_batch_last_stats of the calling thread: how the last batch call's counting was launched."""
+  s = _lib.DvCountBatchStats()
+  _lib.check(_lib.lib().dv_count_batch_last_stats(C.byref(s)))
+  return BatchStats(s.regions, s.regions_batched, s.regions_alone, s.count_launches, s.count_workgroups)
 
 
 class Allele:

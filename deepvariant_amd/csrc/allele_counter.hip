@@ -78,27 +78,7 @@ namespace {
 enum : int { kRef = 1, kSub = 2, kIns = 3, kDel = 4, kSoft = 5 };   // AlleleType
 enum : int { opM = 1, opI = 2, opD = 3, opN = 4, opS = 5, opH = 6, opP = 7, opEQ = 8, opX = 9 };
 
-struct CountArgs {
-  int32_t n_reads;
-  const int32_t* read_pos;
-  const uint32_t* seq_off;
-  const uint32_t* cigar_off;
-  const uint8_t* mapq;
-  const uint8_t* bases;
-  const uint8_t* quals;
-  const uint32_t* cigar;
-  const uint8_t* ref;        // reference bases of [ref_start, ref_start + n_ref)
-  int64_t ref_start, n_ref;
-  int64_t reads_start, reads_end;   // IsValidRefOffset: the reads interval
-  int64_t interval_start, interval_len;
-  int64_t contig_len;
-  int32_t min_mapq, min_bq, legacy;
-  int32_t* ref_count;        // [interval_len]
-  const uint32_t* candidate_mask;   // track_ref_reads: bit p set = keep the reference reads of position p by name
-  dv_allele_event* events;
-  uint32_t event_cap;
-  uint32_t* counters;        // [0] events wanted, [1] reads counted, [2] reference window too small
-};
+using dv::CountArgs;
 
 __device__ __forceinline__ bool canonical(uint8_t b) { return b == 'A' || b == 'C' || b == 'G' || b == 'T'; }
 
@@ -276,10 +256,12 @@ __device__ __forceinline__ void count_read(const CountArgs& a, uint32_t r, int l
   if (pending.have && lane == 0) emit(a, r, pending, window, window_start);
 }
 
-__global__ __launch_bounds__(256) void count_alleles_kernel(CountArgs a) {
-  __shared__ BlockState bs;
+static_assert(4 * kReadsPerWave == dv::kCountReadsPerBlock, "the plan counts workgroups of 64 reads");
+
+// What one workgroup does for the 64 reads of region `a` that start at read `first` (first < a.n_reads): both
+// kernels' whole body.  `a` is the workgroup's own copy of the descriptor.
+__device__ __forceinline__ void count_block(const CountArgs& a, uint32_t first, BlockState& bs) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t first = blockIdx.x * (4 * kReadsPerWave);
   for (int i = threadIdx.x; i < kWindow; i += 256) bs.window[i] = 0;
   if (threadIdx.x == 0) bs.n_events = bs.n_reads = 0;
   const int64_t window_start = a.read_pos[first];      // reads arrive position-sorted (BAM order)
@@ -304,6 +286,33 @@ __global__ __launch_bounds__(256) void count_alleles_kernel(CountArgs a) {
     const uint32_t slot = bs.event_base + i;
     if (slot < a.event_cap) a.events[slot] = bs.events[i];
   }
+}
+
+// One region per launch: dv_count_alleles, the regions of a batch that go alone, and a batch without the switch.
+__global__ __launch_bounds__(256) void count_alleles_kernel(CountArgs a) {
+  __shared__ BlockState bs;
+  count_block(a, blockIdx.x * (4 * kReadsPerWave), bs);
+}
+
+// Every batched region of a call in one grid (DV_COUNT_ONE_LAUNCH).  block_first[s] is the first workgroup of slot
+// s, ascending, block_first[n_slots] the grid; a slot has ceil(n_reads / 64) >= 1 workgroups.  The workgroup finds
+// its slot by upper-bound bisection -- the same loads and branches on every lane, so the search and the descriptor
+// it leads to stay in scalar registers -- and copies the descriptor once: nothing below reads the table again.
+__global__ __launch_bounds__(256) void count_alleles_batch_kernel(const CountArgs* regions, const uint32_t* block_first,
+                                                                  int32_t n_slots) {
+  __shared__ BlockState bs;
+  const uint32_t block = blockIdx.x;
+  int32_t lo = 0, hi = n_slots;                        // block_first[lo] <= block < block_first[hi]
+  while (hi - lo > 1) {
+    const int32_t mid = lo + (hi - lo) / 2;
+    if (block_first[mid] <= block) {
+      lo = mid;
+    } else {
+      hi = mid;
+    }
+  }
+  const CountArgs a = regions[lo];
+  count_block(a, (block - block_first[lo]) * (4 * kReadsPerWave), bs);
 }
 
 template <typename T>
@@ -872,8 +881,30 @@ struct BatchBuffers {
   }
 };
 
-// Region k's arrays into the staging image, and its descriptors for the passes it is in: they point into the
-// device images, at the counts, events and reference the counter uses.
+// The counting kernel's arguments for region k of the batch.
+CountArgs batch_count_args(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, const BatchBuffers& buf) {
+  const dv::RegionPlan& p = plan.regions[k];
+  void* dup = buf.d_up.ptr;
+  CountArgs a = fill_count_args(rq.reads[k], rq.options[k], p.len);
+  a.read_pos = at<const int32_t>(dup, p.up.read_pos);
+  a.seq_off = at<const uint32_t>(dup, p.up.seq_off);
+  a.cigar_off = at<const uint32_t>(dup, p.up.cigar_off);
+  a.mapq = at<const uint8_t>(dup, p.up.mapq);
+  a.bases = at<const uint8_t>(dup, p.up.bases);
+  a.quals = at<const uint8_t>(dup, p.up.quals);
+  a.cigar = at<const uint32_t>(dup, p.up.cigar);
+  a.ref = at<const uint8_t>(dup, p.up.ref);
+  a.candidate_mask = p.mask_words ? at<const uint32_t>(dup, p.up.mask) : nullptr;
+  a.counters = at<uint32_t>(buf.d_res.ptr, plan.counters_at) + static_cast<size_t>(k) * 4;
+  a.ref_count = at<int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off;
+  a.events = static_cast<dv_allele_event*>(buf.d_ev.ptr) + p.ev_off;
+  a.event_cap = p.cap;
+  return a;
+}
+
+// Region k's arrays into the staging image, its entry of the one-launch kernel's table where the plan has one, and
+// its descriptors for the passes it is in: they point into the device images, at the counts, events and reference
+// the counter uses.  Results are indexed by region k, descriptor tables by the region's slot among the batched ones.
 void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, const BatchBuffers& buf) {
   const dv::RegionPlan& p = plan.regions[k];
   const dv_batch* b = rq.reads[k];
@@ -890,6 +921,10 @@ void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, 
   std::memcpy(host + p.up.ref, o->ref_bases, static_cast<size_t>(o->n_ref_bases));
   if (p.mask_words) build_candidate_mask(o, p.len, at<uint32_t>(host, p.up.mask));
   if (p.has_keys) std::memcpy(host + p.up.keys, rq.keys_of(k), nr * 4);
+  if (plan.cnt.one_launch) {
+    const CountArgs a = batch_count_args(rq, plan, k, buf);
+    std::memcpy(host + plan.cnt.args_up + static_cast<size_t>(p.count_slot) * sizeof(a), &a, sizeof(a));
+  }
   if (p.gv.slot < 0 && p.cd.slot < 0 && p.win.slot < 0) return;
   void* dup = buf.d_up.ptr;
   const CountsOnDevice c{at<const int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off,
@@ -927,34 +962,22 @@ void stage_region(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, 
   }
 }
 
-// The counting kernel's arguments for region k of the batch.
-CountArgs batch_count_args(const BatchRequest& rq, const dv::BatchPlan& plan, int32_t k, const BatchBuffers& buf) {
-  const dv::RegionPlan& p = plan.regions[k];
-  void* dup = buf.d_up.ptr;
-  CountArgs a = fill_count_args(rq.reads[k], rq.options[k], p.len);
-  a.read_pos = at<const int32_t>(dup, p.up.read_pos);
-  a.seq_off = at<const uint32_t>(dup, p.up.seq_off);
-  a.cigar_off = at<const uint32_t>(dup, p.up.cigar_off);
-  a.mapq = at<const uint8_t>(dup, p.up.mapq);
-  a.bases = at<const uint8_t>(dup, p.up.bases);
-  a.quals = at<const uint8_t>(dup, p.up.quals);
-  a.cigar = at<const uint32_t>(dup, p.up.cigar);
-  a.ref = at<const uint8_t>(dup, p.up.ref);
-  a.candidate_mask = p.mask_words ? at<const uint32_t>(dup, p.up.mask) : nullptr;
-  a.counters = at<uint32_t>(buf.d_res.ptr, plan.counters_at) + static_cast<size_t>(k) * 4;
-  a.ref_count = at<int32_t>(buf.d_res.ptr, plan.counts_at) + p.cnt_off;
-  a.events = static_cast<dv_allele_event*>(buf.d_ev.ptr) + p.ev_off;
-  a.event_cap = p.cap;
-  return a;
-}
-
-// One upload, the counting kernels back to back, the passes behind them; no synchronisation.
+// One upload, the counting kernels back to back -- or, where the plan holds their table, the one kernel that
+// covers every batched region -- and the passes behind them; no synchronisation.
 int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const BatchBuffers& buf,
-                     const dv_gvcf_site** d_table) {
+                     const dv_gvcf_site** d_table, dv_count_batch_stats* stats) {
   hipStream_t stream = rq.stream;
+  uint32_t* block_first = plan.cnt.one_launch ? at<uint32_t>(buf.h_up.ptr, plan.cnt.first_up) : nullptr;
+  uint32_t n_blocks = 0;
   for (int32_t k = 0; k < rq.n; ++k) {
-    if (plan.regions[k].batched) stage_region(rq, plan, k, buf);
+    if (!plan.regions[k].batched) continue;
+    stage_region(rq, plan, k, buf);
+    if (block_first) {
+      block_first[plan.regions[k].count_slot] = n_blocks;
+      n_blocks += static_cast<uint32_t>(dv::count_blocks(rq.reads[k]->n_reads));
+    }
   }
+  if (block_first) block_first[plan.n_batched] = n_blocks;
   DV_HIP_CHECK(hipMemcpyAsync(buf.d_up.ptr, buf.h_up.ptr, plan.up_bytes, hipMemcpyHostToDevice, stream));
   DV_HIP_CHECK(hipMemsetAsync(buf.d_res.ptr, 0, plan.res_bytes, stream));
   if (plan.gv.n) {
@@ -963,10 +986,19 @@ int stage_and_launch(const BatchRequest& rq, const dv::BatchPlan& plan, const Ba
   }
   if (plan.cd.n) DV_HIP_CHECK(hipMemsetAsync(buf.d_cscr.ptr, 0, plan.cd.scratch_ints * sizeof(int32_t), stream));
   if (plan.win.n) DV_HIP_CHECK(hipMemsetAsync(buf.d_wscr.ptr, 0, plan.win.scratch_ints * sizeof(int32_t), stream));
-  for (int32_t k = 0; k < rq.n; ++k) {
-    if (plan.regions[k].batched) launch_count(batch_count_args(rq, plan, k, buf), rq.reads[k]->n_reads, stream);
+  if (plan.cnt.one_launch) {
+    dv::ProfileScope prof(dv::kProfOther, stream);
+    hipLaunchKernelGGL(count_alleles_batch_kernel, dim3(n_blocks), dim3(256), 0, stream,
+                       at<const CountArgs>(buf.d_up.ptr, plan.cnt.args_up), at<const uint32_t>(buf.d_up.ptr, plan.cnt.first_up),
+                       plan.n_batched);
+  } else {
+    for (int32_t k = 0; k < rq.n; ++k) {
+      if (plan.regions[k].batched) launch_count(batch_count_args(rq, plan, k, buf), rq.reads[k]->n_reads, stream);
+    }
   }
   DV_HIP_CHECK(hipGetLastError());
+  stats->count_launches = plan.cnt.one_launch ? 1 : plan.n_batched;
+  stats->count_workgroups = plan.cnt.workgroups;
   if (plan.gv.n) {
     // the reference-confidence pass reads the counts where the kernels above leave them
     if (int rc = dv::gvcf_launch(at<const dv::GvcfRegion>(buf.d_up.ptr, plan.gv.desc_up), plan.gv.n, plan.gv.max_len,
@@ -1133,9 +1165,11 @@ void unpack(const BatchRequest& rq, const dv::BatchPlan& plan, const dv::SecondI
 }
 
 // The regions the batch did not answer, one by one: the one-region entry, then each pass from its counts.
-int run_alone(const BatchRequest& rq, const dv::SecondImage& second, const dv_gvcf_site* d_table, BatchResults* results) {
+int run_alone(const BatchRequest& rq, const dv::SecondImage& second, const dv_gvcf_site* d_table, BatchResults* results,
+              dv_count_batch_stats* stats) {
   for (int32_t k = 0; k < rq.n; ++k) {
     if (second.regions[k].kept) continue;
+    if (rq.reads[k]->n_reads != 0 && rq.options[k]->interval_end != rq.options[k]->interval_start) ++stats->regions_alone;
     if (int rc = dv_count_alleles(rq.reads[k], rq.options[k], &results->out[k], rq.stream)) return rc;
     if (rq.co) {
       if (int rc = candidates_from_counts(results->out[k], rq.options[k], rq.reads[k], rq.keys_of(k), rq.co, rq.stream,
@@ -1161,6 +1195,16 @@ int run_alone(const BatchRequest& rq, const dv::SecondImage& second, const dv_gv
   }
   return DV_OK;
 }
+
+// What the calling thread's last batch call did: dv_count_batch_last_stats.
+dv_count_batch_stats& last_batch_stats() {
+  static thread_local dv_count_batch_stats stats{};
+  return stats;
+}
+
+// DV_COUNT_ONE_LAUNCH=1: the batched regions of a call are counted by one launch of count_alleles_batch_kernel.
+// Read at every call; off by default.
+bool count_one_launch_enabled() { return dv::env_switch("DV_COUNT_ONE_LAUNCH", false); }
 
 }  // namespace
 
@@ -1249,6 +1293,8 @@ int dv_count_alleles(const dv_batch* b, const dv_allele_counter_options* o, dv_a
 // back to back, and the stream is synchronised twice for the whole batch.  Results per region are
 // those of dv_count_alleles (the same kernel on the same arguments).  Regions whose tables are
 // device-resident, and the rare region whose events overflow the first guess, take the one-region path.
+// With DV_COUNT_ONE_LAUNCH=1 the batched regions' kernels are one launch (count_alleles_batch_kernel: the same
+// workgroups in one grid); nothing that comes back differs, and dv_count_batch_last_stats tells which way a call went.
 // dv_count_alleles_batch, and with `gv` set dv_count_alleles_gvcf_batch: the gVCF pass (gvcf.hip) is queued
 // behind the counting kernels and its records come back with the events.  Without `gv` nothing differs.
 // With `co` set dv_call_candidates_batch: the candidate pass (candidates.hip) is queued behind the counting
@@ -1262,15 +1308,19 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
   const BatchRequest rq{n, reads, options, read_keys, gv, co, wo, (co && co->positions_only) || (wo && !out),
                         static_cast<hipStream_t>(stream_v), who};
   BatchResults results;              // frees whatever it holds on every return but the last
+  dv_count_batch_stats& stats = last_batch_stats();
+  stats = dv_count_batch_stats{};
   if (int rc = check_batch(rq, out, gout, cout, wout, &results)) return rc;
-  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, read_keys, gv, co, wo);
+  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, read_keys, gv, co, wo, count_one_launch_enabled());
+  stats.regions = n;
+  stats.regions_batched = plan.n_batched;
   dv::SecondImage second;            // of no region yet: which regions the batch has answered
   second.regions.resize(plan.regions.size());
   const dv_gvcf_site* d_table = nullptr;
   if (plan.n_batched > 0) {
     static thread_local BatchBuffers buf;
     if (int rc = buf.reserve(plan)) return rc;
-    if (int rc = stage_and_launch(rq, plan, buf, &d_table)) return rc;
+    if (int rc = stage_and_launch(rq, plan, buf, &d_table, &stats)) return rc;
     if (int rc = download_first(rq, plan, buf)) return rc;
     second = dv::second_image(plan, at<const uint32_t>(buf.h_down.ptr, plan.counters_at),
                               at<const int32_t>(buf.h_down.ptr, plan.n_blocks_at),
@@ -1280,7 +1330,7 @@ static int count_batch(int32_t n, const dv_batch* const* reads, const dv_allele_
     if (int rc = download_second(rq, plan, second, &buf)) return rc;
     unpack(rq, plan, second, buf, &results);
   }
-  if (int rc = run_alone(rq, second, d_table, &results)) return rc;
+  if (int rc = run_alone(rq, second, d_table, &results, &stats)) return rc;
   results.release();
   return DV_OK;
 }
@@ -1314,6 +1364,12 @@ int dv_select_windows_batch(int32_t n, const dv_batch* const* reads, const dv_al
   if (!window_options) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_select_windows_batch: window options are null");
   return count_batch(n, reads, options, read_keys, nullptr, nullptr, window_options, counts_out, nullptr, nullptr,
                      windows_out, stream, "dv_select_windows_batch");
+}
+
+int dv_count_batch_last_stats(dv_count_batch_stats* out) {
+  if (!out) return dv::fail(DV_ERR_INVALID_ARGUMENT, "dv_count_batch_last_stats: null");
+  *out = last_batch_stats();
+  return DV_OK;
 }
 
 int64_t dv_windows_arrays(const dv_windows* w, const int64_t** starts, const int64_t** ends,

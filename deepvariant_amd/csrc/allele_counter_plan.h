@@ -6,6 +6,7 @@
 #define DV_ALLELE_COUNTER_PLAN_H_
 
 #include "candidates.h"
+#include "count_args.h"
 #include "device_round_trip.h"
 #include "gvcf.h"
 #include "window_select.h"
@@ -38,6 +39,7 @@ struct RegionPlan {
   size_t mask_words = 0;
   bool has_keys = false;
   size_t cnt_off = 0, ev_off = 0;                 // in ints / events: the region's counts, and its events and words
+  int count_slot = -1;                            // index among the batched regions: its CountArgs and block range
   struct Gvcf {
     int slot = -1;                                // index among the batched regions
     size_t scratch_off = 0, block_off = 0;        // in ints / records
@@ -78,12 +80,23 @@ struct BatchPlan {
     size_t cand_desc_up = 0, desc_up = 0;         // the CandRegion and the WindowRegion descriptors, slot by slot
     size_t scratch_ints = 0, windows = 0, mask_words = 0;
   } win;
+  struct Count {
+    bool one_launch = false;                      // the two sections below exist
+    size_t args_up = 0;                           // CountArgs[n_batched] in the staging image, slot by slot
+    size_t first_up = 0;                          // uint32_t[n_batched + 1]: the first workgroup of every slot, and the grid
+    int64_t workgroups = 0;                       // of all batched regions, whichever way they are launched
+  } cnt;
 };
 
+// One grid holds at most this many workgroups; a batch beyond it (1.4e11 reads) is counted region by region.
+constexpr int64_t kMaxCountWorkgroups = 0x7fffffff;
+
 // `gv` / `co` / `wo`: the optional passes (null = off).  read_keys may be null, and so may each of its entries.
+// `one_launch`: the staging image ends with the table and the block prefix of count_alleles_batch_kernel; without
+// it no offset or total differs from a plan that knows nothing of them.
 inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
                             const int32_t* const* read_keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
-                            const dv_window_options* wo = nullptr) {
+                            const dv_window_options* wo = nullptr, bool one_launch = false) {
   BatchPlan plan;
   plan.regions.resize(static_cast<size_t>(n > 0 ? n : 0));
   Layout up;
@@ -94,7 +107,8 @@ inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_al
     p.len = o->interval_end - o->interval_start;
     if (b->n_reads == 0 || p.len == 0 || b->memory != DV_MEM_HOST) continue;
     p.batched = true;
-    ++plan.n_batched;
+    p.count_slot = plan.n_batched++;
+    plan.cnt.workgroups += count_blocks(b->n_reads);
     const size_t nr = static_cast<size_t>(b->n_reads);
     auto field = [&up](size_t bytes) { return up.add(std::max<size_t>(bytes, 1)); };
     p.up.read_pos = field(nr * 4);
@@ -148,6 +162,11 @@ inline BatchPlan plan_batch(int32_t n, const dv_batch* const* reads, const dv_al
   if (plan.win.n) {
     plan.win.cand_desc_up = up.add(static_cast<size_t>(plan.win.n) * sizeof(CandRegion));
     plan.win.desc_up = up.add(static_cast<size_t>(plan.win.n) * sizeof(WindowRegion));
+  }
+  if (one_launch && plan.n_batched && plan.cnt.workgroups <= kMaxCountWorkgroups) {
+    plan.cnt.one_launch = true;
+    plan.cnt.args_up = up.add(static_cast<size_t>(plan.n_batched) * sizeof(CountArgs));
+    plan.cnt.first_up = up.add((static_cast<size_t>(plan.n_batched) + 1) * sizeof(uint32_t));
   }
   plan.up_bytes = up.bytes();
   // the image's end is its last section's, unpadded

@@ -1467,6 +1467,25 @@ int64_t dv_windows_arrays(const dv_windows* w, const int64_t** starts, const int
                           const uint32_t** candidate_mask, const uint32_t** scores);
 void dv_windows_free(dv_windows* w);
 
+/* How the counting in front of every batch entry point above was launched.  A batch uploads the host-resident
+ * regions that have reads and an interval in one image ("batched"); by default each of them is then counted by a
+ * launch of its own, ceil(n_reads / 64) workgroups each.  With DV_COUNT_ONE_LAUNCH=1 in the environment (read at
+ * every call; off by default) one launch covers them all: the same workgroups in one grid, each finding its region
+ * by bisection of a block prefix that travels with the upload.  The switch changes no result: counts are integer
+ * atomic sums, and the events, whose raw order varies from run to run either way, come home sorted by
+ * (position, read, read_offset).  Regions that are not batched (a device-resident table) and regions whose events
+ * overflow the batch's first guess are counted by the one-region kernel afterwards, with or without the switch. */
+typedef struct dv_count_batch_stats {
+  int32_t regions;           /* n of the call */
+  int32_t regions_batched;   /* counted by the batch's own launches */
+  int32_t regions_alone;     /* counted by a one-region launch: not batched, or overflowed and repeated */
+  int32_t count_launches;    /* counting launches for the batched regions: regions_batched, or 1 with the switch */
+  int64_t count_workgroups;  /* workgroups of those launches together */
+} dv_count_batch_stats;
+/* What the calling thread's last dv_count_alleles_batch, dv_count_alleles_gvcf_batch, dv_call_candidates_batch or
+ * dv_select_windows_batch did (all zero before the first).  A null pointer is DV_ERR_INVALID_ARGUMENT. */
+int dv_count_batch_last_stats(dv_count_batch_stats* out);
+
 /* CRC32C (Castagnoli) as used by TFRecord framing
  * (third_party/nucleus/io/example_writer.cc:88-104 via tensorflow::io::RecordWriter). */
 uint32_t dv_crc32c(const uint8_t* data, size_t n);

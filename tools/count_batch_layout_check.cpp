@@ -4,7 +4,10 @@
 // table sizes and interval lengths from {0, 1, 15, 16, 17, 1000}, with and without candidate positions, read keys, the
 // gVCF pass, the candidate pass, positions_only and the window pass (with and without counts, at window distances 0
 // and 80, with and without the debug arrays), and every subset of regions overflowing its first guess.  The window
-// pass' sections came after the hand-kept arithmetic: they are held against a second statement of them here.
+// pass' sections came after the hand-kept arithmetic: they are held against a second statement of them here.  So are
+// the two sections of the one-launch counting kernel (plan_batch's one_launch: the CountArgs table and the block
+// prefix behind every other section of the staging image), the regions' count slots and the workgroup total: every
+// case without an overflowed region runs a second time with one_launch on, where everything else must stay as it is.
 // Host arithmetic only: no HIP call is made and no device is needed.  Not part of the library's build:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Iinclude -Ideepvariant_amd/csrc \
 //       tools/count_batch_layout_check.cpp -o /tmp/count_batch_layout_check && /tmp/count_batch_layout_check
@@ -244,15 +247,40 @@ long mismatches = 0, cases = 0;
 
 void compare(int32_t n, const dv_batch* const* reads, const dv_allele_counter_options* const* options,
              const int32_t* const* keys, const dv_gvcf_options* gv, const dv_candidate_options* co,
-             const dv_window_options* wo, bool with_counts, unsigned overflowed) {
+             const dv_window_options* wo, bool with_counts, unsigned overflowed, bool one_launch = false) {
   ++cases;
   const bool pos_only = (co && co->positions_only) || (wo && !with_counts);
   std::vector<OldPlan> old;
   const OldTotals t = old_plan(n, reads, options, keys, gv, co, wo, &old);
-  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, keys, gv, co, wo);
+  const dv::BatchPlan plan = dv::plan_batch(n, reads, options, keys, gv, co, wo, one_launch);
   SAME(plan.regions.size(), old.size());
   SAME(plan.n_batched, t.n_batched);
-  SAME(plan.up_bytes, t.up_bytes);
+  {
+    // the one-launch kernel's sections, stated a second time: behind everything the image held before, the table of
+    // 184-byte descriptors slot by slot, then one word per slot and one more; neither without a batched region
+    static_assert(sizeof(dv::CountArgs) == 184, "CountArgs is part of the staging image");
+    const bool sections = one_launch && t.n_batched > 0;
+    size_t up_bytes = t.up_bytes;
+    const size_t args_up = up_bytes;
+    if (sections) up_bytes += align16(static_cast<size_t>(t.n_batched) * 184);
+    const size_t first_up = up_bytes;
+    if (sections) up_bytes += align16((static_cast<size_t>(t.n_batched) + 1) * 4);
+    SAME(plan.cnt.one_launch, sections);
+    SAME(plan.up_bytes, up_bytes);
+    if (sections) {
+      SAME(plan.cnt.args_up, args_up);
+      SAME(plan.cnt.first_up, first_up);
+    }
+    long long workgroups = 0;
+    int slot = 0;
+    for (size_t k = 0; k < old.size(); ++k) {
+      SAME(plan.regions[k].count_slot, old[k].batched ? slot : -1);
+      if (!old[k].batched) continue;
+      ++slot;
+      workgroups += (reads[k]->n_reads + 63) / 64;
+    }
+    SAME(plan.cnt.workgroups, workgroups);
+  }
   SAME(plan.cnt_ints, t.cnt_ints);
   SAME(plan.ev_total, t.ev_total);
   SAME(plan.max_cap, t.max_cap);
@@ -433,6 +461,7 @@ int main() {
             for (unsigned overflowed = 0; overflowed < (1u << n); ++overflowed) {
               compare(n, reads, options, with_keys ? keys : nullptr, m.gv, m.co, m.wo, m.with_counts, overflowed);
             }
+            compare(n, reads, options, with_keys ? keys : nullptr, m.gv, m.co, m.wo, m.with_counts, 0, true);
           }
         }
       }
