@@ -61,6 +61,8 @@ ABI_SYMBOLS = [
     'dv_trim_device_last_stats',
     'dv_alt_align_batch', 'dv_alt_align_batch_device', 'dv_alt_aligned_arrays', 'dv_alt_aligned_free',
     'dv_alt_align_device_last_stats',
+    'dv_align_windows_batch', 'dv_align_windows_batch_device', 'dv_aligned_windows_arrays', 'dv_aligned_windows_free',
+    'dv_realign_finish_last_stats', 'dv_realign_finish_sorted_order',
     'dv_debruijn_build', 'dv_debruijn_destroy', 'dv_debruijn_kmer_size', 'dv_debruijn_haplotypes',
     'dv_debruijn_graphviz', 'dv_debruijn_compact_batch', 'dv_debruijn_compact_batch_device', 'dv_debruijn_compact_free',
     'dv_debruijn_paths_batch', 'dv_debruijn_paths_batch_device', 'dv_debruijn_paths_free', 'dv_debruijn_paths_last_stats',
@@ -294,6 +296,22 @@ class DvAltAlignStats(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('items', 'items_on_host', 'pairs', 'pairs_fast', 'pairs_swept',
                                        'pairs_swept_on_host', 'pairs_traced_on_host', 'status0', 'status1', 'status2',
                                        'words_written', 'launches')]
+
+
+class DvAlignWindow(C.Structure):
+  _fields_ = [('first_read', C.c_int32), ('n_reads', C.c_int32), ('first_haplotype', C.c_int32),
+              ('n_haplotypes', C.c_int32), ('reference', C.c_int32), ('ref_prefix_len', C.c_int32),
+              ('ref_suffix_len', C.c_int32), ('reserved', C.c_int32), ('ref_start', C.c_int64)]
+
+
+class DvAlignedWindowsView(C.Structure):
+  _fields_ = [('n_windows', C.c_int32), ('n_reads', C.c_int32), ('n_words', C.c_int64),
+              ('window_read_off', C.c_void_p), ('status', C.c_void_p), ('position', C.c_void_p),
+              ('cigar_off', C.c_void_p), ('cigar', C.c_void_p)]
+
+
+class DvRealignFinishStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('windows', 'windows_on_host', 'reads', 'cigar_words', 'launches', 'bytes_down')]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -607,6 +625,14 @@ def lib():
     l.dv_alt_aligned_free.argtypes = [C.c_void_p]
     l.dv_alt_aligned_free.restype = None
     l.dv_alt_align_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_align_windows_batch.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    l.dv_align_windows_batch_device.argtypes = l.dv_align_windows_batch.argtypes + [C.c_void_p]
+    l.dv_aligned_windows_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_aligned_windows_free.argtypes = [C.c_void_p]
+    l.dv_aligned_windows_free.restype = None
+    l.dv_realign_finish_last_stats.argtypes = [C.c_void_p]
+    l.dv_realign_finish_sorted_order.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_realign_regions_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]
     l.dv_debruijn_build.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -154,6 +154,9 @@ class FastPassAligner {
   int ref_prefix_len() const { return ref_prefix_len_; }
   int ref_suffix_len() const { return ref_suffix_len_; }
   int score_threshold() const { return score_threshold_; }
+  uint64_t ref_start() const { return region_position_; }
+  bool normalize_reads() const { return normalize_reads_; }
+  bool force_alignment() const { return force_alignment_; }
   size_t index_size() const { return index_.size(); }
   // occurrences of a k-mer: (read, offset) pairs in insertion order
   std::vector<std::pair<uint32_t, uint32_t>> kmer_occurrences(std::string_view kmer) const;

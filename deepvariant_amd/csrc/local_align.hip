@@ -398,13 +398,19 @@ namespace dv {
 int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, const std::vector<int32_t>& pair_ref,
                           const std::vector<int32_t>& pair_query, int match, int mismatch, int gap_open,
                           int gap_extend, void* stream_in, std::vector<SweepCorners>* corners,
-                          std::vector<uint8_t>* route, DeviceAlignStats* stats, DeviceRuns* traced) {
+                          std::vector<uint8_t>* route, DeviceAlignStats* stats, DeviceRuns* traced,
+                          ResidentSweep* keep) {
   const size_t n_pairs = pair_ref.size();
+  if (keep) {
+    *keep = ResidentSweep();
+    keep->item_of_pair.assign(n_pairs, -1);
+    keep->traced.assign(n_pairs, 0);
+  }
   corners->assign(n_pairs, SweepCorners());
   route->assign(n_pairs, kRouteHost);
   TracebackStats& tb = last_traceback_stats();
   tb = TracebackStats();
-  const bool trace = traced && device_traceback_enabled();
+  const bool trace = traced && (keep || device_traceback_enabled());
   if (traced) {
     traced->traced.assign(n_pairs, 0);
     traced->band.assign(n_pairs, 0);
@@ -506,12 +512,29 @@ int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, co
                        static_cast<int>(out_words), static_cast<uint8_t*>(rt.d_scratch.ptr));
     DV_HIP_CHECK(hipGetLastError());
   }
-  if (int rc = rt.finish(down_bytes)) return rc;
+  // the words a pair's row holds on the host: all of them, or with `keep` the header alone, rows packed
+  const size_t host_words = keep ? kTraceHeaderWords : out_words;
+  if (keep) {
+    DV_HIP_CHECK(hipMemcpy2DAsync(rt.down.ptr, host_words * sizeof(int32_t), rt.d_down.ptr, out_words * sizeof(int32_t),
+                                  host_words * sizeof(int32_t), n_items, hipMemcpyDeviceToHost, rt.stream()));
+    DV_HIP_CHECK(hipStreamSynchronize(rt.stream()));
+    keep->d_out = rt.dev_down<const int32_t>(0);
+    keep->out_words = static_cast<int32_t>(out_words);
+    keep->n_items = static_cast<int32_t>(n_items);
+    keep->d_items = rt.dev_up<const SweepItem>(o_items);
+    keep->d_seq_off = rt.dev_up<const int32_t>(o_off);
+    keep->d_codes = rt.dev_up<const uint8_t>(o_codes);
+    keep->stream = rt.stream();
+    keep->bytes_down = static_cast<int64_t>(n_items * host_words * sizeof(int32_t));
+  } else if (int rc = rt.finish(down_bytes)) {
+    return rc;
+  }
   if (stats) stats->launches += 1;
   const int32_t* res = rt.host_down<int32_t>(0);
   for (size_t w = 0; w < n_items; ++w) {
-    const int32_t* r = res + w * out_words;
+    const int32_t* r = res + w * host_words;
     const size_t k = static_cast<size_t>(items[w].pair);
+    if (keep) keep->item_of_pair[k] = static_cast<int32_t>(w);
     SweepCorners& c = (*corners)[k];
     c.score = r[0];
     c.ref_end = r[1];
@@ -528,6 +551,10 @@ int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, co
     ++tb.traced_on_device;
     tb.band_cells += static_cast<int64_t>(c.query_end - c.query_begin + 1) * (2 * band + 1);
     tb.widest_band = std::max<int64_t>(tb.widest_band, band);
+    if (keep) {                // the runs stay on the device
+      keep->traced[k] = 1;
+      continue;
+    }
     traced->traced[k] = 1;
     traced->band[k] = band;
     traced->first[k] = static_cast<int32_t>(traced->words.size());

@@ -58,17 +58,37 @@ inline bool device_align_fits(size_t ref_len, size_t query_len) {
          ref_len <= static_cast<size_t>(kDeviceAlignMaxReference);
 }
 
+// A sweep call's buffers as it left them on the device, for a caller that goes on working there (realign_finish.hip):
+// the pairs' words stay in the calling thread's download buffer, its items, sequence offsets and codes in its upload
+// buffer.  Valid until the calling thread's next sweep_pairs_on_device.
+struct ResidentSweep {
+  const int32_t* d_out = nullptr;      // out_words per item: 6 corner values, traced, runs | band << 16, the runs
+  int32_t out_words = 0, n_items = 0;
+  const void* d_items = nullptr;       // {ref slot, query slot, rows, pair, area} per item
+  const int32_t* d_seq_off = nullptr;  // [slots + 1] into d_codes
+  const uint8_t* d_codes = nullptr;
+  void* stream = nullptr;              // the stream the sweep ran on
+  std::vector<int32_t> item_of_pair;   // -1: the pair was not swept on the device
+  std::vector<uint8_t> traced;         // per pair: the kernel traced it back; its runs are in d_out
+  int64_t bytes_down = 0;              // what the call downloaded
+};
+
 // Sweeps pair k = (*sequences[pair_ref[k]], *sequences[pair_query[k]]) for every pair inside the
 // limits: one upload, one launch, one download on `stream` (null: a non-blocking stream the
 // library owns), then waits for it.  Indices must be valid.  route[k] says what became of pair k;
 // stats (may be null) is added to.  Buffers are the calling thread's and are reused.
 // `traced` (may be null: no trace-back) receives the runs of the pairs the kernel traced back, when
 // device_traceback_enabled(); last_traceback_stats() says how the pairs holding an alignment were split.
+// `keep` (may be null: exactly the call above): the trace-back runs whatever the switch says, the result buffer stays
+// on the device and *keep says where; of each pair only the corners, the traced flag, the run count and the band are
+// downloaded (8 words instead of 8 + DV_LOCAL_ALIGN_DEVICE_MAX_RUNS), and `traced` receives no runs: a pair the
+// caller finishes on the host goes through LocalAligner::complete.
 // Returns a dv_status; DV_ERR_NO_DEVICE without a GPU (only when there is device work).
 int sweep_pairs_on_device(const std::vector<const CodedSequence*>& sequences, const std::vector<int32_t>& pair_ref,
                           const std::vector<int32_t>& pair_query, int match, int mismatch, int gap_open,
                           int gap_extend, void* stream, std::vector<SweepCorners>* corners,
-                          std::vector<uint8_t>* route, DeviceAlignStats* stats, DeviceRuns* traced);
+                          std::vector<uint8_t>* route, DeviceAlignStats* stats, DeviceRuns* traced,
+                          ResidentSweep* keep = nullptr);
 
 // LocalAligner::complete for pair k of a device call: the text form around the device's runs where the
 // kernel traced the pair back, complete() itself otherwise.  Returns what complete() returns.

@@ -21,6 +21,11 @@
 //   2b, once: the pairs of all windows go through one kernel launch; the CIGARs of the pairs that
 //       aligned (LocalAligner::complete) are spread over the worker pool;
 //   2c, one task per window: FastPassAligner::finish_alignments.
+// With DV_REALIGN_DEVICE_FINISH=1 (honoured only with DV_REALIGN_DEVICE_TRACEBACK=1) 2b's launch leaves its result on the
+// device and downloads the corners, traced flag, run count and band of each pair; its worker-pool loop makes text
+// (LocalAligner::complete) only for the windows the device hands back -- a pair outside the sweep kernel's limits, or
+// an alignment the kernel did not trace back --, and 2c becomes one call of realign_finish.hip's kernels for all
+// other windows plus finish_alignments for those.
 // With DV_REALIGN_DEVICE_ASSEMBLY=1 the device route's phase 1 becomes 1a, the batch's window list; 1b, once, the
 // graph of every window in one kernel launch (debruijn.hip), choice of k and cycle test included; 1c, one task per
 // window: DeBruijnGraph::from_compact (which prunes), candidate_haplotypes and the comparison with the reference.
@@ -51,6 +56,7 @@
 #include "fast_pass_aligner.h"
 #include "fast_pass_device.h"
 #include "local_align_device.h"
+#include "realign_finish_device.h"
 
 struct dv_realign_result {
   std::vector<int64_t> region_row_off;
@@ -221,6 +227,7 @@ int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_region
     dv::last_fast_pass_stats() = dv::FastPassStats();
     dv::last_assembly_stats() = dv::AssemblyStats();
     dv::last_paths_stats() = dv::PathsStats();
+    dv::last_finish_stats() = dv::FinishStats();
     const DeviceRoute device{stream, stats};
     return realign_regions_impl(regions, n_regions, o, out, arrays, &device);
   } catch (const std::bad_alloc&) {
@@ -553,15 +560,32 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
     }
     std::vector<dv::LocalAlignment> results(pair_ref.size());
     std::vector<char> ok(pair_ref.size(), 0);
-    if (!pair_ref.empty()) {
+    const bool finish_on_device = dv::device_finish_enabled() && dv::device_traceback_enabled();
+    dv::ResidentSweep resident;
+    std::vector<char> window_on_device(windows.size(), 0);   // finish_on_device: finished by the kernels
+    if (!pair_ref.empty() || finish_on_device) {
       std::vector<dv::SweepCorners> corners;
       std::vector<uint8_t> route;
       dv::DeviceAlignStats stats;
       dv::DeviceRuns traced;
-      if (int rc = dv::sweep_pairs_on_device(sequences, pair_ref, pair_query, scoring->match(), scoring->mismatch(),
-                                             scoring->gap_open(), scoring->gap_extend(), device->stream, &corners,
-                                             &route, &stats, &traced)) {
-        return rc;
+      if (!pair_ref.empty()) {
+        if (int rc = dv::sweep_pairs_on_device(sequences, pair_ref, pair_query, scoring->match(), scoring->mismatch(),
+                                               scoring->gap_open(), scoring->gap_extend(), device->stream, &corners,
+                                               &route, &stats, &traced, finish_on_device ? &resident : nullptr)) {
+          return rc;
+        }
+      }
+      if (finish_on_device) {
+        dv::FinishStats& fs = dv::last_finish_stats();
+        fs.bytes_down += resident.bytes_down;
+        for (int t : align_tasks) {
+          const Window& win = windows[t];
+          if (!win.aligner) continue;
+          ++fs.windows;
+          window_on_device[t] = dv::window_finishes_on_device(win.first_pair, win.pairs.pair_ref.size(), route, corners,
+                                                              resident);
+          if (!window_on_device[t]) ++fs.windows_on_host;
+        }
       }
       if (device->stats) {
         device->stats->pairs = stats.pairs;
@@ -574,9 +598,21 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
       constexpr size_t kPairsPerTask = 16;
       std::vector<int> chunks((pair_ref.size() + kPairsPerTask - 1) / kPairsPerTask);
       for (size_t c = 0; c < chunks.size(); ++c) chunks[c] = static_cast<int>(c);
+      // finish_on_device: only the pairs of the windows handed back need it
+      std::vector<char> pair_skipped;
+      if (finish_on_device) {
+        pair_skipped.assign(pair_ref.size(), 0);
+        for (int t : align_tasks) {
+          if (!window_on_device[t]) continue;
+          const Window& win = windows[t];
+          std::fill(pair_skipped.begin() + static_cast<std::ptrdiff_t>(win.first_pair),
+                    pair_skipped.begin() + static_cast<std::ptrdiff_t>(win.first_pair + win.pairs.pair_ref.size()), 1);
+        }
+      }
       parallel_tasks(chunks, n_threads, [&](int c) {
         const size_t end = std::min(pair_ref.size(), (static_cast<size_t>(c) + 1) * kPairsPerTask);
         for (size_t k = static_cast<size_t>(c) * kPairsPerTask; k < end; ++k) {
+          if (finish_on_device && pair_skipped[k]) continue;
           const dv::CodedSequence& ref = *sequences[pair_ref[k]];
           const dv::CodedSequence& q = *sequences[pair_query[k]];
           if (route[k] == dv::kRouteDevice) {
@@ -591,10 +627,32 @@ static int realign_regions_impl(const dv_realign_region* regions, int32_t n_regi
         }
       });
     }
-    // ---- 2c: the rest of align_reads per window
+    // ---- 2c: the rest of align_reads, on the device for the windows inside its limits, per window for the others
+    if (finish_on_device) {
+      std::vector<dv::FinishWindow> on_device;
+      const dv::FastPassAligner* any = nullptr;
+      for (int t : align_tasks) {
+        Window& win = windows[t];
+        if (!win.aligner || !window_on_device[t]) continue;
+        any = win.aligner.get();
+        on_device.push_back(dv::FinishWindow{any, &win.pairs, win.first_pair, &win.aligned});
+      }
+      if (any) {
+        if (!resident.stream) resident.stream = device->stream;
+        if (int rc = dv::finish_windows_on_device(on_device, resident, any->force_alignment(), any->normalize_reads(),
+                                                  &dv::last_finish_stats())) {
+          return rc;
+        }
+      }
+    }
     parallel_tasks(align_tasks, n_threads, [&](int t) {
       Window& win = windows[t];
       if (!win.aligner) return;
+      if (window_on_device[t]) {
+        win.aligner.reset();
+        win.pairs = dv::AlignmentPairs();
+        return;
+      }
       win.aligned = win.aligner->finish_alignments(win.pairs, results.data() + win.first_pair, ok.data() + win.first_pair);
       win.aligner.reset();
       win.pairs = dv::AlignmentPairs();

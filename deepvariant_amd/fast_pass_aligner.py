@@ -326,6 +326,68 @@ def fast_pass_batch_device(windows: Sequence[dict], options: Optional[dict] = No
   return res, stats
 
 
+def _align_windows(entry, windows, options, stream):
+  import numpy as np
+  raw, descs = [], (_lib.DvAlignWindow * max(len(windows), 1))()
+  as_bytes = lambda s: s.encode('latin-1') if isinstance(s, str) else bytes(s)      # noqa: E731
+  for d, w in zip(descs, windows):
+    reads, haplotypes = [as_bytes(r) for r in w['reads']], [as_bytes(h) for h in w['haplotypes']]
+    d.first_read, d.n_reads = len(raw), len(reads)
+    raw += reads
+    d.first_haplotype, d.n_haplotypes = len(raw), len(haplotypes)
+    raw += haplotypes
+    d.reference = len(raw)
+    raw.append(as_bytes(w['reference']))
+    d.ref_prefix_len, d.ref_suffix_len = w.get('ref_prefix_len', 0), w.get('ref_suffix_len', 0)
+    d.ref_start = w.get('ref_start', 0)
+  off = np.zeros(len(raw) + 1, np.int64)
+  np.cumsum([len(b) for b in raw], out=off[1:])
+  table = b''.join(raw)
+  opt = _lib.DvAlignerOptions()
+  for name, value in (options or {}).items():
+    setattr(opt, name, value)
+  handle = C.c_void_p()
+  args = [len(raw), table, off.ctypes.data, len(windows), descs, C.byref(opt), C.byref(handle)]
+  if stream is not None:
+    args.append(stream or None)
+  _lib.check(entry(*args))
+  try:
+    view = _lib.DvAlignedWindowsView()
+    _lib.check(_lib.lib().dv_aligned_windows_arrays(handle, C.byref(view)))
+    take = lambda ptr, n, ctype, dtype: (np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).copy()   # noqa: E731
+                                         if n else np.zeros(0, dtype))
+    return dict(window_read_off=take(view.window_read_off, view.n_windows + 1, C.c_int32, np.int32),
+                status=take(view.status, view.n_reads, C.c_int32, np.int32),
+                position=take(view.position, view.n_reads, C.c_int64, np.int64),
+                cigar_off=take(view.cigar_off, view.n_reads + 1, C.c_uint32, np.uint32),
+                cigar=take(view.cigar, view.n_words, C.c_uint32, np.uint32))
+  finally:
+    _lib.lib().dv_aligned_windows_free(handle)
+
+
+def align_windows_batch(windows: Sequence[dict], options: Optional[dict] = None):
+  """FastPassAligner.AlignReads for every window of a batch, host code (dv_align_windows_batch).  A window is
+  dict(reads=[...], haplotypes=[...], reference=str, ref_prefix_len=0, ref_suffix_len=0, ref_start=0); reads are
+  upper-cased by the call.  `options`: fields of dv_aligner_options (0 or absent keeps the class default).
+  -> dict(window_read_off int32[w + 1], status int32[r], position int64[r], cigar_off uint32[r + 1], cigar uint32[...])
+  over the reads of all windows in window order."""
+  return _align_windows(_lib.lib().dv_align_windows_batch, windows, options, None)
+
+
+def align_windows_batch_device(windows: Sequence[dict], options: Optional[dict] = None, stream: int = 0,
+                               with_stats: bool = False):
+  """`align_windows_batch` end to end on the device: the fast pass, the sweeps with their trace-back and the finish
+  kernels of csrc/realign_finish.hip; identical arrays.  A window with a pair outside the sweep or trace-back
+  kernel's limits is finished by the host code inside the call.  There is no CPU fallback: without a GPU this raises
+  DV_ERR_NO_DEVICE.  with_stats: -> (arrays, _lib.DvRealignFinishStats)."""
+  res = _align_windows(_lib.lib().dv_align_windows_batch_device, windows, options, stream)
+  if not with_stats:
+    return res
+  stats = _lib.DvRealignFinishStats()
+  _lib.check(_lib.lib().dv_realign_finish_last_stats(C.byref(stats)))
+  return res, stats
+
+
 def realign_reads_to_haplotype(haplotype: str, reads: Sequence, contig: str, ref_start: int, ref_end: int,
                                ref_reader, aln_config: Optional[dict] = None) -> List[Optional[T.Read]]:
   """RealignReadsToHaplotype (alt_aligned_pileup_lib.cc:278-313).

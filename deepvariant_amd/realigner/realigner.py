@@ -322,6 +322,8 @@ class RealignJob:
                                    # DV_REALIGN_DEVICE_ASSEMBLY=1 moved phase 1's graphs to the device)
     self.paths_stats = None        # _lib.DvDebruijnPathsStats of the call, device route only (all zero unless
                                    # DV_REALIGN_DEVICE_PATHS=1 moved pruning and path enumeration there as well)
+    self.finish_stats = None       # _lib.DvRealignFinishStats of the call, device route only (all zero unless
+                                   # DV_REALIGN_DEVICE_FINISH=1, with the trace-back on, finished the alignments there)
     self._want_haplotypes = want_haplotypes
     self._options = options
     self._jobs: List = []          # (slot, table, usable windows)
@@ -377,6 +379,9 @@ class RealignJob:
       paths = _lib.DvDebruijnPathsStats()
       _lib.check(_lib.lib().dv_debruijn_paths_last_stats(C.byref(paths)))
       self.paths_stats = paths
+      finish = _lib.DvRealignFinishStats()
+      _lib.check(_lib.lib().dv_realign_finish_last_stats(C.byref(finish)))
+      self.finish_stats = finish
     else:
       _lib.check(_lib.lib().dv_realign_regions(descs, len(self._jobs), C.byref(self._options), C.byref(handle),
                                                C.byref(out)))

@@ -914,6 +914,74 @@ typedef struct dv_alt_align_stats {
 /* What the calling thread's last dv_alt_align_batch_device did. */
 int dv_alt_align_device_last_stats(dv_alt_align_stats* out);
 
+/* ---- the window aligner over many windows in one call -------------------------------
+ * FastPassAligner::AlignReads (deepvariant/realigner/fast_pass_aligner.cc:131-177) for a batch of windows, each with
+ * its own reads, haplotypes and reference: what dv_aligner_create / set_reference / set_haplotypes /
+ * dv_aligner_align_reads do per window, in one call and with the result as arrays.
+ * Sequences are raw bytes: sequence s is bytes[seq_off[s], seq_off[s + 1]); reads are upper-cased by the call,
+ * haplotypes and the reference are taken as given.  options: as dv_aligner_create (0 keeps the class default;
+ * read_size and force_alignment are the call's, normalize_reads too; ref_prefix_len / ref_suffix_len come from each
+ * window).  Per read of every window, in window order then read order: status (0 / 1 / 2 as dv_realigned_read),
+ * position and the merged CIGAR (status 1 only).
+ * Null pointers, negative counts or lengths, descending offsets, a range or index outside the table, a window
+ * without a reference, a negative ref_start, options the class refuses or scoring values past 127:
+ * DV_ERR_INVALID_ARGUMENT before any device work.  On any error *out is NULL and nothing stays allocated. */
+typedef struct dv_align_window {
+  int32_t first_read, n_reads;             /* its reads: sequences [first_read, first_read + n_reads) */
+  int32_t first_haplotype, n_haplotypes;   /* its haplotypes: sequences [first_haplotype, ...) */
+  int32_t reference;                       /* the sequence holding the window's reference (required) */
+  int32_t ref_prefix_len, ref_suffix_len;  /* reference padding around the haplotypes */
+  int32_t reserved;
+  int64_t ref_start;                       /* reference coordinate of reference[0] */
+} dv_align_window;
+typedef struct dv_aligned_windows dv_aligned_windows;   /* owns the host arrays of one call's result */
+typedef struct dv_aligned_windows_view {                /* views into the result; valid until dv_aligned_windows_free */
+  int32_t n_windows;
+  int32_t n_reads;                 /* of all windows */
+  int64_t n_words;
+  const int32_t* window_read_off;  /* [n_windows + 1]: window w's reads are [off[w], off[w + 1]) */
+  const int32_t* status;           /* [n_reads] 0 / 1 / 2 as dv_realigned_read */
+  const int64_t* position;         /* [n_reads] status 1 only, else 0 */
+  const uint32_t* cigar_off;       /* [n_reads + 1] into cigar; words only for status 1 */
+  const uint32_t* cigar;           /* [n_words] dv_batch's encoding */
+} dv_aligned_windows_view;
+/* Host code (csrc/realign_finish.hip): FastPassAligner::align_reads window by window.  The checker of the device form. */
+int dv_align_windows_batch(int32_t n_seqs, const char* bytes, const int64_t* seq_off, int32_t n_windows,
+                           const dv_align_window* windows, const dv_aligner_options* options,
+                           dv_aligned_windows** out);
+/* The same end to end on the device: the fast pass of every (window, haplotype) in one launch (csrc/fast_pass.hip),
+ * one download, the pairs collected on the host, every pair's sweeps and trace-back in one launch
+ * (csrc/local_align.hip) whose result stays on the device -- of a pair only its corners, traced flag, run count and band
+ * come down --, then the finish kernels of csrc/realign_finish.hip, one lane per haplotype and then per (window, read):
+ * haplotype states, best haplotype + merge counted, scan, merge written; one staged upload, one download, one
+ * synchronisation on `stream` (NULL = a non-blocking stream the library owns); identical arrays.  A window is finished
+ * on the device only if every one of its pairs was swept there and every pair that holds an alignment was traced back
+ * there (DV_LOCAL_ALIGN_DEVICE_MAX_*, the trace-back's scratch budget); any other window is finished by the host code
+ * inside the call, with the host's trace-back for its pairs, and counted.  No read at all is DV_OK without a device;
+ * no device is DV_ERR_NO_DEVICE (there is no CPU fallback).  The device holds room for 64 CIGAR words per read of the
+ * call; a call with more runs its launches a second time with the exact room.  DV_REALIGN_FINISH_ROOM=1..64 in the
+ * environment, read at each call, lowers that room (for tests of the second run; results are identical). */
+int dv_align_windows_batch_device(int32_t n_seqs, const char* bytes, const int64_t* seq_off, int32_t n_windows,
+                                  const dv_align_window* windows, const dv_aligner_options* options,
+                                  dv_aligned_windows** out, void* stream);
+int dv_aligned_windows_arrays(const dv_aligned_windows* a, dv_aligned_windows_view* out);
+void dv_aligned_windows_free(dv_aligned_windows* a);
+typedef struct dv_realign_finish_stats {
+  int64_t windows;          /* windows with reads that reached the finish step */
+  int64_t windows_on_host;  /* of them handed back: finished by FastPassAligner::finish_alignments */
+  int64_t reads;            /* reads finished on the device */
+  int64_t cigar_words;      /* words of their merged CIGARs */
+  int64_t launches;         /* finish kernel launches */
+  int64_t bytes_down;       /* downloaded by the sweep call (8 words per pair) and by the finish step */
+} dv_realign_finish_stats;
+/* What the calling thread's last dv_align_windows_batch_device or dv_realign_regions_device did with the finish step
+ * (all zero when the latter did not use it: DV_REALIGN_DEVICE_FINISH unset). */
+int dv_realign_finish_last_stats(dv_realign_finish_stats* out);
+/* Test hook, host only: the order FastPassAligner's std::sort by haplotype_score gives n haplotype alignments with
+ * these scores, computed over (score, index) records (order_records, what the device route uploads) and over real
+ * HaplotypeAlignment objects (order_objects); both [n]. */
+int dv_realign_finish_sorted_order(int32_t n, const int32_t* scores, int32_t* order_records, int32_t* order_objects);
+
 /* ---- local assembly for the window realigner ------------------------------------
  * Replaces deepvariant/realigner/debruijn_graph.{h,cc} (DeBruijnGraph::Build,
  * CandidateHaplotypes, GraphViz; python binding deepvariant/realigner/python/
@@ -1135,7 +1203,11 @@ void dv_realign_result_free(dv_realign_result* r);
  * DV_REALIGN_DEVICE_PATHS=1, read at each call and honoured only together with DV_REALIGN_DEVICE_ASSEMBLY=1, also
  * prunes and enumerates there (dv_debruijn_paths_batch_device's kernels): the host threads only compare a window's
  * haplotypes with its reference, and build the windows the device hands back.  dv_debruijn_paths_last_stats reports
- * it. */
+ * it.
+ * DV_REALIGN_DEVICE_FINISH=1, read at each call and honoured only together with DV_REALIGN_DEVICE_TRACEBACK=1, also
+ * finishes the alignments there (dv_align_windows_batch_device's finish kernels, behind the sweep launch whose result
+ * stays on the device): the host threads make the text form and run FastPassAligner::finish_alignments only for the
+ * windows the device hands back.  dv_realign_finish_last_stats reports it. */
 int dv_realign_regions_device(const dv_realign_region* regions, int32_t n_regions, const dv_realign_options* options,
                               void* stream, dv_realign_result** out, dv_realign_output* arrays,
                               dv_realign_device_stats* stats);

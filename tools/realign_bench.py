@@ -15,7 +15,10 @@ phase 1's graphs in one launch of csrc/debruijn.hip) and `device_all` (all three
 windows, k-mer occurrences hashed and k values tried are in `stats`.  Where it has the device paths, `device_all_paths`
 (all four switches 1: DV_REALIGN_DEVICE_PATHS=1 on top of `device_all`, pruning and the haplotypes from the device too)
 is one more arm, compared with `device_all`; its windows, haplotypes and download size are in `stats`, next to the
-size of `device_all`'s download of the graphs' pools.  Fails without a GPU.  On a tree without the device route the host route is measured alone, so the same file
+size of `device_all`'s download of the graphs' pools.  Where it has the device finish, `device_all_finish` (all five
+switches 1: DV_REALIGN_DEVICE_FINISH=1 on top of `device_all_paths`, the alignments finished by csrc/realign_finish.hip)
+is one more arm, compared with `device_all_paths`; its windows, reads, words and download size are in `stats`.  Fails
+without a GPU.  On a tree without the device route the host route is measured alone, so the same file
 measures an older checkout.  Kernel time is not measured here: run this under
 `rocprofv3 --kernel-trace --stats -- python tools/realign_bench.py --repeats 1 --threads 16` and divide
 `cells` by local_align_sweeps' time per call (fast_pass_kernel: `fast_pass_cells`, with DV_REALIGN_DEVICE_FASTPASS=1
@@ -101,6 +104,8 @@ def main(argv=None):
   assembly_switch = 'DV_REALIGN_DEVICE_ASSEMBLY'
   has_paths = hasattr(_lib, 'DvDebruijnPathsStats')
   paths_switch = 'DV_REALIGN_DEVICE_PATHS'
+  has_finish = hasattr(_lib, 'DvRealignFinishStats')
+  finish_switch = 'DV_REALIGN_DEVICE_FINISH'
   if has_device:
     routes = {'host': R.Realigner(R.realigner_config(), ref, device_align=False),
               'device': R.Realigner(R.realigner_config(), ref, device_align=True)}
@@ -113,19 +118,23 @@ def main(argv=None):
       routes['device_all'] = routes['device']
     if has_paths:
       routes['device_all_paths'] = routes['device']
+    if has_finish:
+      routes['device_all_finish'] = routes['device']
   else:
     routes = {'host': R.Realigner(R.realigner_config(), ref)}
 
   def run(route):
     if has_traceback:
       # read by the library at each call
-      os.environ[switch] = '1' if route in ('device_traceback', 'device_all', 'device_all_paths') else '0'
+      os.environ[switch] = '1' if route in ('device_traceback', 'device_all', 'device_all_paths', 'device_all_finish') else '0'
     if has_fast_pass:
-      os.environ[fast_pass_switch] = '1' if route in ('device_fast_pass', 'device_all', 'device_all_paths') else '0'
+      os.environ[fast_pass_switch] = '1' if route in ('device_fast_pass', 'device_all', 'device_all_paths', 'device_all_finish') else '0'
     if has_assembly:
-      os.environ[assembly_switch] = '1' if route in ('device_assembly', 'device_all', 'device_all_paths') else '0'
+      os.environ[assembly_switch] = '1' if route in ('device_assembly', 'device_all', 'device_all_paths', 'device_all_finish') else '0'
     if has_paths:
-      os.environ[paths_switch] = '1' if route == 'device_all_paths' else '0'
+      os.environ[paths_switch] = '1' if route in ('device_all_paths', 'device_all_finish') else '0'
+    if has_finish:
+      os.environ[finish_switch] = '1' if route == 'device_all_finish' else '0'
     gc.collect()
     t0 = time.perf_counter()
     job = routes[route].start_realign_tables(tables, regions, want_haplotypes=False)    # window selection
@@ -180,6 +189,15 @@ def main(argv=None):
     result['stats'].update({'paths_windows': ps.windows, 'paths_windows_on_host': ps.windows_on_host,
                             'paths_haplotypes': ps.paths, 'paths_hap_bytes': ps.hap_bytes,
                             'paths_launches': ps.launches, 'paths_bytes_down': ps.bytes_down})
+  if has_finish:
+    _, _, got, job = run('device_all_finish')
+    assert len(want) == len(got) and all(_same(a[1], b[1]) for a, b in zip(want, got)), 'the device finish differs'
+    fs = job.finish_stats
+    assert job.device_stats.launches == 1 and fs.launches == 4 and fs.windows > 0 and fs.reads > 0
+    result['stats'].update({'finish_windows': fs.windows, 'finish_windows_on_host': fs.windows_on_host,
+                            'finish_reads': fs.reads, 'finish_cigar_words': fs.cigar_words,
+                            'finish_launches': fs.launches, 'finish_bytes_down': fs.bytes_down,
+                            'parent_sweep_bytes_down': job.device_stats.pairs * 72 * 4})
   for threads in [int(t) for t in args.threads.split(',')]:
     R._NATIVE_THREADS = threads                             # pylint: disable=protected-access
     runs = {route: [] for route in routes if not args.arms or route in args.arms.split(',')}
@@ -215,6 +233,11 @@ def main(argv=None):
                                                                entry['device_all']['native_call_ms'], 4)
       entry['device_all_paths_median_below_device_all_min'] = (entry['device_all_paths']['native_call_ms'] <
                                                                min(entry['device_all']['native_call_runs_ms']))
+    if 'device_all_finish' in entry and 'device_all_paths' in entry:
+      entry['device_all_finish_over_device_all_paths_native'] = round(entry['device_all_finish']['native_call_ms'] /
+                                                                      entry['device_all_paths']['native_call_ms'], 4)
+      entry['device_all_finish_median_below_device_all_paths_min'] = (
+          entry['device_all_finish']['native_call_ms'] < min(entry['device_all_paths']['native_call_runs_ms']))
     result['threads'][str(threads)] = entry
   line = json.dumps(result)
   print(line)
