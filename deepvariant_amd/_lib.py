@@ -72,7 +72,12 @@ ABI_SYMBOLS = [
     'dv_count_alleles_gvcf_batch', 'dv_gvcf_blocks_arrays', 'dv_gvcf_blocks_free',
     'dv_call_candidates_batch', 'dv_candidates_arrays', 'dv_candidates_free',
     'dv_select_windows_batch', 'dv_windows_arrays', 'dv_windows_free', 'dv_count_batch_last_stats',
+    'dv_genotype_sites', 'dv_genotype_sites_device', 'dv_genotypes_arrays', 'dv_genotypes_free',
+    'dv_genotype_min_nonref_prob', 'dv_genotype_device_last_stats',
 ]
+
+DV_GENOTYPE_DEVICE_MAX_ALTS = 6
+DV_GENOTYPE_OK, DV_GENOTYPE_BAD_SUM, DV_GENOTYPE_INCOMPLETE = 0, 1, 2
 
 
 # dv_ref_fetch_fn (include/dvhip.h): the reference bases a CRAM written against an external FASTA leaves out
@@ -312,6 +317,16 @@ class DvAlignedWindowsView(C.Structure):
 
 class DvRealignFinishStats(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('windows', 'windows_on_host', 'reads', 'cigar_words', 'launches', 'bytes_down')]
+
+
+class DvGenotypesView(C.Structure):
+  _fields_ = [('n_sites', C.c_int32), ('reserved', C.c_int32), ('n_items', C.c_int64), ('n_predictions', C.c_int64),
+              ('rounded', C.c_void_p), ('pred_off', C.c_void_p), ('predictions', C.c_void_p), ('best', C.c_void_p),
+              ('removed', C.c_void_p), ('status', C.c_void_p)]
+
+
+class DvGenotypeDeviceStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('sites', 'sites_on_host', 'launches', 'bytes_down')]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -690,6 +705,16 @@ def lib():
     l.dv_windows_free.argtypes = [C.c_void_p]
     l.dv_windows_free.restype = None
     l.dv_count_batch_last_stats.argtypes = [C.c_void_p]
+    l.dv_genotype_sites.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                    C.c_int32, C.c_void_p]
+    l.dv_genotype_sites_device.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    l.dv_genotypes_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_genotypes_free.argtypes = [C.c_void_p]
+    l.dv_genotypes_free.restype = None
+    l.dv_genotype_min_nonref_prob.argtypes = [C.c_double]
+    l.dv_genotype_min_nonref_prob.restype = C.c_double
+    l.dv_genotype_device_last_stats.argtypes = [C.c_void_p]
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -140,6 +140,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
   ap.add_argument('--checkpoint', default='')
   ap.add_argument('--checkpoint_json', default='')
   ap.add_argument('--call_variants_outfile', default='')
+  # not a reference flag: the fused route through postprocess_variants as well -- each site's calls are merged on the
+  # device from the classifier's output and a VCF (.gz by its name) is written; alone or beside --call_variants_outfile
+  ap.add_argument('--vcf_outfile', default='')
+  ap.add_argument('--qual_filter', type=float, default=1.0)
+  ap.add_argument('--cnn_homref_call_min_gq', type=float, default=20.0)
   ap.add_argument('--device', type=int, default=0)
   # not a reference flag: the node-level launcher that stands in for run_deepvariant's N processes
   # (scripts/run_deepvariant.py:457-462) -- N ranks, rank r = task r of --call_variants_outfile name@N,
@@ -240,7 +245,15 @@ def check_flags(args) -> None:
                      '(--ws_use_window_selector_model selects the built-in linear model)')
   if args.call_variants_outfile and not args.checkpoint:
     raise ValueError('--call_variants_outfile needs --checkpoint (the fused route)')
-  if not args.examples and not args.call_variants_outfile:
+  vcf_outfile = getattr(args, 'vcf_outfile', '')
+  if vcf_outfile:
+    if not args.checkpoint:
+      raise ValueError('--vcf_outfile needs --checkpoint (the fused route)')
+    if args.examples:
+      raise ValueError('--examples and --vcf_outfile are two routes: give one of them')
+    if args.gpus * args.ranks_per_gpu > 1:
+      raise ValueError('--vcf_outfile runs on one rank: the multi-rank gather of the sites is not built')
+  if not args.examples and not args.call_variants_outfile and not vcf_outfile:
     raise ValueError('--examples (or --call_variants_outfile with --checkpoint) is required')
   if args.examples and args.call_variants_outfile:
     raise ValueError('--examples and --call_variants_outfile are two routes (tf.Examples, or CallVariantsOutput '
@@ -525,7 +538,13 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
   reads_for = RegionReads(args, ref_reader)
   proc = hooks.make_processor(options, ref_reader, po, args.device)
   model = None
-  if args.call_variants_outfile:
+  vcf_outfile = getattr(args, 'vcf_outfile', '')
+  if vcf_outfile:
+    # each flush of the queue merges its sites' calls on the device and leaves their finished records here
+    proc.vcf = make_examples_core.VcfSink(qual_filter=getattr(args, 'qual_filter', 1.0),
+                                          cnn_homref_call_min_gq=getattr(args, 'cnn_homref_call_min_gq', 20.0),
+                                          want_records=bool(args.call_variants_outfile))
+  if args.call_variants_outfile or vcf_outfile:
     shape = (make_examples_native.calculate_pileup_image_height(options), options.pic_options.width,
              len(options.pic_options.channels))
     model = _BackgroundModel(lambda: hooks.make_model(args, options), shape)
@@ -550,7 +569,7 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
     print('make_examples task %d: %d regions, %d reads, %d candidate positions -> %s' % (
         args.task, stats['n_regions'], stats['n_reads'], stats['n_candidates'], out_path), file=log)
     return stats
-  writer = sink if sink is not None else tfrecord.Writer(out_path)
+  writer = sink if sink is not None else (tfrecord.Writer(out_path) if out_path else _MemorySink())   # --vcf_outfile alone
   image_shape = None
   # the table path (no Read objects between the BAM decoder and the encoder) where the
   # configuration allows it; DV_REGION_OBJECTS=1 forces the object path (A/B, tests)
@@ -634,7 +653,12 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
         in_reads = reservoir_sample(in_reads, args.max_reads_per_partition, np.random.RandomState(_RANDOM_SEED))
       stats['n_regions'] += 1
       stats['n_reads'] += len(in_reads)
-      if model is not None:
+      if model is not None and vcf_outfile:
+        # the queue's route, so that flush_queue sees the region's sites
+        candidates, realigned = proc.process(region, in_reads)
+        proc.queue_region_candidates(candidates, realigned, model.get())
+        records = proc.flush_queue(model.get())[0]
+      elif model is not None:
         candidates, records = proc.call_variants_in_region(region, in_reads, model.get())
       else:
         candidates, records = proc.examples_in_region(region, in_reads)
@@ -649,6 +673,14 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
         stats['n_examples'] += len(records)
     if model is not None:
       model.get()                 # a failed model set-up is an error even when no example asked for it
+    if vcf_outfile:
+      from deepvariant_amd import postprocess_variants
+      records = proc.vcf.records
+      postprocess_variants.write_vcf(vcf_outfile, records, postprocess_variants.fasta_contigs(ref_reader),
+                                     postprocess_variants.default_sample_name(records, args.sample_name or None))
+      stats['n_vcf_records'] = len(records)
+      stats['n_examples'] = proc.vcf.n_examples     # also when no CallVariantsOutput record was asked for
+      stats['genotype_device'] = dict(proc.vcf.device_stats)
   finally:
     writer.close()
   stats['loop_s'] = time.perf_counter() - t_loop   # the region loop proper (BAM decode to the last record written)
@@ -659,7 +691,7 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
       make_examples_native.write_example_info_json(out_path, image_shape, pic.channels)
   print('make_examples task %d: %d regions, %d reads, %d candidates, %d %s -> %s' % (
       args.task, stats['n_regions'], stats['n_reads'], stats['n_candidates'], stats['n_examples'],
-      'CallVariantsOutputs' if model is not None else 'examples', out_path), file=log)
+      'CallVariantsOutputs' if model is not None else 'examples', out_path or vcf_outfile), file=log)
   return stats
 
 

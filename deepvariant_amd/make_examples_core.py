@@ -22,6 +22,7 @@ outside SURVEY.md section 8.
 from __future__ import annotations
 
 import dataclasses
+import os
 import numpy as np
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
@@ -226,6 +227,18 @@ def regions_to_process(contigs, partition_size: int, calling_regions: Optional[S
   return pieces
 
 
+@dataclasses.dataclass
+class VcfSink:
+  """What flush_queue needs to turn the classifier's output into finished VCF records, and where they collect."""
+  qual_filter: float = 1.0
+  cnn_homref_call_min_gq: float = 20.0
+  sample_name: Optional[str] = None
+  want_records: bool = True                  # CallVariantsOutput records beside the VCF
+  n_examples: int = 0                        # classified so far
+  records: List = dataclasses.field(default_factory=list)
+  device_stats: Dict[str, int] = dataclasses.field(default_factory=dict)    # dv_genotype_device_stats, summed
+
+
 class RegionProcessor:
   def __init__(self, options: T.MakeExamplesOptions, ref_reader, processor_options: Optional[RegionProcessorOptions] = None,
                example_filenames: Optional[Dict[str, str]] = None, device: int = 0):
@@ -252,6 +265,7 @@ class RegionProcessor:
     self.gvcf_records: List[List[T.Variant]] = []
     self._queue: List = []
     self.n_queued_examples = 0
+    self.vcf: Optional[VcfSink] = None       # --vcf_outfile: flush_queue merges each site's calls and collects the records
     self.generator = make_examples_native.ExamplesGenerator(
         options, example_filenames or {}, test_mode=not example_filenames, device=device, ref_reader=ref_reader)
 
@@ -554,13 +568,56 @@ class RegionProcessor:
       return [[] for _ in queue]
     limit = model.max_batch
     stacked = torch.cat(tensors) if len(tensors) > 1 else tensors[0]
-    rows = [cv.round_gls_batch(model(stacked[i:i + limit]).cpu().numpy(), 10) for i in range(0, stacked.shape[0], limit)]
-    gls = np.concatenate(rows)
+    if self.vcf is not None:
+      probs = [model(stacked[i:i + limit]) for i in range(0, stacked.shape[0], limit)]
+      gls = self._genotype_queue(queue, torch.cat(probs) if len(probs) > 1 else probs[0])
+      if not self.vcf.want_records:
+        return [[] for _ in queue]
+    else:
+      rows = [cv.round_gls_batch(model(stacked[i:i + limit]).cpu().numpy(), 10) for i in range(0, stacked.shape[0], limit)]
+      gls = np.concatenate(rows)
     at = 0
     for candidates, plan, _ in queue:
       out.append(self.generator.call_variants_outputs(candidates, plan, gls[at:at + len(plan)]) if plan else [])
       at += len(plan)
     return out
+
+  @staticmethod
+  def queue_sites(queue):
+    """The queue's plans as sites: -> ([the variant of each site], postprocess_variants.site_tables of them).  A site
+    is one candidate, its items the plan's examples of it, which follow each other."""
+    from deepvariant_amd import postprocess_variants as pp
+    variants, sites = [], []
+    for candidates, plan, _ in queue:
+      last = None
+      for ci, combo in plan:
+        variant = candidates[ci].variant
+        if ci != last:
+          variants.append(variant)
+          sites.append((len(variant.alternate_bases), []))
+          last = ci
+        sites[-1][1].append(sorted(make_examples_native.encode_alt_alleles(variant, combo)[1]))
+    return variants, pp.site_tables(sites)
+
+  def _genotype_queue(self, queue, probs) -> np.ndarray:
+    """--vcf_outfile: the queue's sites merged on the device from the classifier's output tensor where it lies
+    (postprocess_variants.genotype_sites_device; DV_GENOTYPE_HOST=1: downloaded and merged by the host code), their
+    finished records added to self.vcf.records.  A site is one candidate, its items the plan's examples of it.
+    -> the rounded likelihood rows, float64 [N, 3], what round_gls_batch gives."""
+    from deepvariant_amd import postprocess_variants as pp
+    variants, tables = self.queue_sites(queue)
+    vcf = self.vcf
+    vcf.n_examples += int(probs.shape[0])
+    if os.environ.get('DV_GENOTYPE_HOST', '0') not in ('', '0'):
+      result = pp.genotype_sites(probs.cpu().numpy(), *tables, qual_filter=vcf.qual_filter)
+    else:
+      result = pp.genotype_sites_device(probs.contiguous(), *tables, qual_filter=vcf.qual_filter)
+      stats = pp.last_device_stats()
+      for name, value in stats.items():
+        vcf.device_stats[name] = vcf.device_stats.get(name, 0) + value
+    pp.check_status(result, lambda i: probs[i].cpu().numpy(), tables[1], lambda s: pp.describe_variant(variants[s]))
+    vcf.records.extend(pp.finish_sites(variants, result, vcf.qual_filter, vcf.cnn_homref_call_min_gq, vcf.sample_name))
+    return result.rounded
 
   def examples_in_region(self, region: T.Range, reads: Sequence, stats: Optional[dict] = None
                          ) -> Tuple[List[T.DeepVariantCall], List[bytes]]:

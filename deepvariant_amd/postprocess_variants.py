@@ -1,0 +1,430 @@
+"""MI355X `postprocess_variants`: CallVariantsOutput records -> one genotype, GQ and QUAL per site -> VCF.
+
+This project's restatement of the reference's `deepvariant/postprocess_variants.py` (`merge_predictions`,
+`get_alt_alleles_to_remove`, `convert_call_variants_outputs_to_probs_dict`, `add_call_to_variant`, `compute_quals`)
+and nucleus `genomics_math.py`; DESIGN.md section 21 is the contract and lists what is remembered, not pinned.
+
+Steps 1 to 3 (rounding, which alts to drop, the merge) are native: `genotype_sites` is the host code
+(dv_genotype_sites), `genotype_sites_device` the kernel (dv_genotype_sites_device, csrc/genotype.hip), which reads the
+classifier's output tensor where it lies.  Both return the same arrays bit for bit.  Step 4 (`finish_sites`: phred
+scores, the call, pruned and simplified alleles) needs log10 and is one host function for both routes.
+
+  python -m deepvariant_amd.postprocess_variants --infile CVO --ref FASTA --outfile VCF
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import gzip
+import math
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from deepvariant_amd import _lib
+from deepvariant_amd import dv_types as T
+
+_MAX_CONFIDENCE = 1.0 - 1e-15            # genomics_math.ptrue_to_bounded_phred's max_prob
+DEFAULT_QUAL_FILTER = 1.0                # --qual_filter
+DEFAULT_CNN_HOMREF_CALL_MIN_GQ = 20.0    # --cnn_homref_call_min_gq
+OK, BAD_SUM, INCOMPLETE = _lib.DV_GENOTYPE_OK, _lib.DV_GENOTYPE_BAD_SUM, _lib.DV_GENOTYPE_INCOMPLETE
+
+
+# ------------------------------------------------------------------------------------------ steps 1 to 3, native
+@dataclasses.dataclass
+class SiteGenotypes:
+  """One call's arrays (dv_genotypes_view, copied)."""
+  rounded: np.ndarray        # float64 [N, 3]
+  pred_off: np.ndarray       # int64 [S + 1]
+  predictions: np.ndarray    # float64; site s owns [pred_off[s], pred_off[s + 1]), the kept alleles' genotypes first
+  best: np.ndarray           # int32 [S]
+  removed: np.ndarray        # uint32 [S], a bit per removed alt
+  status: np.ndarray         # uint8 [S]
+
+  def n_kept_alts(self, site: int) -> int:
+    slots = int(self.pred_off[site + 1] - self.pred_off[site])
+    alts = (math.isqrt(8 * slots + 1) - 3) // 2
+    return alts - bin(int(self.removed[site])).count('1')
+
+  def site_predictions(self, site: int) -> List[float]:
+    kept = self.n_kept_alts(site)
+    at = int(self.pred_off[site])
+    return self.predictions[at:at + (kept + 1) * (kept + 2) // 2].tolist()
+
+
+def min_nonref_prob(qual_filter: float) -> float:
+  """Step 2's threshold: the smallest probability whose QUAL reaches `qual_filter` (dv_genotype_min_nonref_prob)."""
+  return float(_lib.lib().dv_genotype_min_nonref_prob(float(qual_filter)))
+
+
+def _tables(item_alts, site_off, n_alts):
+  alts = np.ascontiguousarray(item_alts, np.int8).reshape(-1, 2)
+  off = np.ascontiguousarray(site_off, np.int32).reshape(-1)
+  n = np.ascontiguousarray(n_alts, np.int32).reshape(-1)
+  if off.size != n.size + 1:
+    raise ValueError('site_off must have one entry more than n_alts')
+  return alts, off, n
+
+
+def _take(handle) -> SiteGenotypes:
+  l = _lib.lib()
+  try:
+    view = _lib.DvGenotypesView()
+    _lib.check(l.dv_genotypes_arrays(handle, C.byref(view)))
+
+    def array(ptr, count, dtype):
+      if count == 0:
+        return np.zeros(0, dtype)
+      return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
+                                   (count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+    s = view.n_sites
+    return SiteGenotypes(rounded=array(view.rounded, view.n_items * 3, np.float64).reshape(-1, 3),
+                         pred_off=array(view.pred_off, s + 1, np.int64),
+                         predictions=array(view.predictions, view.n_predictions, np.float64),
+                         best=array(view.best, s, np.int32), removed=array(view.removed, s, np.uint32),
+                         status=array(view.status, s, np.uint8))
+  finally:
+    l.dv_genotypes_free(handle)
+
+
+def genotype_sites(probs, item_alts, site_off, n_alts, qual_filter: float = DEFAULT_QUAL_FILTER,
+                   t: Optional[float] = None, already_rounded: bool = False) -> SiteGenotypes:
+  """The host code.  probs float32 [N, 3]; item_alts int8 [N, 2] (the second -1 for one alt); site_off int32
+  [S + 1]; n_alts int32 [S].  `t` overrides min_nonref_prob(qual_filter).  already_rounded: the rows are the rounded
+  values of CallVariantsOutput records and are not rounded again (round_gls is not idempotent in float32)."""
+  p = np.ascontiguousarray(probs, np.float32).reshape(-1, 3)
+  alts, off, n = _tables(item_alts, site_off, n_alts)
+  if alts.shape[0] != p.shape[0]:
+    raise ValueError('one item_alts row per probability row is expected')
+  handle = C.c_void_p()
+  _lib.check(_lib.lib().dv_genotype_sites(p.ctypes.data, p.shape[0], alts.ctypes.data, n.size, off.ctypes.data,
+                                          n.ctypes.data, min_nonref_prob(qual_filter) if t is None else float(t),
+                                          1 if already_rounded else 0, C.byref(handle)))
+  return _take(handle)
+
+
+def genotype_sites_device(probs, item_alts, site_off, n_alts, qual_filter: float = DEFAULT_QUAL_FILTER,
+                          stream=None, t: Optional[float] = None) -> SiteGenotypes:
+  """The same on the device.  `probs` is a float32 [N, 3] NumPy array (staged and uploaded) or a contiguous CUDA
+  tensor, read in place: on the tensor's current stream, or -- when that is the default stream -- after waiting for
+  it, on a stream the library owns.  `stream` (a raw handle) overrides; `t` as in genotype_sites."""
+  alts, off, n = _tables(item_alts, site_off, n_alts)
+  if isinstance(probs, np.ndarray):
+    p = np.ascontiguousarray(probs, np.float32).reshape(-1, 3)
+    pointer, memory, rows = p.ctypes.data, _lib.DV_MEM_HOST, p.shape[0]
+  else:
+    import torch  # device memory + stream only
+    p = probs
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.dim() != 2 or p.shape[1] != 3:
+      raise ValueError('a contiguous float32 [N, 3] CUDA tensor is expected')
+    pointer, memory, rows = p.data_ptr(), _lib.DV_MEM_DEVICE, p.shape[0]
+    if stream is None:
+      current = torch.cuda.current_stream(p.device)
+      stream = current.cuda_stream
+      if not stream:
+        current.synchronize()
+  if alts.shape[0] != rows:
+    raise ValueError('one item_alts row per probability row is expected')
+  handle = C.c_void_p()
+  _lib.check(_lib.lib().dv_genotype_sites_device(pointer, memory, rows, alts.ctypes.data, n.size, off.ctypes.data,
+                                                 n.ctypes.data, min_nonref_prob(qual_filter) if t is None else float(t),
+                                                 C.byref(handle), C.c_void_p(stream or None)))
+  return _take(handle)
+
+
+def last_device_stats() -> Dict[str, int]:
+  stats = _lib.DvGenotypeDeviceStats()
+  _lib.check(_lib.lib().dv_genotype_device_last_stats(C.byref(stats)))
+  return {name: int(getattr(stats, name)) for name, _ in stats._fields_}
+
+
+def site_tables(sites: Sequence[Tuple[int, Sequence[Sequence[int]]]]):
+  """[(n_alts, [the alt indices of each item])] -> (item_alts, site_off, n_alts)."""
+  item_alts, site_off, n_alts = [], [0], []
+  for alts, items in sites:
+    for indices in items:
+      indices = list(indices)
+      if not 1 <= len(indices) <= 2:
+        raise ValueError('an item names one or two alts, got %s' % (indices,))
+      item_alts.append((indices[0], indices[1] if len(indices) == 2 else -1))
+    site_off.append(len(item_alts))
+    n_alts.append(alts)
+  return (np.array(item_alts, np.int8).reshape(-1, 2), np.array(site_off, np.int32), np.array(n_alts, np.int32))
+
+
+def check_status(result: SiteGenotypes, probs_row, site_off, describe) -> None:
+  """BAD_SUM raises round_gls' ValueError, INCOMPLETE a ValueError naming the site.  probs_row(i) -> item i's
+  float32 probabilities; describe(s) -> text for site s."""
+  bad = np.nonzero(result.status != OK)[0]
+  if not bad.size:
+    return
+  site = int(bad[0])
+  if result.status[site] == BAD_SUM:
+    for i in range(int(site_off[site]), int(site_off[site + 1])):
+      row = np.asarray(probs_row(i), np.float32)
+      total = (row[0] + row[1]) + row[2]
+      if np.abs(total - np.float32(1)) > np.float32(1e-6):
+        raise ValueError('Invalid genotype likelihoods do not sum to one: sum({}) = {}'.format(list(row), total))
+  raise ValueError('%s: its examples do not cover every genotype of its alleles' % describe(site))
+
+
+# ------------------------------------------------------------------------------------------ step 4, host
+def _phred(p: float) -> float:
+  """genomics_math.ptrue_to_bounded_phred."""
+  return -10.0 * math.log10(1.0 - min(p, _MAX_CONFIDENCE))
+
+
+def compute_quals(predictions: Sequence[float], prediction_index: int) -> Tuple[int, float]:
+  """-> (GQ, QUAL): the phred of the called genotype, and of any non-reference genotype."""
+  gq = int(np.around(_phred(predictions[prediction_index])))
+  qual = round(_phred(min(sum(predictions[1:]), 1.0)), 7)
+  return gq, qual
+
+
+def most_likely_genotype(predictions: Sequence[float]) -> Tuple[int, List[int]]:
+  """-> (the first index of the largest prediction, its diploid genotype in VCF order)."""
+  index = max(range(len(predictions)), key=predictions.__getitem__)
+  return index, genotype_of_index(index)
+
+
+def genotype_of_index(index: int) -> List[int]:
+  b = (math.isqrt(8 * index + 1) - 1) // 2
+  return [index - b * (b + 1) // 2, b]
+
+
+def _call_values(variant: T.Variant, key: str) -> Optional[list]:
+  if not variant.calls or key not in variant.calls[0].info:
+    return None
+  out = []
+  for v in variant.calls[0].info[key].values:
+    out.append(v.int_value if v.int_value is not None else v.number_value)
+  return out
+
+
+def prune_alleles(variant: T.Variant, removed: int):
+  """-> (alts, AD, VAF) without the alts whose bit is set in `removed`; AD keeps its leading reference entry."""
+  keep = [a for a in range(len(variant.alternate_bases)) if not (removed >> a) & 1]
+  ad, vaf = _call_values(variant, 'AD'), _call_values(variant, 'VAF')
+  if ad is not None and len(ad) == len(variant.alternate_bases) + 1:
+    ad = [ad[0]] + [ad[a + 1] for a in keep]
+  if vaf is not None and len(vaf) == len(variant.alternate_bases):
+    vaf = [vaf[a] for a in keep]
+  return [variant.alternate_bases[a] for a in keep], ad, vaf
+
+
+def simplify_variant_alleles(ref: str, alts: Sequence[str]) -> Tuple[str, List[str]]:
+  """Strips the longest common suffix of the reference and every alt, leaving at least one base each."""
+  alleles = [ref] + list(alts)
+  shortest = min(len(a) for a in alleles)
+  strip = 0
+  while strip < shortest - 1 and len({a[len(a) - 1 - strip] for a in alleles}) == 1:
+    strip += 1
+  if not strip:
+    return ref, list(alts)
+  return ref[:-strip], [a[:-strip] for a in alts]
+
+
+@dataclasses.dataclass
+class VcfRecord:
+  reference_name: str
+  start: int
+  end: int
+  reference_bases: str
+  alternate_bases: List[str]
+  quality: float
+  filter: str
+  genotype: List[int]
+  gq: int
+  genotype_likelihood: List[float]
+  dp: Optional[int] = None
+  ad: Optional[List[int]] = None
+  vaf: Optional[List[float]] = None
+  call_set_name: str = ''
+
+
+def add_call_to_variant(variant: T.Variant, predictions: Sequence[float], best: int, removed: int = 0,
+                        qual_filter: float = DEFAULT_QUAL_FILTER,
+                        cnn_homref_call_min_gq: float = DEFAULT_CNN_HOMREF_CALL_MIN_GQ,
+                        sample_name: Optional[str] = None) -> VcfRecord:
+  """Step 4 for one site: the merged predictions of its kept alleles -> the finished record."""
+  gq, qual = compute_quals(predictions, best)
+  genotype = genotype_of_index(best)
+  if genotype == [0, 0]:
+    filter_name = 'RefCall'
+    if gq < cnn_homref_call_min_gq:
+      genotype = [-1, -1]
+  else:
+    filter_name = 'LowQual' if qual < qual_filter else 'PASS'
+  gls = [math.log10(max(p, 1.0 - _MAX_CONFIDENCE)) for p in predictions]
+  alts, ad, vaf = prune_alleles(variant, removed)
+  ref, alts = simplify_variant_alleles(variant.reference_bases, alts)
+  dp = _call_values(variant, 'DP')
+  name = sample_name if sample_name is not None else (variant.calls[0].call_set_name if variant.calls else '')
+  return VcfRecord(reference_name=variant.reference_name, start=variant.start, end=variant.start + len(ref),
+                   reference_bases=ref, alternate_bases=alts, quality=qual, filter=filter_name, genotype=genotype,
+                   gq=gq, genotype_likelihood=gls, dp=dp[0] if dp else None, ad=ad, vaf=vaf, call_set_name=name)
+
+
+def finish_sites(variants: Sequence[T.Variant], result: SiteGenotypes, qual_filter: float = DEFAULT_QUAL_FILTER,
+                 cnn_homref_call_min_gq: float = DEFAULT_CNN_HOMREF_CALL_MIN_GQ,
+                 sample_name: Optional[str] = None) -> List[VcfRecord]:
+  """Step 4 for the sites of one native call, whichever side made it."""
+  return [add_call_to_variant(v, result.site_predictions(s), int(result.best[s]), int(result.removed[s]), qual_filter,
+                              cnn_homref_call_min_gq, sample_name) for s, v in enumerate(variants)]
+
+
+def merge_predictions(call_variants_outputs, qual_filter: float = DEFAULT_QUAL_FILTER):
+  """One site's (variant, alt indices, probabilities) triples, in any order -> (removed alts' bit mask, the merged
+  predictions of the kept alleles, the index of the best) by the host code."""
+  items = sorted(call_variants_outputs, key=lambda c: (len(c[1]), list(c[1])))
+  variant = items[0][0]
+  tables = site_tables([(len(variant.alternate_bases), [c[1] for c in items])])
+  probs = np.array([c[2] for c in items], np.float32).reshape(-1, 3)
+  result = genotype_sites(probs, *tables, qual_filter=qual_filter, already_rounded=True)
+  check_status(result, lambda i: probs[i], tables[1], lambda s: describe_variant(variant))
+  return int(result.removed[0]), result.site_predictions(0), int(result.best[0])
+
+
+def describe_variant(variant: T.Variant) -> str:
+  return '%s:%d %s>%s' % (variant.reference_name, variant.start + 1, variant.reference_bases,
+                          ','.join(variant.alternate_bases))
+
+
+# ------------------------------------------------------------------------------------------ the VCF writer
+_HEADER = (
+    '##fileformat=VCFv4.2',
+    '##FILTER=<ID=PASS,Description="All filters passed">',
+    '##FILTER=<ID=RefCall,Description="Genotyping model thinks this site is reference.">',
+    '##FILTER=<ID=LowQual,Description="Confidence in this variant being real is below calling threshold.">',
+    '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">',
+    '##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Conditional genotype quality">',
+    '##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Read depth">',
+    '##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Read depth for each allele">',
+    '##FORMAT=<ID=VAF,Number=A,Type=Float,Description="Variant allele fractions.">',
+    '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods rounded to the closest integer">',
+)
+
+
+def vcf_header(contigs: Iterable[Tuple[str, int]], sample_name: str) -> str:
+  lines = list(_HEADER)
+  lines += ['##contig=<ID=%s,length=%d>' % (name, length) for name, length in contigs]
+  lines.append('\t'.join(['#CHROM', 'POS', 'ID', 'REF', 'ALT', 'QUAL', 'FILTER', 'INFO', 'FORMAT', sample_name]))
+  return '\n'.join(lines) + '\n'
+
+
+def vcf_row(r: VcfRecord) -> str:
+  pls = [int(round(-10 * gl)) for gl in r.genotype_likelihood]
+  low = min(pls)
+  sample = [
+      '/'.join('.' if g < 0 else str(g) for g in r.genotype),
+      str(r.gq),
+      '.' if r.dp is None else str(r.dp),
+      '.' if r.ad is None else ','.join(str(v) for v in r.ad),
+      '.' if not r.vaf else ','.join('%g' % v for v in r.vaf),
+      ','.join(str(pl - low) for pl in pls),
+  ]
+  return '\t'.join([r.reference_name, str(r.start + 1), '.', r.reference_bases,
+                    ','.join(r.alternate_bases) if r.alternate_bases else '.',
+                    '%g' % (round(r.quality, 1) + 0.0),     # + 0.0: a phred of -0.0 prints as 0
+                    r.filter, '.', 'GT:GQ:DP:AD:VAF:PL', ':'.join(sample)]) + '\n'
+
+
+def vcf_text(records: Sequence[VcfRecord], contigs: Sequence[Tuple[str, int]], sample_name: str) -> str:
+  """Header and rows, the rows sorted by (contig order, start, end), stable."""
+  order = {name: k for k, (name, _) in enumerate(contigs)}
+  for r in records:
+    if r.reference_name not in order:
+      raise ValueError('%s is not a contig of the reference' % r.reference_name)
+  rows = sorted(records, key=lambda r: (order[r.reference_name], r.start, r.end))
+  return vcf_header(contigs, sample_name) + ''.join(vcf_row(r) for r in rows)
+
+
+def write_vcf(path: str, records: Sequence[VcfRecord], contigs: Sequence[Tuple[str, int]], sample_name: str) -> None:
+  data = vcf_text(records, contigs, sample_name).encode()
+  with open(path, 'wb') as f:
+    if path.endswith('.gz'):
+      with gzip.GzipFile(filename='', fileobj=f, mode='wb', mtime=0) as z:     # the same bytes on every run
+        z.write(data)
+    else:
+      f.write(data)
+
+
+def fasta_contigs(ref_reader) -> List[Tuple[str, int]]:
+  return [(name, ref_reader.n_bases(name)) for name in ref_reader.contig_names()]
+
+
+def default_sample_name(records: Sequence[VcfRecord], sample_name: Optional[str]) -> str:
+  if sample_name:
+    return sample_name
+  for r in records:
+    if r.call_set_name:
+      return r.call_set_name
+  return 'default'
+
+
+# ------------------------------------------------------------------------------------------ CVO records -> VCF
+def records_from_cvos(cvos, qual_filter: float = DEFAULT_QUAL_FILTER,
+                      cnn_homref_call_min_gq: float = DEFAULT_CNN_HOMREF_CALL_MIN_GQ,
+                      sample_name: Optional[str] = None) -> List[VcfRecord]:
+  """Decoded CallVariantsOutputs (variant, alt indices, probabilities) in any order -> the finished records of their
+  sites.  A site is the records that share (contig, start, end, ref, alts); the host code merges them all at once."""
+  groups: Dict[tuple, list] = {}
+  for variant, alts, probs in cvos:
+    if len(probs) != 3:
+      raise ValueError('%s: three genotype probabilities are expected' % describe_variant(variant))
+    key = (variant.reference_name, variant.start, variant.end, variant.reference_bases, tuple(variant.alternate_bases))
+    groups.setdefault(key, []).append((variant, sorted(set(alts)), probs))
+  keys = sorted(groups)
+  variants, sites, rows = [], [], []
+  for key in keys:
+    items = sorted(groups[key], key=lambda c: (len(c[1]), c[1]))
+    variants.append(items[0][0])
+    sites.append((len(key[4]), [c[1] for c in items]))
+    rows.extend(c[2] for c in items)
+  if not variants:
+    return []
+  tables = site_tables(sites)
+  probs = np.array(rows, np.float32).reshape(-1, 3)
+  result = genotype_sites(probs, *tables, qual_filter=qual_filter, already_rounded=True)
+  check_status(result, lambda i: probs[i], tables[1], lambda s: describe_variant(variants[s]))
+  return finish_sites(variants, result, qual_filter, cnn_homref_call_min_gq, sample_name)
+
+
+def postprocess_variants(infile: str, ref: str, outfile: str, qual_filter: float = DEFAULT_QUAL_FILTER,
+                         cnn_homref_call_min_gq: float = DEFAULT_CNN_HOMREF_CALL_MIN_GQ,
+                         sample_name: Optional[str] = None) -> int:
+  """-> the number of rows written."""
+  from deepvariant_amd import call_variants, genomics_io, protowire, tfrecord
+  cvos = []
+  for path in call_variants.sharded_paths(infile):
+    for rec in tfrecord.read_tfrecords(path):
+      cvos.append(protowire.decode_call_variants_output(rec))
+  records = records_from_cvos(cvos, qual_filter, cnn_homref_call_min_gq, sample_name)
+  write_vcf(outfile, records, fasta_contigs(genomics_io.FastaReader(ref)), default_sample_name(records, sample_name))
+  return len(records)
+
+
+def build_arg_parser():
+  import argparse
+  ap = argparse.ArgumentParser(prog='postprocess_variants', allow_abbrev=False,
+                               description='MI355X postprocess_variants: CallVariantsOutput TFRecords -> VCF')
+  ap.add_argument('--infile', required=True)
+  ap.add_argument('--ref', required=True)
+  ap.add_argument('--outfile', required=True)
+  ap.add_argument('--qual_filter', type=float, default=DEFAULT_QUAL_FILTER)
+  ap.add_argument('--cnn_homref_call_min_gq', type=float, default=DEFAULT_CNN_HOMREF_CALL_MIN_GQ)
+  ap.add_argument('--sample_name', default=None)
+  return ap
+
+
+def main(argv=None) -> int:
+  args = build_arg_parser().parse_args(argv)
+  n = postprocess_variants(args.infile, args.ref, args.outfile, args.qual_filter, args.cnn_homref_call_min_gq,
+                           args.sample_name)
+  print('postprocess_variants: wrote %d records' % n)
+  return 0
+
+
+if __name__ == '__main__':
+  import sys
+  sys.exit(main())

@@ -1728,6 +1728,68 @@ double dv_profile_ms(int kind);
 /* Number of launches summed by the last dv_profile_ms call. */
 int dv_last_profile_count(void);
 
+/* ---- postprocess_variants: the genotype merge of each site (csrc/genotype.hip) ----
+ * A site is one candidate; its items are its images, contiguous: site s owns items [site_off[s], site_off[s + 1]).
+ * Item i carries the classifier's probs[i][0..2] and one or two 0-based alt indices item_alts[i][0..1], the second -1
+ * for a single alt.  Per item the probabilities are rounded as call_variants.round_gls_batch(p, 10) does (float32,
+ * then widened); per site with more than one item and t > 0, alt a is removed when the largest min(r1 + r2, 1) over
+ * its single-alt items is < t (an alt without such an item stays; were all removed, the one with the largest value
+ * stays, the first on ties); the items that name no removed alt are merged by the minimum per genotype of the kept
+ * alleles, in VCF order, and divided by their left-to-right sum (a site of exactly one item is neither pruned nor
+ * renormalised).  `t` is dv_genotype_min_nonref_prob(qual_filter).
+ * Results, bit-identical from both entry points: rounded [N][3]; pred_off [S + 1], site s owning
+ * (A + 1)(A + 2) / 2 slots of `predictions` by its n_alts A, the first (A' + 1)(A' + 2) / 2 valid for its A' kept
+ * alts and the rest 0; best [S], the first index of the largest prediction; removed [S], bit a set for a removed alt;
+ * status [S].  DV_GENOTYPE_BAD_SUM: an item's float32 sum is off by more than 1e-6 (it outranks INCOMPLETE; the site's
+ * other results are computed all the same).  DV_GENOTYPE_INCOMPLETE: a genotype of the kept alleles got no
+ * contribution; its slot is +inf, the site's slots are not renormalised and best is -1.
+ * Null pointers with non-zero counts or negative counts: DV_ERR_INVALID_ARGUMENT.  site_off that does not ascend from
+ * 0 to n_items, n_alts outside 1..32, an alt index outside [0, A) or a second index equal to the first:
+ * DV_ERR_BAD_INPUT.  On any error *out is NULL and nothing stays allocated. */
+#define DV_GENOTYPE_DEVICE_MAX_ALTS 6 /* 28 genotypes; and at most 21 items, alt_allele_combinations of 6 alts */
+enum { DV_GENOTYPE_OK = 0, DV_GENOTYPE_BAD_SUM = 1, DV_GENOTYPE_INCOMPLETE = 2 };
+typedef struct dv_genotypes dv_genotypes; /* owns the host arrays of one call's result */
+typedef struct dv_genotypes_view {        /* views into the result; valid until dv_genotypes_free */
+  int32_t n_sites;
+  int32_t reserved;
+  int64_t n_items;
+  int64_t n_predictions;
+  const double* rounded;
+  const int64_t* pred_off;
+  const double* predictions;
+  const int32_t* best;
+  const uint32_t* removed;
+  const uint8_t* status;
+} dv_genotypes_view;
+/* Host code: the twin every test compares against.  already_rounded != 0: `probs` holds the rounded values of an
+ * earlier run (CallVariantsOutput records; the rounding is not idempotent) and is widened as it is; the sum is still
+ * checked. */
+int dv_genotype_sites(const float* probs, int64_t n_items, const int8_t* item_alts, int32_t n_sites,
+                      const int32_t* site_off, const int32_t* n_alts, double t, int32_t already_rounded,
+                      dv_genotypes** out);
+/* The same in one launch, one lane per site; `probs` is read where it lies (probs_memory: dv_memory), the other
+ * tables are host arrays.  One staged upload, one download, one synchronisation on `stream` (NULL = a non-blocking
+ * stream the library owns; device-resident probs must then be complete before the call).  A site with more than
+ * DV_GENOTYPE_DEVICE_MAX_ALTS alts or more than 21 items is merged by the host code inside the call and counted; a
+ * call without any other site launches nothing.  No site is DV_OK without a device; no device is DV_ERR_NO_DEVICE. */
+int dv_genotype_sites_device(const float* probs, int32_t probs_memory, int64_t n_items, const int8_t* item_alts,
+                             int32_t n_sites, const int32_t* site_off, const int32_t* n_alts, double t,
+                             dv_genotypes** out, void* stream);
+int dv_genotypes_arrays(const dv_genotypes* g, dv_genotypes_view* out);
+void dv_genotypes_free(dv_genotypes* g);
+/* The smallest double t in [0, 1] with round(-10 * log10(1 - min(t, 1 - 1e-15)), 7) >= qual_filter (Python's round),
+ * by bisection over the bit patterns: `s < t` then decides what `QUAL(s) < qual_filter` decides, without a logarithm.
+ * 0 for qual_filter <= 0; +inf when no t qualifies. */
+double dv_genotype_min_nonref_prob(double qual_filter);
+typedef struct dv_genotype_device_stats {
+  int64_t sites;         /* of the call */
+  int64_t sites_on_host; /* of them above the device limit: merged by the host code */
+  int64_t launches;
+  int64_t bytes_down;
+} dv_genotype_device_stats;
+/* What the calling thread's last dv_genotype_sites_device did. */
+int dv_genotype_device_last_stats(dv_genotype_device_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
