@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     'dv_select_windows_batch', 'dv_windows_arrays', 'dv_windows_free', 'dv_count_batch_last_stats',
     'dv_genotype_sites', 'dv_genotype_sites_device', 'dv_genotypes_arrays', 'dv_genotypes_free',
     'dv_genotype_min_nonref_prob', 'dv_genotype_device_last_stats',
+    'dv_gvcf_merge', 'dv_gvcf_merge_device', 'dv_gvcf_merged_arrays', 'dv_gvcf_merged_free',
+    'dv_gvcf_merge_scan_chunk', 'dv_gvcf_merge_last_stats',
 ]
 
 DV_GENOTYPE_DEVICE_MAX_ALTS = 6
@@ -327,6 +329,15 @@ class DvGenotypesView(C.Structure):
 
 class DvGenotypeDeviceStats(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('sites', 'sites_on_host', 'launches', 'bytes_down')]
+
+
+class DvGvcfMergedView(C.Structure):
+  _fields_ = [('n_pieces', C.c_int64), ('n_variants', C.c_int64), ('piece_start', C.c_void_p), ('piece_end', C.c_void_p),
+              ('piece_block', C.c_void_p), ('piece_slot', C.c_void_p), ('var_slot', C.c_void_p)]
+
+
+class DvGvcfMergeStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('blocks', 'variants', 'pieces', 'launches', 'bytes_up', 'bytes_down')]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -715,6 +726,14 @@ def lib():
     l.dv_genotype_min_nonref_prob.argtypes = [C.c_double]
     l.dv_genotype_min_nonref_prob.restype = C.c_double
     l.dv_genotype_device_last_stats.argtypes = [C.c_void_p]
+    l.dv_gvcf_merge.argtypes = [C.c_int32] + [C.c_void_p] * 7
+    l.dv_gvcf_merge_device.argtypes = [C.c_int32] + [C.c_void_p] * 8
+    l.dv_gvcf_merged_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_gvcf_merged_free.argtypes = [C.c_void_p]
+    l.dv_gvcf_merged_free.restype = None
+    l.dv_gvcf_merge_scan_chunk.argtypes = []
+    l.dv_gvcf_merge_scan_chunk.restype = C.c_int32
+    l.dv_gvcf_merge_last_stats.argtypes = [C.c_void_p]
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

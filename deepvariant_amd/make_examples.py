@@ -143,6 +143,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
   # not a reference flag: the fused route through postprocess_variants as well -- each site's calls are merged on the
   # device from the classifier's output and a VCF (.gz by its name) is written; alone or beside --call_variants_outfile
   ap.add_argument('--vcf_outfile', default='')
+  # the reference's postprocess_variants flag, here on the fused route: the allele counter's reference-confidence
+  # blocks merged with the finished records after the last flush and written as a gVCF (.gz by its
+  # name); alone or beside --vcf_outfile and / or --call_variants_outfile.  --gvcf itself (the TFRecord output) stays
+  # refused
+  ap.add_argument('--gvcf_outfile', default='')
+  ap.add_argument('--gvcf_gq_binsize', type=int, default=5)
+  ap.add_argument('--include_med_dp', default='false', **boolean)
   ap.add_argument('--qual_filter', type=float, default=1.0)
   ap.add_argument('--cnn_homref_call_min_gq', type=float, default=20.0)
   ap.add_argument('--device', type=int, default=0)
@@ -253,7 +260,17 @@ def check_flags(args) -> None:
       raise ValueError('--examples and --vcf_outfile are two routes: give one of them')
     if args.gpus * args.ranks_per_gpu > 1:
       raise ValueError('--vcf_outfile runs on one rank: the multi-rank gather of the sites is not built')
-  if not args.examples and not args.call_variants_outfile and not vcf_outfile:
+  gvcf_outfile = getattr(args, 'gvcf_outfile', '')
+  if gvcf_outfile:
+    if not args.checkpoint:
+      raise ValueError('--gvcf_outfile needs --checkpoint (the fused route)')
+    if args.examples:
+      raise ValueError('--examples and --gvcf_outfile are two routes: give one of them')
+    if args.gpus * args.ranks_per_gpu > 1:
+      raise ValueError('--gvcf_outfile runs on one rank: the multi-rank gather of the sites and blocks is not built')
+    if getattr(args, 'gvcf_gq_binsize', 5) < 1:
+      raise ValueError('--gvcf_gq_binsize must be positive')
+  if not args.examples and not args.call_variants_outfile and not vcf_outfile and not gvcf_outfile:
     raise ValueError('--examples (or --call_variants_outfile with --checkpoint) is required')
   if args.examples and args.call_variants_outfile:
     raise ValueError('--examples and --call_variants_outfile are two routes (tf.Examples, or CallVariantsOutput '
@@ -325,7 +342,10 @@ def options_from_flags(args):
       keep_legacy_allele_counter_behavior=_true(args.keep_legacy_allele_counter_behavior),
       partition_size=args.partition_size, track_ref_reads=_true(args.track_ref_reads),
       phase_reads=_true(args.phase_reads), phase_max_candidates=args.phase_max_candidates,
-      min_alleles_to_phase=args.min_alleles_to_phase)
+      min_alleles_to_phase=args.min_alleles_to_phase,
+      # --gvcf_outfile: the regions' blocks come out of the allele-count pass as arrays; no Variant is made per block
+      gvcf=bool(getattr(args, 'gvcf_outfile', '')), gvcf_arrays_only=bool(getattr(args, 'gvcf_outfile', '')),
+      gvcf_gq_binsize=getattr(args, 'gvcf_gq_binsize', 5), include_med_dp=_true(getattr(args, 'include_med_dp', 'false')))
   return options, po
 
 
@@ -539,12 +559,20 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
   proc = hooks.make_processor(options, ref_reader, po, args.device)
   model = None
   vcf_outfile = getattr(args, 'vcf_outfile', '')
-  if vcf_outfile:
+  gvcf_outfile = getattr(args, 'gvcf_outfile', '')
+  gvcf_arrays: dict = {}          # --gvcf_outfile: {contig: [every region's block array]}
+
+  def keep_blocks(regions):
+    if gvcf_outfile:
+      for region, blocks in zip(regions, proc.gvcf_block_arrays):
+        gvcf_arrays.setdefault(region.reference_name, []).append(blocks)
+
+  if vcf_outfile or gvcf_outfile:
     # each flush of the queue merges its sites' calls on the device and leaves their finished records here
     proc.vcf = make_examples_core.VcfSink(qual_filter=getattr(args, 'qual_filter', 1.0),
                                           cnn_homref_call_min_gq=getattr(args, 'cnn_homref_call_min_gq', 20.0),
                                           want_records=bool(args.call_variants_outfile))
-  if args.call_variants_outfile or vcf_outfile:
+  if args.call_variants_outfile or vcf_outfile or gvcf_outfile:
     shape = (make_examples_native.calculate_pileup_image_height(options), options.pic_options.width,
              len(options.pic_options.channels))
     model = _BackgroundModel(lambda: hooks.make_model(args, options), shape)
@@ -614,6 +642,7 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
       stats['wait_for_prepared_batches_s'] = stats.get('wait_for_prepared_batches_s', 0.0) + time.perf_counter() - t_wait
       pending = start_batch(at + _REGION_BATCH) if at + _REGION_BATCH < len(pieces) else None
       called = proc.process_tables(batch, tables, realigned_tables)       # the batch's allele counts: one device call
+      keep_blocks(batch)
       if model is not None and packing.pack_device_enabled():
         # DV_PACK_DEVICE=1: the batch's regions packed and drawn together (one pack call, one encoder launch)
         for in_table, (candidates, _) in zip(tables, called):
@@ -653,9 +682,10 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
         in_reads = reservoir_sample(in_reads, args.max_reads_per_partition, np.random.RandomState(_RANDOM_SEED))
       stats['n_regions'] += 1
       stats['n_reads'] += len(in_reads)
-      if model is not None and vcf_outfile:
+      if model is not None and (vcf_outfile or gvcf_outfile):
         # the queue's route, so that flush_queue sees the region's sites
         candidates, realigned = proc.process(region, in_reads)
+        keep_blocks([region])
         proc.queue_region_candidates(candidates, realigned, model.get())
         records = proc.flush_queue(model.get())[0]
       elif model is not None:
@@ -673,11 +703,20 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
         stats['n_examples'] += len(records)
     if model is not None:
       model.get()                 # a failed model set-up is an error even when no example asked for it
-    if vcf_outfile:
+    if vcf_outfile or gvcf_outfile:
       from deepvariant_amd import postprocess_variants
       records = proc.vcf.records
-      postprocess_variants.write_vcf(vcf_outfile, records, postprocess_variants.fasta_contigs(ref_reader),
-                                     postprocess_variants.default_sample_name(records, args.sample_name or None))
+      contigs = postprocess_variants.fasta_contigs(ref_reader)
+      sample_name = postprocess_variants.default_sample_name(records, args.sample_name or None)
+      if vcf_outfile:
+        postprocess_variants.write_vcf(vcf_outfile, records, contigs, sample_name)
+      if gvcf_outfile:
+        # once, after the last flush: every block and every finished record of the run in one native merge call
+        blocks = postprocess_variants.concatenate_blocks(gvcf_arrays)
+        on_device = postprocess_variants.fused_merge_on_device()
+        postprocess_variants.write_gvcf(gvcf_outfile, records, blocks, ref_reader, contigs, sample_name, device=on_device)
+        stats['n_gvcf_blocks'] = sum(len(b) for b in blocks.values())
+        stats['gvcf_merge'] = postprocess_variants.last_merge_stats() if on_device else {}
       stats['n_vcf_records'] = len(records)
       stats['n_examples'] = proc.vcf.n_examples     # also when no CallVariantsOutput record was asked for
       stats['genotype_device'] = dict(proc.vcf.device_stats)
@@ -691,7 +730,7 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
       make_examples_native.write_example_info_json(out_path, image_shape, pic.channels)
   print('make_examples task %d: %d regions, %d reads, %d candidates, %d %s -> %s' % (
       args.task, stats['n_regions'], stats['n_reads'], stats['n_candidates'], stats['n_examples'],
-      'CallVariantsOutputs' if model is not None else 'examples', out_path or vcf_outfile), file=log)
+      'CallVariantsOutputs' if model is not None else 'examples', out_path or vcf_outfile or gvcf_outfile), file=log)
   return stats
 
 

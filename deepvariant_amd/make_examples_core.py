@@ -64,6 +64,8 @@ class RegionProcessorOptions:
   gvcf: bool = False
   gvcf_gq_binsize: int = 5
   include_med_dp: bool = False
+  # the blocks as arrays only (RegionProcessor.gvcf_block_arrays): gvcf_records stays empty, no Variant per block
+  gvcf_arrays_only: bool = False
 
 
 END_OF_REGION = -1        # make_examples_core.py:125-129: markers in a candidate-positions file
@@ -263,6 +265,8 @@ class RegionProcessor:
     # with po.gvcf: the gVCF records of the regions of the last process / process_table(s) call, one list
     # per region in call order (empty for a region without reads, as in the reference)
     self.gvcf_records: List[List[T.Variant]] = []
+    # the same blocks as allelecounter.GVCF_BLOCK_DTYPE arrays, one per region in call order
+    self.gvcf_block_arrays: List[np.ndarray] = []
     self._queue: List = []
     self.n_queued_examples = 0
     self.vcf: Optional[VcfSink] = None       # --vcf_outfile: flush_queue merges each site's calls and collects the records
@@ -300,6 +304,7 @@ class RegionProcessor:
     po = self.processor_options
     in_region = [r for r in reads if utils.ranges_overlap(utils.read_range(r), region)]
     self.gvcf_records = [[]] if po.gvcf else []
+    self.gvcf_block_arrays = [np.zeros(0, allelecounter.GVCF_BLOCK_DTYPE)] if po.gvcf else []
     if not in_region:
       return []
     effective = padded_region or region
@@ -313,7 +318,7 @@ class RegionProcessor:
       # summary_counts(left_padding, right_padding): the padding of a padded region is not reported
       opts = self._gvcf_options(region.start - effective.start, effective.end - region.end)
       allelecounter.AlleleCounter.run_batch([counter], gvcf=opts, **self._device_call())
-      self.gvcf_records = [counter.gvcf_blocks(opts)]
+      self._keep_gvcf(0, counter, opts)
     candidates = self.variant_caller.calls_from_allele_counter(counter)
     if self.direct_phasing is not None:
       to_phase = [r for r in in_region if utils.ranges_overlap(utils.read_range(r), effective)]
@@ -334,6 +339,12 @@ class RegionProcessor:
     if getattr(allelecounter.AlleleCounter, 'candidates', None) is None:
       return {}
     return {'call': self.variant_caller.candidate_options(positions_only)}
+
+  def _keep_gvcf(self, k: int, counter, opts) -> None:
+    """Region k's blocks from its counter: the array, and the Variant records unless gvcf_arrays_only."""
+    self.gvcf_block_arrays[k] = counter.gvcf_block_array(opts)
+    if not self.processor_options.gvcf_arrays_only:
+      self.gvcf_records[k] = counter.gvcf_blocks(opts)
 
   def _gvcf_options(self, left_padding: int = 0, right_padding: int = 0) -> 'variant_calling.GvcfOptions':
     caller_options = self.variant_caller._options          # pylint: disable=protected-access
@@ -455,17 +466,18 @@ class RegionProcessor:
     if po.gvcf:
       # the same counts, with the regions' gVCF blocks computed behind them on the device
       self.gvcf_records = [[] for _ in regions]
+      self.gvcf_block_arrays = [np.zeros(0, allelecounter.GVCF_BLOCK_DTYPE) for _ in regions]
       if po.phase_reads:
         # summary_counts(left_padding, right_padding): the padding of a padded region is not reported
         for k, counter in zip(slots, counters):
           opts = self._gvcf_options(regions[k].start - effective[k].start, effective[k].end - regions[k].end)
           allelecounter.AlleleCounter.run_batch([counter], gvcf=opts, **self._device_call())
-          self.gvcf_records[k] = counter.gvcf_blocks(opts)
+          self._keep_gvcf(k, counter, opts)
       else:
         opts = self._gvcf_options()
         allelecounter.AlleleCounter.run_batch(counters, gvcf=opts, **self._device_call())
         for k, counter in zip(slots, counters):
-          self.gvcf_records[k] = counter.gvcf_blocks(opts)
+          self._keep_gvcf(k, counter, opts)
     else:
       run_batch(counters, **self._device_call())
     phased = self._phase_tables(slots, counters, in_region, rows_of, realigned_tables) if po.phase_reads else {}

@@ -9,7 +9,13 @@ Steps 1 to 3 (rounding, which alts to drop, the merge) are native: `genotype_sit
 classifier's output tensor where it lies.  Both return the same arrays bit for bit.  Step 4 (`finish_sites`: phred
 scores, the call, pruned and simplified alleles) needs log10 and is one host function for both routes.
 
+The gVCF: `merge_blocks_and_variants` (dv_gvcf_merge) and `merge_blocks_and_variants_device`
+(dv_gvcf_merge_device, csrc/gvcf_merge.hip) interleave the reference blocks of the allele counter with the finished
+records -- both return the same arrays -- and `gvcf_text` / `write_gvcf` print the rows.  Blocks travel as
+`allelecounter.GVCF_BLOCK_DTYPE` arrays per contig from end to end; no object is made per block.
+
   python -m deepvariant_amd.postprocess_variants --infile CVO --ref FASTA --outfile VCF
+      [--nonvariant_site_tfrecord_path GVCF_TFRECORDS --gvcf_outfile GVCF]
 """
 from __future__ import annotations
 
@@ -17,6 +23,7 @@ import ctypes as C
 import dataclasses
 import gzip
 import math
+import os
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -305,8 +312,8 @@ _HEADER = (
 )
 
 
-def vcf_header(contigs: Iterable[Tuple[str, int]], sample_name: str) -> str:
-  lines = list(_HEADER)
+def vcf_header(contigs: Iterable[Tuple[str, int]], sample_name: str, extra: Sequence[str] = ()) -> str:
+  lines = list(_HEADER) + list(extra)
   lines += ['##contig=<ID=%s,length=%d>' % (name, length) for name, length in contigs]
   lines.append('\t'.join(['#CHROM', 'POS', 'ID', 'REF', 'ALT', 'QUAL', 'FILTER', 'INFO', 'FORMAT', sample_name]))
   return '\n'.join(lines) + '\n'
@@ -340,7 +347,12 @@ def vcf_text(records: Sequence[VcfRecord], contigs: Sequence[Tuple[str, int]], s
 
 
 def write_vcf(path: str, records: Sequence[VcfRecord], contigs: Sequence[Tuple[str, int]], sample_name: str) -> None:
-  data = vcf_text(records, contigs, sample_name).encode()
+  _write_text(path, vcf_text(records, contigs, sample_name))
+
+
+def _write_text(path: str, text: str) -> None:
+  """GZIP when the name ends in .gz."""
+  data = text.encode()
   with open(path, 'wb') as f:
     if path.endswith('.gz'):
       with gzip.GzipFile(filename='', fileobj=f, mode='wb', mtime=0) as z:     # the same bytes on every run
@@ -360,6 +372,233 @@ def default_sample_name(records: Sequence[VcfRecord], sample_name: Optional[str]
     if r.call_set_name:
       return r.call_set_name
   return 'default'
+
+
+# ------------------------------------------------------------------------------------------ the gVCF merge, native
+@dataclasses.dataclass
+class MergedBlocks:
+  """One call's arrays (dv_gvcf_merged_view, copied): the pieces the variants leave of the blocks, and where every
+  piece and every variant stands in the merged sequence of P + V slots."""
+  piece_start: np.ndarray    # int64 [P]
+  piece_end: np.ndarray      # int64 [P]
+  piece_block: np.ndarray    # int32 [P], the index of the source block in the call
+  piece_slot: np.ndarray     # int64 [P]
+  var_slot: np.ndarray       # int64 [V]
+
+
+def _merge_arguments(block_off, var_off, block_start, block_end, var_start, var_end):
+  arrays = [np.ascontiguousarray(a, np.int64).reshape(-1)
+            for a in (block_off, var_off, block_start, block_end, var_start, var_end)]
+  b_off, v_off, b_start, b_end, v_start, v_end = arrays
+  if b_off.size < 1 or b_off.size != v_off.size:
+    raise ValueError('block_off and var_off must have one entry per group and one more')
+  if b_start.size != b_end.size or v_start.size != v_end.size:
+    raise ValueError('one end per start is expected')
+  if int(b_off[-1]) != b_start.size or int(v_off[-1]) != v_start.size:
+    raise ValueError('the offsets must end at the number of blocks and of variants')
+  return arrays
+
+
+def _take_merged(handle) -> MergedBlocks:
+  l = _lib.lib()
+  try:
+    view = _lib.DvGvcfMergedView()
+    _lib.check(l.dv_gvcf_merged_arrays(handle, C.byref(view)))
+
+    def array(ptr, count, dtype):
+      if count == 0:
+        return np.zeros(0, dtype)
+      return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)),
+                                   (count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+    p, v = view.n_pieces, view.n_variants
+    return MergedBlocks(piece_start=array(view.piece_start, p, np.int64), piece_end=array(view.piece_end, p, np.int64),
+                        piece_block=array(view.piece_block, p, np.int32),
+                        piece_slot=array(view.piece_slot, p, np.int64), var_slot=array(view.var_slot, v, np.int64))
+  finally:
+    l.dv_gvcf_merged_free(handle)
+
+
+def merge_blocks_and_variants(block_off, var_off, block_start, block_end, var_start, var_end) -> MergedBlocks:
+  """The host code (dv_gvcf_merge).  G groups (contigs): block_off, var_off int64 [G + 1]; per group the blocks
+  [start, end) sorted and disjoint, the variants sorted by (start, end)."""
+  a = _merge_arguments(block_off, var_off, block_start, block_end, var_start, var_end)
+  handle = C.c_void_p()
+  _lib.check(_lib.lib().dv_gvcf_merge(a[0].size - 1, *[x.ctypes.data for x in a], C.byref(handle)))
+  return _take_merged(handle)
+
+
+def merge_blocks_and_variants_device(block_off, var_off, block_start, block_end, var_start, var_end,
+                                     stream=None) -> MergedBlocks:
+  """The same on the device (dv_gvcf_merge_device): one upload, nine launches, one download.  `stream` is a raw
+  handle; None = a stream the library owns."""
+  a = _merge_arguments(block_off, var_off, block_start, block_end, var_start, var_end)
+  handle = C.c_void_p()
+  _lib.check(_lib.lib().dv_gvcf_merge_device(a[0].size - 1, *[x.ctypes.data for x in a], C.byref(handle),
+                                             C.c_void_p(stream or None)))
+  return _take_merged(handle)
+
+
+def last_merge_stats() -> Dict[str, int]:
+  stats = _lib.DvGvcfMergeStats()
+  _lib.check(_lib.lib().dv_gvcf_merge_last_stats(C.byref(stats)))
+  return {name: int(getattr(stats, name)) for name, _ in stats._fields_}
+
+
+def merge_scan_chunk() -> int:
+  return int(_lib.lib().dv_gvcf_merge_scan_chunk())
+
+
+# ------------------------------------------------------------------------------------------ the gVCF writer
+GVCF_ALT = '<*>'
+_GVCF_GL = -99.0          # every genotype that names <*>: PL 990 before the minimum is taken off
+_GVCF_HEADER = (
+    '##INFO=<ID=END,Number=1,Type=Integer,Description="End position (for use with symbolic alleles)">',
+    '##FORMAT=<ID=MIN_DP,Number=1,Type=Integer,Description="Minimum DP observed within the GVCF block.">',
+)
+_GVCF_HEADER_MED_DP = '##FORMAT=<ID=MED_DP,Number=1,Type=Integer,Description="Median DP observed within the GVCF block rounded to the nearest integer.">'
+
+
+def gvcf_variant_row(r: VcfRecord) -> str:
+  """vcf_row of the record with <*> as one more alt: AD and VAF 0, and GL -99 for its A + 2 genotypes, which follow
+  the record's own in VCF order."""
+  alts = len(r.alternate_bases)
+  if len(r.genotype_likelihood) != (alts + 1) * (alts + 2) // 2:
+    raise ValueError('%s:%d: one likelihood per genotype of its alleles is expected' % (r.reference_name, r.start + 1))
+  return vcf_row(dataclasses.replace(
+      r, alternate_bases=list(r.alternate_bases) + [GVCF_ALT], ad=None if r.ad is None else list(r.ad) + [0],
+      vaf=None if r.vaf is None else list(r.vaf) + [0.0],
+      genotype_likelihood=list(r.genotype_likelihood) + [_GVCF_GL] * (alts + 2)))
+
+
+def _gvcf_dtype():
+  from deepvariant_amd import allelecounter
+  return allelecounter.GVCF_BLOCK_DTYPE
+
+
+def blocks_from_variants(variants: Iterable[T.Variant]) -> Dict[str, np.ndarray]:
+  """Reference-block Variant records (make_gvcfs / variant_calling.gvcf_record, in any order) -> {contig: their
+  GVCF_BLOCK_DTYPE array sorted by start}; MED_DP -1 where a record has none."""
+  columns: Dict[str, list] = {}
+  for v in variants:
+    call = v.calls[0]
+    gl = list(call.genotype_likelihood)
+    if len(gl) != 3 or not v.reference_bases:
+      raise ValueError('%s:%d: a reference block carries one base and three likelihoods' % (v.reference_name, v.start + 1))
+    med = call.info['MED_DP'].values[0].int_value if 'MED_DP' in call.info else -1
+    columns.setdefault(v.reference_name, []).append(
+        (v.start, v.end, gl, call.info['GQ'].values[0].int_value, call.info['MIN_DP'].values[0].int_value, med,
+         ord(v.reference_bases[0]), 1 if list(call.genotype) == [0, 0] else 0, (0, 0)))
+  out = {}
+  for contig, rows in columns.items():
+    arr = np.array(rows, _gvcf_dtype())
+    out[contig] = arr[np.argsort(arr['start'], kind='stable')]
+  return out
+
+
+def _piece_rows(contig: str, blocks: np.ndarray, piece_start: np.ndarray, piece_end: np.ndarray, piece_block: np.ndarray,
+                ref_reader, med_dp: bool) -> List[str]:
+  """The rows of one contig's pieces, formatted from columns: piece_block indexes `blocks`."""
+  if not piece_start.size:
+    return []
+  src = blocks[piece_block]
+  bases = src['ref_base'].copy()
+  moved = np.nonzero(piece_start != src['start'])[0]
+  if moved.size:
+    # one fetch per contig over the moved starts, indexed by array
+    lo, hi = int(piece_start[moved].min()), int(piece_start[moved].max()) + 1
+    fetched = np.frombuffer(ref_reader.get_bases(contig, lo, hi).encode(), np.uint8)
+    bases[moved] = fetched[piece_start[moved] - lo]
+  pls = np.rint(-10.0 * src['likelihoods']).astype(np.int64)       # vcf_row's int(round(-10 * GL)): half to even
+  pls -= pls.min(axis=1, keepdims=True)
+  letters = bases.tobytes().decode('latin-1')
+  head = contig + '\t'
+  rows = []
+  if med_dp:
+    tail = '\tGT:GQ:MIN_DP:MED_DP:PL\t'
+    for k, (s, e, gq, mn, md, ok, (p0, p1, p2)) in enumerate(zip(
+        (piece_start + 1).tolist(), piece_end.tolist(), src['gq'].tolist(), src['min_dp'].tolist(),
+        src['med_dp'].tolist(), src['has_valid_gl'].tolist(), pls.tolist())):
+      rows.append('%s%d\t.\t%s\t<*>\t0\t.\tEND=%d%s%s:%d:%d:%s:%d,%d,%d\n' % (
+          head, s, letters[k], e, tail, '0/0' if ok else './.', gq, mn, '.' if md < 0 else md, p0, p1, p2))
+  else:
+    tail = '\tGT:GQ:MIN_DP:PL\t'
+    for k, (s, e, gq, mn, ok, (p0, p1, p2)) in enumerate(zip(
+        (piece_start + 1).tolist(), piece_end.tolist(), src['gq'].tolist(), src['min_dp'].tolist(),
+        src['has_valid_gl'].tolist(), pls.tolist())):
+      rows.append('%s%d\t.\t%s\t<*>\t0\t.\tEND=%d%s%s:%d:%d:%d,%d,%d\n' % (
+          head, s, letters[k], e, tail, '0/0' if ok else './.', gq, mn, p0, p1, p2))
+  return rows
+
+
+def gvcf_rows(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
+              contigs: Sequence[Tuple[str, int]], device: bool = False, stream=None) -> Tuple[List[str], bool]:
+  """-> (the rows of the gVCF in merged order, the contigs in the order of `contigs`; whether the blocks carry
+  MED_DP).  records: the finished records, in any order.  blocks_by_contig: GVCF_BLOCK_DTYPE arrays, in any order.
+  One native merge call over all contigs: the host code, or the device with `device`."""
+  order = {name: k for k, (name, _) in enumerate(contigs)}
+  for name in list(blocks_by_contig) + [r.reference_name for r in records]:
+    if name not in order:
+      raise ValueError('%s is not a contig of the reference' % name)
+  records = sorted(records, key=lambda r: (order[r.reference_name], r.start, r.end))
+  dtype = _gvcf_dtype()
+  blocks, block_off, var_off = [], [0], [0]
+  at = 0
+  for name, _ in contigs:
+    arr = np.asarray(blocks_by_contig.get(name, np.zeros(0, dtype)), dtype)
+    if arr.size > 1 and (arr['start'][1:] < arr['start'][:-1]).any():
+      arr = arr[np.argsort(arr['start'], kind='stable')]
+    blocks.append(arr)
+    block_off.append(block_off[-1] + arr.size)
+    while at < len(records) and records[at].reference_name == name:
+      at += 1
+    var_off.append(at)
+  every = np.concatenate(blocks) if blocks else np.zeros(0, dtype)
+  var_start = np.array([r.start for r in records], np.int64)
+  var_end = np.array([r.end for r in records], np.int64)
+  merge = merge_blocks_and_variants_device if device else merge_blocks_and_variants
+  kwargs = {'stream': stream} if device else {}
+  merged = merge(block_off, var_off, every['start'], every['end'], var_start, var_end, **kwargs)
+  med_dp = bool(every.size and (every['med_dp'] >= 0).any())
+  rows: List[Optional[str]] = [None] * (merged.piece_slot.size + len(records))
+  piece_group = np.searchsorted(merged.piece_block, np.array(block_off, np.int64), side='left')
+  for g, (name, _) in enumerate(contigs):
+    p0, p1 = int(piece_group[g]), int(piece_group[g + 1])
+    texts = _piece_rows(name, blocks[g], merged.piece_start[p0:p1], merged.piece_end[p0:p1],
+                        merged.piece_block[p0:p1].astype(np.int64) - block_off[g], ref_reader, med_dp)
+    for slot, text in zip(merged.piece_slot[p0:p1].tolist(), texts):
+      rows[slot] = text
+  for slot, r in zip(merged.var_slot.tolist(), records):
+    rows[slot] = gvcf_variant_row(r)
+  if any(row is None for row in rows):
+    raise RuntimeError('the merged slots are not a permutation')
+  return rows, med_dp
+
+
+def gvcf_text(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
+              contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None) -> str:
+  rows, med_dp = gvcf_rows(records, blocks_by_contig, ref_reader, contigs, device, stream)
+  extra = _GVCF_HEADER + ((_GVCF_HEADER_MED_DP,) if med_dp else ())
+  return vcf_header(contigs, sample_name, extra) + ''.join(rows)
+
+
+def write_gvcf(path: str, records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
+               contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None) -> None:
+  """The .gz rule is write_vcf's."""
+  _write_text(path, gvcf_text(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream))
+
+
+def concatenate_blocks(arrays_by_contig: Dict[str, List[np.ndarray]]) -> Dict[str, np.ndarray]:
+  """{contig: [the regions' block arrays]} -> {contig: one array}."""
+  return {name: np.concatenate(arrays) for name, arrays in arrays_by_contig.items() if arrays}
+
+
+def _env_on(name: str) -> bool:
+  return os.environ.get(name, '0') not in ('', '0')
+
+
+def fused_merge_on_device() -> bool:
+  """make_examples --gvcf_outfile: the merge runs on the device; DV_GVCF_MERGE_HOST=1 forces the host code (A/B)."""
+  return not _env_on('DV_GVCF_MERGE_HOST')
 
 
 # ------------------------------------------------------------------------------------------ CVO records -> VCF
@@ -390,17 +629,38 @@ def records_from_cvos(cvos, qual_filter: float = DEFAULT_QUAL_FILTER,
   return finish_sites(variants, result, qual_filter, cnn_homref_call_min_gq, sample_name)
 
 
+def read_nonvariant_blocks(spec: str) -> Dict[str, np.ndarray]:
+  """--nonvariant_site_tfrecord_path: a sharded spec (or one file) of nucleus Variant records, one per reference block
+  -> {contig: GVCF_BLOCK_DTYPE array}.  A record is decoded, copied into its row and dropped."""
+  from deepvariant_amd import call_variants, protowire, tfrecord
+  def decoded():
+    for path in call_variants.sharded_paths(spec):
+      for rec in tfrecord.read_tfrecords(path):
+        yield protowire.decode_variant(rec)
+  return blocks_from_variants(decoded())
+
+
 def postprocess_variants(infile: str, ref: str, outfile: str, qual_filter: float = DEFAULT_QUAL_FILTER,
                          cnn_homref_call_min_gq: float = DEFAULT_CNN_HOMREF_CALL_MIN_GQ,
-                         sample_name: Optional[str] = None) -> int:
-  """-> the number of rows written."""
+                         sample_name: Optional[str] = None, nonvariant_site_tfrecord_path: str = '',
+                         gvcf_outfile: str = '') -> int:
+  """-> the number of rows written to `outfile`.  With the two gVCF arguments (each needs the other) the reference
+  blocks are merged with the records and written to `gvcf_outfile`: by the host code, or on the device with
+  DV_GVCF_MERGE_DEVICE=1."""
   from deepvariant_amd import call_variants, genomics_io, protowire, tfrecord
+  if bool(nonvariant_site_tfrecord_path) != bool(gvcf_outfile):
+    raise ValueError('--nonvariant_site_tfrecord_path and --gvcf_outfile need each other')
   cvos = []
   for path in call_variants.sharded_paths(infile):
     for rec in tfrecord.read_tfrecords(path):
       cvos.append(protowire.decode_call_variants_output(rec))
   records = records_from_cvos(cvos, qual_filter, cnn_homref_call_min_gq, sample_name)
-  write_vcf(outfile, records, fasta_contigs(genomics_io.FastaReader(ref)), default_sample_name(records, sample_name))
+  ref_reader = genomics_io.FastaReader(ref)
+  contigs, name = fasta_contigs(ref_reader), default_sample_name(records, sample_name)
+  write_vcf(outfile, records, contigs, name)
+  if gvcf_outfile:
+    write_gvcf(gvcf_outfile, records, read_nonvariant_blocks(nonvariant_site_tfrecord_path), ref_reader, contigs, name,
+               device=_env_on('DV_GVCF_MERGE_DEVICE'))
   return len(records)
 
 
@@ -414,13 +674,16 @@ def build_arg_parser():
   ap.add_argument('--qual_filter', type=float, default=DEFAULT_QUAL_FILTER)
   ap.add_argument('--cnn_homref_call_min_gq', type=float, default=DEFAULT_CNN_HOMREF_CALL_MIN_GQ)
   ap.add_argument('--sample_name', default=None)
+  # the reference's flag names: the gVCF TFRecords of make_examples --gvcf (GvcfShardWriter here) and the .g.vcf
+  ap.add_argument('--nonvariant_site_tfrecord_path', default='')
+  ap.add_argument('--gvcf_outfile', default='')
   return ap
 
 
 def main(argv=None) -> int:
   args = build_arg_parser().parse_args(argv)
   n = postprocess_variants(args.infile, args.ref, args.outfile, args.qual_filter, args.cnn_homref_call_min_gq,
-                           args.sample_name)
+                           args.sample_name, args.nonvariant_site_tfrecord_path, args.gvcf_outfile)
   print('postprocess_variants: wrote %d records' % n)
   return 0
 

@@ -1790,6 +1790,54 @@ typedef struct dv_genotype_device_stats {
 /* What the calling thread's last dv_genotype_sites_device did. */
 int dv_genotype_device_last_stats(dv_genotype_device_stats* out);
 
+/* ---- gVCF: the merge of the reference blocks with the variant records (csrc/gvcf_merge.hip) ----
+ * A call carries G groups (contigs): group g owns blocks [block_off[g], block_off[g + 1]) and variants
+ * [var_off[g], var_off[g + 1]), half-open spans [start, end).  Within a group the blocks are sorted and pairwise
+ * disjoint, the variants sorted by (start, end); variants may overlap and nest.  A block loses what the variants
+ * cover; what is left are its pieces, in order.  With the P pieces in block order and the V variants in theirs, the
+ * merged sequence (merge_variants_and_nonvariants, groups in order) is a permutation of P + V slots: piece k of a group
+ * comes after the group's variant j iff start[j] < piece_end[k].  P <= B + V.
+ * Results, equal from both entry points: piece_start, piece_end [P]; piece_block [P], the index of the source block
+ * in the call; piece_slot [P] and var_slot [V], positions in the whole call's merged sequence.
+ * Null pointers with non-zero counts, a negative count or more than 2^31 - 1 records: DV_ERR_INVALID_ARGUMENT.
+ * Offsets that do not ascend from 0, an empty span, blocks out of order or overlapping, variants out of (start, end)
+ * order: DV_ERR_BAD_INPUT with a message.  Empty groups, and groups with blocks only or variants only, are legal.
+ * On any error *out is NULL and nothing stays allocated. */
+typedef struct dv_gvcf_merged dv_gvcf_merged; /* owns the host arrays of one call's result */
+typedef struct dv_gvcf_merged_view {          /* views into the result; valid until dv_gvcf_merged_free */
+  int64_t n_pieces;
+  int64_t n_variants;
+  const int64_t* piece_start;
+  const int64_t* piece_end;
+  const int32_t* piece_block;
+  const int64_t* piece_slot;
+  const int64_t* var_slot;
+} dv_gvcf_merged_view;
+/* Host code: the twin every test compares against. */
+int dv_gvcf_merge(int32_t n_groups, const int64_t* block_off, const int64_t* var_off, const int64_t* block_start,
+                  const int64_t* block_end, const int64_t* var_start, const int64_t* var_end, dv_gvcf_merged** out);
+/* The same on the device; every array is a host array and is checked before any device work.  One staged upload,
+ * launches queued on `stream` (NULL = a non-blocking stream the library owns), one download sized for B + V pieces,
+ * one synchronisation.  A call without records is DV_OK without a device; no device is DV_ERR_NO_DEVICE. */
+int dv_gvcf_merge_device(int32_t n_groups, const int64_t* block_off, const int64_t* var_off, const int64_t* block_start,
+                         const int64_t* block_end, const int64_t* var_start, const int64_t* var_end,
+                         dv_gvcf_merged** out, void* stream);
+int dv_gvcf_merged_arrays(const dv_gvcf_merged* m, dv_gvcf_merged_view* out);
+void dv_gvcf_merged_free(dv_gvcf_merged* m);
+/* Elements per workgroup of the device's two scans (the running maximum of the variant ends, the sum of the piece
+ * counts): a carry crosses from one workgroup's chunk to the next at multiples of it. */
+int32_t dv_gvcf_merge_scan_chunk(void);
+typedef struct dv_gvcf_merge_stats {
+  int64_t blocks; /* of the call */
+  int64_t variants;
+  int64_t pieces;
+  int64_t launches;
+  int64_t bytes_up;
+  int64_t bytes_down;
+} dv_gvcf_merge_stats;
+/* What the calling thread's last dv_gvcf_merge_device did. */
+int dv_gvcf_merge_last_stats(dv_gvcf_merge_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
