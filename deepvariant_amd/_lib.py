@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     'dv_genotype_min_nonref_prob', 'dv_genotype_device_last_stats',
     'dv_gvcf_merge', 'dv_gvcf_merge_device', 'dv_gvcf_merged_arrays', 'dv_gvcf_merged_free',
     'dv_gvcf_merge_scan_chunk', 'dv_gvcf_merge_last_stats',
+    'dv_gvcf_rows', 'dv_gvcf_rows_device', 'dv_gvcf_text_arrays', 'dv_gvcf_text_free', 'dv_gvcf_rows_last_stats',
 ]
 
 DV_GENOTYPE_DEVICE_MAX_ALTS = 6
@@ -338,6 +339,23 @@ class DvGvcfMergedView(C.Structure):
 
 class DvGvcfMergeStats(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('blocks', 'variants', 'pieces', 'launches', 'bytes_up', 'bytes_down')]
+
+
+class DvGvcfRowsInput(C.Structure):
+  _fields_ = [('n_groups', C.c_int32), ('med_dp', C.c_int32), ('want_row_off', C.c_int32), ('reserved', C.c_int32),
+              ('block_off', C.c_void_p), ('var_off', C.c_void_p), ('blocks', C.c_void_p), ('var_start', C.c_void_p),
+              ('var_end', C.c_void_p), ('var_end_base', C.c_void_p), ('var_text_off', C.c_void_p),
+              ('var_text', C.c_void_p), ('name_off', C.c_void_p), ('names', C.c_void_p)]
+
+
+class DvGvcfTextView(C.Structure):
+  _fields_ = [('text', C.c_void_p), ('n_bytes', C.c_int64), ('row_off', C.c_void_p), ('n_rows', C.c_int64),
+              ('n_pieces', C.c_int64), ('med_dp', C.c_int32), ('reserved', C.c_int32)]
+
+
+class DvGvcfRowsStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('blocks', 'variants', 'pieces', 'rows', 'text_bytes', 'launches', 'bytes_up',
+                                       'bytes_down')]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -734,6 +752,12 @@ def lib():
     l.dv_gvcf_merge_scan_chunk.argtypes = []
     l.dv_gvcf_merge_scan_chunk.restype = C.c_int32
     l.dv_gvcf_merge_last_stats.argtypes = [C.c_void_p]
+    l.dv_gvcf_rows.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_gvcf_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    l.dv_gvcf_text_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_gvcf_text_free.argtypes = [C.c_void_p]
+    l.dv_gvcf_text_free.restype = None
+    l.dv_gvcf_rows_last_stats.argtypes = [C.c_void_p]
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -714,9 +714,16 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
         # once, after the last flush: every block and every finished record of the run in one native merge call
         blocks = postprocess_variants.concatenate_blocks(gvcf_arrays)
         on_device = postprocess_variants.fused_merge_on_device()
-        postprocess_variants.write_gvcf(gvcf_outfile, records, blocks, ref_reader, contigs, sample_name, device=on_device)
+        rows = postprocess_variants.gvcf_rows_switch()
+        postprocess_variants.write_gvcf(gvcf_outfile, records, blocks, ref_reader, contigs, sample_name, device=on_device,
+                                        rows=rows)
         stats['n_gvcf_blocks'] = sum(len(b) for b in blocks.values())
-        stats['gvcf_merge'] = postprocess_variants.last_merge_stats() if on_device else {}
+        if rows == 'native':
+          # the rows' own call merges as well: no merge call ran
+          stats['gvcf_merge'] = {}
+          stats['gvcf_rows'] = postprocess_variants.last_rows_stats() if on_device else {}
+        else:
+          stats['gvcf_merge'] = postprocess_variants.last_merge_stats() if on_device else {}
       stats['n_vcf_records'] = len(records)
       stats['n_examples'] = proc.vcf.n_examples     # also when no CallVariantsOutput record was asked for
       stats['genotype_device'] = dict(proc.vcf.device_stats)

@@ -11,8 +11,9 @@ scores, the call, pruned and simplified alleles) needs log10 and is one host fun
 
 The gVCF: `merge_blocks_and_variants` (dv_gvcf_merge) and `merge_blocks_and_variants_device`
 (dv_gvcf_merge_device, csrc/gvcf_merge.hip) interleave the reference blocks of the allele counter with the finished
-records -- both return the same arrays -- and `gvcf_text` / `write_gvcf` print the rows.  Blocks travel as
-`allelecounter.GVCF_BLOCK_DTYPE` arrays per contig from end to end; no object is made per block.
+records -- both return the same arrays -- and `gvcf_text` / `write_gvcf` print the rows; with rows='native'
+(DV_GVCF_ROWS_NATIVE=1) `gvcf_body_native` merges and prints in one native call (section 23, csrc/gvcf_rows.hip).
+Blocks travel as `allelecounter.GVCF_BLOCK_DTYPE` arrays per contig from end to end; no object is made per block.
 
   python -m deepvariant_amd.postprocess_variants --infile CVO --ref FASTA --outfile VCF
       [--nonvariant_site_tfrecord_path GVCF_TFRECORDS --gvcf_outfile GVCF]
@@ -352,13 +353,18 @@ def write_vcf(path: str, records: Sequence[VcfRecord], contigs: Sequence[Tuple[s
 
 def _write_text(path: str, text: str) -> None:
   """GZIP when the name ends in .gz."""
-  data = text.encode()
+  _write_bytes(path, text.encode())
+
+
+def _write_bytes(path: str, *chunks: bytes) -> None:
   with open(path, 'wb') as f:
     if path.endswith('.gz'):
       with gzip.GzipFile(filename='', fileobj=f, mode='wb', mtime=0) as z:     # the same bytes on every run
-        z.write(data)
+        for data in chunks:
+          z.write(data)
     else:
-      f.write(data)
+      for data in chunks:
+        f.write(data)
 
 
 def fasta_contigs(ref_reader) -> List[Tuple[str, int]]:
@@ -575,16 +581,137 @@ def gvcf_rows(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarr
 
 
 def gvcf_text(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
-              contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None) -> str:
+              contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None,
+              rows: str = 'python') -> str:
+  """rows: 'python' formats the rows here (gvcf_rows); 'native' takes them from gvcf_body_native (section 23)."""
+  if rows == 'native':
+    header, body = _native_gvcf(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream)
+    return header + body.decode()
+  if rows != 'python':
+    raise ValueError("rows must be 'python' or 'native'")
   rows, med_dp = gvcf_rows(records, blocks_by_contig, ref_reader, contigs, device, stream)
   extra = _GVCF_HEADER + ((_GVCF_HEADER_MED_DP,) if med_dp else ())
   return vcf_header(contigs, sample_name, extra) + ''.join(rows)
 
 
 def write_gvcf(path: str, records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
-               contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None) -> None:
-  """The .gz rule is write_vcf's."""
-  _write_text(path, gvcf_text(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream))
+               contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None,
+               rows: str = 'python') -> None:
+  """The .gz rule is write_vcf's.  rows as for gvcf_text; the native body goes to the file as the bytes it is."""
+  if rows == 'native':
+    header, body = _native_gvcf(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream)
+    _write_bytes(path, header.encode(), body)
+    return
+  _write_text(path, gvcf_text(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream, rows))
+
+
+# ------------------------------------------------------------------------------------------ the gVCF rows, native
+@dataclasses.dataclass
+class GvcfBody:
+  """One native call's result (dv_gvcf_text_view, copied): the rows of a gVCF in merged order, without the header."""
+  text: bytes
+  row_off: Optional[np.ndarray]     # int64 [rows + 1] when asked for
+  med_dp: bool                      # the block rows carry MED_DP
+  n_pieces: int                     # the block rows; the others are the variants'
+
+
+def gvcf_rows_native(block_off, var_off, blocks, var_start, var_end, var_end_base, var_text_off, var_text: bytes,
+                     name_off, names: bytes, med_dp: int = -1, want_row_off: bool = False, device: bool = False,
+                     stream=None) -> GvcfBody:
+  """dv_gvcf_rows, or dv_gvcf_rows_device with `device` (csrc/gvcf_rows.hip): the merge of merge_blocks_and_variants
+  carried on to the text.  blocks: GVCF_BLOCK_DTYPE [B] over all groups; var_end_base: uint8 [V], the reference base at
+  every variant's end; var_text_off [V + 1] into var_text, the variants' finished rows; name_off [G + 1] into names,
+  the groups' contig names; med_dp: -1 = MED_DP when any block has one, else 0 or 1."""
+  ints = [np.ascontiguousarray(a, np.int64).reshape(-1) for a in (block_off, var_off, var_start, var_end, var_text_off,
+                                                                  name_off)]
+  b_off, v_off, v_start, v_end, text_off, n_off = ints
+  blocks = np.ascontiguousarray(blocks, _gvcf_dtype()).reshape(-1)
+  bases = np.ascontiguousarray(var_end_base, np.uint8).reshape(-1)
+  if b_off.size < 1 or b_off.size != v_off.size or n_off.size != b_off.size:
+    raise ValueError('block_off, var_off and name_off must have one entry per group and one more')
+  if v_start.size != v_end.size or bases.size != v_start.size or text_off.size != v_start.size + 1:
+    raise ValueError('one end, one base and one row per variant are expected')
+  if int(b_off[-1]) != blocks.size or int(v_off[-1]) != v_start.size:
+    raise ValueError('the offsets must end at the number of blocks and of variants')
+  if int(text_off[-1]) > len(var_text) or int(n_off[-1]) > len(names):
+    raise ValueError('the text offsets pass the end of their text')
+  arg = _lib.DvGvcfRowsInput(
+      n_groups=b_off.size - 1, med_dp=int(med_dp), want_row_off=1 if want_row_off else 0, block_off=b_off.ctypes.data,
+      var_off=v_off.ctypes.data, blocks=blocks.ctypes.data, var_start=v_start.ctypes.data, var_end=v_end.ctypes.data,
+      var_end_base=bases.ctypes.data, var_text_off=text_off.ctypes.data,
+      var_text=C.cast(C.c_char_p(var_text), C.c_void_p), name_off=n_off.ctypes.data,
+      names=C.cast(C.c_char_p(names), C.c_void_p))
+  l = _lib.lib()
+  handle = C.c_void_p()
+  if device:
+    _lib.check(l.dv_gvcf_rows_device(C.byref(arg), C.byref(handle), C.c_void_p(stream or None)))
+  else:
+    _lib.check(l.dv_gvcf_rows(C.byref(arg), C.byref(handle)))
+  try:
+    view = _lib.DvGvcfTextView()
+    _lib.check(l.dv_gvcf_text_arrays(handle, C.byref(view)))
+    row_off = None
+    if want_row_off:
+      row_off = np.ctypeslib.as_array(C.cast(view.row_off, C.POINTER(C.c_int64)), (view.n_rows + 1,)).copy()
+    return GvcfBody(text=C.string_at(view.text, view.n_bytes), row_off=row_off, med_dp=bool(view.med_dp),
+                    n_pieces=int(view.n_pieces))
+  finally:
+    l.dv_gvcf_text_free(handle)
+
+
+def last_rows_stats() -> Dict[str, int]:
+  """What the calling thread's last device call of gvcf_rows_native did."""
+  stats = _lib.DvGvcfRowsStats()
+  _lib.check(_lib.lib().dv_gvcf_rows_last_stats(C.byref(stats)))
+  return {name: int(getattr(stats, name)) for name, _ in stats._fields_}
+
+
+def gvcf_body_native(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
+                     contigs: Sequence[Tuple[str, int]], device: bool = False, stream=None,
+                     want_row_off: bool = False) -> GvcfBody:
+  """gvcf_rows with the block rows made by the native code, on the host or with `device` on the device: the records
+  and blocks are sorted and grouped as there, the variants' rows are gvcf_variant_row's, and one native call merges
+  and prints.  One get_bases per contig that has variants, over the variant ends below the contig's length."""
+  order = {name: k for k, (name, _) in enumerate(contigs)}
+  for name in list(blocks_by_contig) + [r.reference_name for r in records]:
+    if name not in order:
+      raise ValueError('%s is not a contig of the reference' % name)
+  records = sorted(records, key=lambda r: (order[r.reference_name], r.start, r.end))
+  dtype = _gvcf_dtype()
+  blocks, block_off, var_off, name_off, names = [], [0], [0], [0], []
+  var_end = np.array([r.end for r in records], np.int64)
+  var_end_base = np.full(len(records), ord('N'), np.uint8)      # an end at the contig's length: no piece starts there
+  at = 0
+  for name, length in contigs:
+    arr = np.asarray(blocks_by_contig.get(name, np.zeros(0, dtype)), dtype)
+    if arr.size > 1 and (arr['start'][1:] < arr['start'][:-1]).any():
+      arr = arr[np.argsort(arr['start'], kind='stable')]
+    blocks.append(arr)
+    block_off.append(block_off[-1] + arr.size)
+    first = at
+    while at < len(records) and records[at].reference_name == name:
+      at += 1
+    var_off.append(at)
+    names.append(name.encode())
+    name_off.append(name_off[-1] + len(names[-1]))
+    inside = first + np.nonzero(var_end[first:at] < length)[0]
+    if inside.size:
+      lo, hi = int(var_end[inside].min()), int(var_end[inside].max()) + 1
+      fetched = np.frombuffer(ref_reader.get_bases(name, lo, hi).encode('latin-1'), np.uint8)
+      var_end_base[inside] = fetched[var_end[inside] - lo]
+  texts = [gvcf_variant_row(r).encode() for r in records]
+  var_text_off = np.zeros(len(texts) + 1, np.int64)
+  np.cumsum([len(t) for t in texts], out=var_text_off[1:])
+  return gvcf_rows_native(block_off, var_off, np.concatenate(blocks) if blocks else np.zeros(0, dtype),
+                          np.array([r.start for r in records], np.int64), var_end, var_end_base, var_text_off,
+                          b''.join(texts), name_off, b''.join(names), want_row_off=want_row_off, device=device,
+                          stream=stream)
+
+
+def _native_gvcf(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream) -> Tuple[str, bytes]:
+  body = gvcf_body_native(records, blocks_by_contig, ref_reader, contigs, device, stream)
+  extra = _GVCF_HEADER + ((_GVCF_HEADER_MED_DP,) if body.med_dp else ())
+  return vcf_header(contigs, sample_name, extra), body.text
 
 
 def concatenate_blocks(arrays_by_contig: Dict[str, List[np.ndarray]]) -> Dict[str, np.ndarray]:
@@ -594,6 +721,11 @@ def concatenate_blocks(arrays_by_contig: Dict[str, List[np.ndarray]]) -> Dict[st
 
 def _env_on(name: str) -> bool:
   return os.environ.get(name, '0') not in ('', '0')
+
+
+def gvcf_rows_switch() -> str:
+  """DV_GVCF_ROWS_NATIVE=1: both gVCF routes pass rows='native'; the side follows the merge's switches."""
+  return 'native' if _env_on('DV_GVCF_ROWS_NATIVE') else 'python'
 
 
 def fused_merge_on_device() -> bool:
@@ -646,7 +778,7 @@ def postprocess_variants(infile: str, ref: str, outfile: str, qual_filter: float
                          gvcf_outfile: str = '') -> int:
   """-> the number of rows written to `outfile`.  With the two gVCF arguments (each needs the other) the reference
   blocks are merged with the records and written to `gvcf_outfile`: by the host code, or on the device with
-  DV_GVCF_MERGE_DEVICE=1."""
+  DV_GVCF_MERGE_DEVICE=1; with DV_GVCF_ROWS_NATIVE=1 the native code of that side prints the rows as well."""
   from deepvariant_amd import call_variants, genomics_io, protowire, tfrecord
   if bool(nonvariant_site_tfrecord_path) != bool(gvcf_outfile):
     raise ValueError('--nonvariant_site_tfrecord_path and --gvcf_outfile need each other')
@@ -660,7 +792,7 @@ def postprocess_variants(infile: str, ref: str, outfile: str, qual_filter: float
   write_vcf(outfile, records, contigs, name)
   if gvcf_outfile:
     write_gvcf(gvcf_outfile, records, read_nonvariant_blocks(nonvariant_site_tfrecord_path), ref_reader, contigs, name,
-               device=_env_on('DV_GVCF_MERGE_DEVICE'))
+               device=_env_on('DV_GVCF_MERGE_DEVICE'), rows=gvcf_rows_switch())
   return len(records)
 
 

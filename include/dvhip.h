@@ -1838,6 +1838,64 @@ typedef struct dv_gvcf_merge_stats {
 /* What the calling thread's last dv_gvcf_merge_device did. */
 int dv_gvcf_merge_last_stats(dv_gvcf_merge_stats* out);
 
+/* ---- gVCF: the rows behind the merge (csrc/gvcf_rows.hip) ----
+ * The merge above, carried on to the text: every piece becomes a reference-block row (csrc/gvcf_rows.h, the format of
+ * postprocess_variants._piece_rows), every variant's finished row is copied, and both stand in merged order, the
+ * groups in order, without a header.  A piece that starts at its block's start prints the block's ref_base; a moved
+ * start is some variant's end, and prints that variant's var_end_base.
+ * Refused with DV_ERR_BAD_INPUT and a message, on the host before any device work: everything dv_gvcf_merge refuses;
+ * var_text_off that does not ascend from 0; a variant row that is empty or does not end in '\n'; name_off that does
+ * not ascend from >= 0; a ref_base, or a var_end_base that a piece takes, outside 0x21..0x7E; a likelihood that is
+ * not finite or has |10 GL| >= 2^53.  med_dp outside -1..1 and null pointers: DV_ERR_INVALID_ARGUMENT.  Empty groups,
+ * and groups with blocks only or variants only, are legal.  On any error *out is NULL and nothing stays allocated. */
+typedef struct dv_gvcf_rows_input {
+  int32_t n_groups;             /* G */
+  int32_t med_dp;               /* the rows carry MED_DP: -1 = when any block has med_dp >= 0, else 0 or 1 */
+  int32_t want_row_off;         /* also return row_off */
+  int32_t reserved;
+  const int64_t* block_off;     /* [G + 1] */
+  const int64_t* var_off;       /* [G + 1] */
+  const dv_gvcf_block* blocks;  /* [B]; start and end are the merge's block_start and block_end */
+  const int64_t* var_start;     /* [V] */
+  const int64_t* var_end;       /* [V] */
+  const uint8_t* var_end_base;  /* [V], the reference base at var_end[j] */
+  const int64_t* var_text_off;  /* [V + 1] */
+  const char* var_text;         /* every variant's finished row with its '\n' */
+  const int64_t* name_off;      /* [G + 1] */
+  const char* names;            /* the groups' contig names, back to back */
+} dv_gvcf_rows_input;
+typedef struct dv_gvcf_text dv_gvcf_text;     /* owns one call's text */
+typedef struct dv_gvcf_text_view {            /* views into the result; valid until dv_gvcf_text_free */
+  const char* text;             /* all rows in merged order */
+  int64_t n_bytes;
+  const int64_t* row_off;       /* [n_rows + 1] with want_row_off, else NULL */
+  int64_t n_rows;               /* n_pieces + V */
+  int64_t n_pieces;
+  int32_t med_dp;               /* as decided */
+  int32_t reserved;
+} dv_gvcf_text_view;
+/* Host code: one pass per group. */
+int dv_gvcf_rows(const dv_gvcf_rows_input* in, dv_gvcf_text** out);
+/* The same on the device; every array is a host array.  One staged upload, launches queued on `stream` (NULL = a
+ * non-blocking stream the library owns), a wait for the 16-byte header, then a download of exactly n_bytes (and
+ * row_off when asked for) and a second wait.  A call without records is DV_OK without a device and launches nothing;
+ * no device is DV_ERR_NO_DEVICE. */
+int dv_gvcf_rows_device(const dv_gvcf_rows_input* in, dv_gvcf_text** out, void* stream);
+int dv_gvcf_text_arrays(const dv_gvcf_text* t, dv_gvcf_text_view* out);
+void dv_gvcf_text_free(dv_gvcf_text* t);
+typedef struct dv_gvcf_rows_stats {
+  int64_t blocks; /* of the call */
+  int64_t variants;
+  int64_t pieces;
+  int64_t rows;
+  int64_t text_bytes;
+  int64_t launches;
+  int64_t bytes_up;
+  int64_t bytes_down;
+} dv_gvcf_rows_stats;
+/* What the calling thread's last dv_gvcf_rows_device did. */
+int dv_gvcf_rows_last_stats(dv_gvcf_rows_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
