@@ -77,6 +77,8 @@ ABI_SYMBOLS = [
     'dv_gvcf_merge', 'dv_gvcf_merge_device', 'dv_gvcf_merged_arrays', 'dv_gvcf_merged_free',
     'dv_gvcf_merge_scan_chunk', 'dv_gvcf_merge_last_stats',
     'dv_gvcf_rows', 'dv_gvcf_rows_device', 'dv_gvcf_text_arrays', 'dv_gvcf_text_free', 'dv_gvcf_rows_last_stats',
+    'dv_bgzf_params', 'dv_bgzf_compress', 'dv_bgzf_compress_device', 'dv_bgzf_arrays', 'dv_bgzf_free', 'dv_bgzf_last_stats',
+    'dv_gvcf_rows_bgzf', 'dv_gvcf_rows_bgzf_device',
 ]
 
 DV_GENOTYPE_DEVICE_MAX_ALTS = 6
@@ -356,6 +358,24 @@ class DvGvcfTextView(C.Structure):
 class DvGvcfRowsStats(C.Structure):
   _fields_ = [(n, C.c_int64) for n in ('blocks', 'variants', 'pieces', 'rows', 'text_bytes', 'launches', 'bytes_up',
                                        'bytes_down')]
+
+
+class DvBgzfParameters(C.Structure):
+  _fields_ = [(n, C.c_int32) for n in ('block', 'tile', 'seg', 'hash_bits')]
+
+
+class DvBgzfView(C.Structure):
+  _fields_ = [('data', C.c_void_p), ('n_bytes', C.c_int64), ('n_blocks', C.c_int64), ('block_coff', C.c_void_p),
+              ('stored_blocks', C.c_int64)]
+
+
+class DvBgzfStats(C.Structure):
+  _fields_ = [(n, C.c_int64) for n in ('text_bytes', 'file_bytes', 'blocks', 'stored_blocks', 'launches', 'bytes_up',
+                                       'bytes_down')]
+
+
+class DvGvcfRowsMeta(C.Structure):
+  _fields_ = [('n_rows', C.c_int64), ('n_pieces', C.c_int64), ('text_bytes', C.c_int64), ('row_off', C.c_void_p)]
 
 
 class DvRealignTracebackStats(C.Structure):
@@ -758,6 +778,15 @@ def lib():
     l.dv_gvcf_text_free.argtypes = [C.c_void_p]
     l.dv_gvcf_text_free.restype = None
     l.dv_gvcf_rows_last_stats.argtypes = [C.c_void_p]
+    l.dv_bgzf_params.argtypes = [C.c_void_p]
+    l.dv_bgzf_compress.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    l.dv_bgzf_compress_device.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    l.dv_bgzf_arrays.argtypes = [C.c_void_p, C.c_void_p]
+    l.dv_bgzf_free.argtypes = [C.c_void_p]
+    l.dv_bgzf_free.restype = None
+    l.dv_bgzf_last_stats.argtypes = [C.c_void_p]
+    l.dv_gvcf_rows_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    l.dv_gvcf_rows_bgzf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     l.dv_merge_alt_channels.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     _lib = l

@@ -12,6 +12,10 @@
 // No workgroup reads what another workgroup writes in the same launch.  The text buffer is sized on the host before
 // the launches by a bound (every block's longest possible row, V more rows of the longest of all, the variants' text);
 // the kernels skip a row that would pass it and the host refuses a total that does.
+//
+// dv_gvcf_rows_bgzf[_device] are the same rows behind a caller's prefix, compressed by bgzf.hip
+// instead of returned: on the device the launches above stop at the wait for the header (rows_text_on_device), the
+// text stays where it is and is deflated there; only row_off, when asked for, comes back beside the file.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -20,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "bgzf_internal.h"
 #include "device_round_trip.h"
 #include "gvcf_merge.h"
 #include "gvcf_merge_device.h"
@@ -29,6 +34,7 @@ static_assert(sizeof(dv_gvcf_block) == 56, "dv_gvcf_block layout");
 static_assert(sizeof(dv_gvcf_rows_input) == 96, "dv_gvcf_rows_input layout");
 static_assert(sizeof(dv_gvcf_text_view) == 48, "dv_gvcf_text_view layout");
 static_assert(sizeof(dv_gvcf_rows_stats) == 64, "dv_gvcf_rows_stats layout");
+static_assert(sizeof(dv_gvcf_rows_meta) == 32, "dv_gvcf_rows_meta layout");
 
 struct dv_gvcf_text {
   std::unique_ptr<char[]> text;
@@ -246,15 +252,16 @@ int parse(const char* who, const dv_gvcf_rows_input* in, dv_gvcf_text** out, Che
 }
 
 // The host code: per group its pieces, then the two-way merge of the pieces and the variants straight into the text --
-// variant j stands before piece k iff var_start[j] < piece_end[k] (gvcf_merge.h).
-void rows_on_host(const dv_gvcf_rows_input& in, const Checked& c, dv_gvcf_text* r) {
+// variant j stands before piece k iff var_start[j] < piece_end[k] (gvcf_merge.h).  lead: bytes left free in front of
+// the rows for the caller's prefix; n_bytes and row_off count them.
+void rows_on_host(const dv_gvcf_rows_input& in, const Checked& c, dv_gvcf_text* r, int64_t lead = 0) {
   struct Piece {
     int64_t start, end, block;
     uint8_t base;
   };
-  r->text.reset(new char[static_cast<size_t>(c.text_bound) + 1]);
+  r->text.reset(new char[static_cast<size_t>(lead + c.text_bound) + 1]);
   char* const text = r->text.get();
-  int64_t at = 0;
+  int64_t at = lead;
   if (in.want_row_off) r->row_off.reserve(static_cast<size_t>(c.nb + 2 * c.nv + 1));
   std::vector<int64_t> cm(static_cast<size_t>(c.nv));
   std::vector<Piece> pieces;
@@ -289,7 +296,17 @@ void rows_on_host(const dv_gvcf_rows_input& in, const Checked& c, dv_gvcf_text* 
   r->n_rows = r->n_pieces + c.nv;
 }
 
-int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream, dv_gvcf_text* r) {
+// What rows_text_on_device leaves on the device, valid until the calling thread's next call.
+struct DeviceText {
+  const char* text = nullptr;           // the prefix, then the rows
+  const int64_t* row_off = nullptr;     // [n_rows], exclusive, into the rows
+  int64_t n_bytes = 0, pieces = 0;      // of the rows
+  hipStream_t stream = nullptr;
+};
+
+// The launches and the wait for the header; the text stays on the device, `n_prefix` bytes of `prefix` in front of it.
+int rows_text_on_device(const std::string& who, const dv_gvcf_rows_input& in, const Checked& c, void* stream,
+                        const void* prefix, size_t n_prefix, DeviceText* d) {
   dv_gvcf_rows_stats& stats = last_stats();
   const size_t ng = static_cast<size_t>(in.n_groups);
   const size_t nb = static_cast<size_t>(c.nb), nv = static_cast<size_t>(c.nv);
@@ -314,6 +331,7 @@ int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream,
   const size_t u_var_end_base = up.add(nv);
   const size_t u_names = up.add(name_bytes);
   const size_t u_var_text = up.add(var_bytes);
+  const size_t u_prefix = up.add(n_prefix);
   dv::Layout down;
   const size_t d_header = down.add(2 * sizeof(int64_t));     // the number of pieces, the number of bytes
   dv::Layout scratch;
@@ -331,10 +349,10 @@ int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream,
   const size_t s_piece_base = scratch.add(cap);
   const size_t s_len = scratch.add(rows_cap * sizeof(int64_t));
   const size_t s_row_off = scratch.add(rows_cap * sizeof(int64_t));
-  const size_t s_text = scratch.add(text_cap + 16);          // never empty
+  const size_t s_text = scratch.add(n_prefix + text_cap + 16);       // never empty
 
   static thread_local dv::RoundTrip rt;
-  if (int rc = rt.begin("dv_gvcf_rows_device: no HIP device (dv_gvcf_rows is the host code)", stream, up.bytes(),
+  if (int rc = rt.begin(who + ": no HIP device (dv_gvcf_rows is the host code)", stream, up.bytes(),
                         down.bytes(), scratch.bytes())) {
     return rc;
   }
@@ -358,6 +376,7 @@ int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream,
     std::memcpy(rt.host_up<uint8_t>(u_var_end_base), in.var_end_base, nv);
     std::memcpy(rt.host_up<char>(u_var_text), in.var_text, var_bytes);
   }
+  if (n_prefix > 0) std::memcpy(rt.host_up<char>(u_prefix), prefix, n_prefix);
   if (int rc = rt.upload(up.bytes())) return rc;
   stats.bytes_up = static_cast<int64_t>(up.bytes());
 
@@ -394,7 +413,11 @@ int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream,
   rows.piece_base = scratch_base + s_piece_base;
   rows.len = reinterpret_cast<int64_t*>(scratch_base + s_len);
   rows.row_off = reinterpret_cast<int64_t*>(scratch_base + s_row_off);
-  rows.text = reinterpret_cast<char*>(scratch_base + s_text);
+  rows.text = reinterpret_cast<char*>(scratch_base + s_text) + n_prefix;
+  if (n_prefix > 0) {
+    DV_HIP_CHECK(hipMemcpyAsync(scratch_base + s_text, rt.dev_up<const char>(u_prefix), n_prefix, hipMemcpyDeviceToDevice,
+                                rt.stream()));
+  }
   rows.text_cap = static_cast<int64_t>(text_cap);
   rows.med_dp = c.med_dp ? 1 : 0;
   {
@@ -436,28 +459,46 @@ int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream,
   if (int rc = rt.finish(down.bytes())) return rc;
   const int64_t pieces = rt.host_down<int64_t>(d_header)[0], n_bytes = rt.host_down<int64_t>(d_header)[1];
   if (pieces < 0 || static_cast<size_t>(pieces) > cap || n_bytes < 0 || static_cast<size_t>(n_bytes) > text_cap) {
-    return dv::fail(DV_ERR_HIP, "dv_gvcf_rows_device: the device counted " + std::to_string(pieces) + " pieces and " +
+    return dv::fail(DV_ERR_HIP, who + ": the device counted " + std::to_string(pieces) + " pieces and " +
                                     std::to_string(n_bytes) + " bytes for " + std::to_string(cap) + " records and a bound of " +
                                     std::to_string(text_cap) + " bytes");
   }
-  r->n_pieces = pieces;
-  r->n_rows = pieces + static_cast<int64_t>(nv);
-  r->n_bytes = n_bytes;
-  r->text.reset(new char[static_cast<size_t>(n_bytes) + 1]);
-  stats.bytes_down = static_cast<int64_t>(down.bytes()) + n_bytes;
-  if (n_bytes > 0) {
-    DV_HIP_CHECK(hipMemcpyAsync(r->text.get(), rows.text, static_cast<size_t>(n_bytes), hipMemcpyDeviceToHost, rt.stream()));
+  d->text = reinterpret_cast<const char*>(scratch_base + s_text);
+  d->row_off = rows.row_off;
+  d->n_bytes = n_bytes;
+  d->pieces = pieces;
+  d->stream = rt.stream();
+  stats.bytes_down = static_cast<int64_t>(down.bytes());
+  return DV_OK;
+}
+
+// row_off[0 .. n_rows] from the device; queued on d.stream, not waited for.
+int fetch_row_off(const DeviceText& d, int64_t n_rows, std::vector<int64_t>* row_off) {
+  row_off->resize(static_cast<size_t>(n_rows) + 1);
+  if (n_rows > 0) {
+    DV_HIP_CHECK(hipMemcpyAsync(row_off->data(), d.row_off, static_cast<size_t>(n_rows) * sizeof(int64_t),
+                                hipMemcpyDeviceToHost, d.stream));
+    last_stats().bytes_down += n_rows * static_cast<int64_t>(sizeof(int64_t));
+  }
+  row_off->back() = d.n_bytes;
+  return DV_OK;
+}
+
+int rows_on_device(const dv_gvcf_rows_input& in, const Checked& c, void* stream, dv_gvcf_text* r) {
+  DeviceText d;
+  if (int rc = rows_text_on_device("dv_gvcf_rows_device", in, c, stream, nullptr, 0, &d)) return rc;
+  r->n_pieces = d.pieces;
+  r->n_rows = d.pieces + c.nv;
+  r->n_bytes = d.n_bytes;
+  r->text.reset(new char[static_cast<size_t>(d.n_bytes) + 1]);
+  last_stats().bytes_down += d.n_bytes;
+  if (d.n_bytes > 0) {
+    DV_HIP_CHECK(hipMemcpyAsync(r->text.get(), d.text, static_cast<size_t>(d.n_bytes), hipMemcpyDeviceToHost, d.stream));
   }
   if (in.want_row_off) {
-    r->row_off.resize(static_cast<size_t>(r->n_rows) + 1);
-    if (r->n_rows > 0) {
-      DV_HIP_CHECK(hipMemcpyAsync(r->row_off.data(), rows.row_off, static_cast<size_t>(r->n_rows) * sizeof(int64_t),
-                                  hipMemcpyDeviceToHost, rt.stream()));
-      stats.bytes_down += r->n_rows * static_cast<int64_t>(sizeof(int64_t));
-    }
-    r->row_off.back() = n_bytes;
+    if (int rc = fetch_row_off(d, r->n_rows, &r->row_off)) return rc;
   }
-  DV_HIP_CHECK(hipStreamSynchronize(rt.stream()));
+  DV_HIP_CHECK(hipStreamSynchronize(d.stream));
   return DV_OK;
 }
 
@@ -500,6 +541,89 @@ int dv_gvcf_rows_device(const dv_gvcf_rows_input* in, dv_gvcf_text** out, void* 
     stats.rows = res->n_rows;
     stats.text_bytes = res->n_bytes;
     *out = res.release();
+    return DV_OK;
+  });
+}
+
+// The arguments of the two compressed entry points: their own, then dv_gvcf_rows's through the same `parse`.
+static int parse_compressed(const char* who, const dv_gvcf_rows_input* in, const void* prefix, int64_t n_prefix,
+                            dv_gvcf_rows_meta* meta, dv_bgzf_file** file, Checked* c) {
+  if (file) *file = nullptr;
+  if (meta) *meta = dv_gvcf_rows_meta();
+  if (!meta || !file || n_prefix < 0 || (!prefix && n_prefix > 0)) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, std::string(who) + ": null pointer or negative count");
+  }
+  if (in && in->med_dp < 0) {
+    return dv::fail(DV_ERR_INVALID_ARGUMENT, std::string(who) + ": med_dp must be 0 or 1 (the header is written already)");
+  }
+  dv_gvcf_text* none = nullptr;
+  return parse(who, in, &none, c);
+}
+
+int dv_gvcf_rows_bgzf(const dv_gvcf_rows_input* in, const void* prefix, int64_t n_prefix, dv_gvcf_rows_meta* meta,
+                      dv_bgzf_file** file) {
+  return dv::guarded("dv_gvcf_rows_bgzf", [&]() -> int {
+    Checked c;
+    if (int rc = parse_compressed("dv_gvcf_rows_bgzf", in, prefix, n_prefix, meta, file, &c)) return rc;
+    dv_gvcf_text text;
+    rows_on_host(*in, c, &text, n_prefix);
+    if (n_prefix > 0) std::memcpy(text.text.get(), prefix, static_cast<size_t>(n_prefix));
+    auto res = std::make_unique<dv_bgzf_file>();
+    dv::bgzf_compress_on_host(reinterpret_cast<const uint8_t*>(text.text.get()), text.n_bytes, res.get());
+    if (in->want_row_off) res->row_off = std::move(text.row_off);
+    meta->n_rows = text.n_rows;
+    meta->n_pieces = text.n_pieces;
+    meta->text_bytes = text.n_bytes;
+    meta->row_off = in->want_row_off ? res->row_off.data() : nullptr;
+    *file = res.release();
+    return DV_OK;
+  });
+}
+
+int dv_gvcf_rows_bgzf_device(const dv_gvcf_rows_input* in, const void* prefix, int64_t n_prefix, dv_gvcf_rows_meta* meta,
+                             dv_bgzf_file** file, void* stream) {
+  return dv::guarded("dv_gvcf_rows_bgzf_device", [&]() -> int {
+    const char* const who = "dv_gvcf_rows_bgzf_device";
+    last_stats() = dv_gvcf_rows_stats();
+    Checked c;
+    if (int rc = parse_compressed(who, in, prefix, n_prefix, meta, file, &c)) return rc;
+    dv_gvcf_rows_stats& stats = last_stats();
+    stats.blocks = c.nb;
+    stats.variants = c.nv;
+    auto res = std::make_unique<dv_bgzf_file>();
+    int64_t pieces = 0, text_bytes = n_prefix;
+    if (c.nb + c.nv > 0) {
+      DeviceText d;
+      if (int rc = rows_text_on_device(who, *in, c, stream, prefix, static_cast<size_t>(n_prefix), &d)) return rc;
+      pieces = d.pieces;
+      text_bytes += d.n_bytes;
+      // the text is deflated where it lies, on the stream that wrote it
+      if (int rc = dv::bgzf_compress_on_device(who, reinterpret_cast<const uint8_t*>(d.text), true, text_bytes, d.stream,
+                                               res.get())) {
+        return rc;
+      }
+      if (in->want_row_off) {
+        // after the compressor, which has waited for the stream: no copy into row_off is pending when an error frees it
+        const int rc = fetch_row_off(d, pieces + c.nv, &res->row_off);
+        const hipError_t waited = hipStreamSynchronize(d.stream);
+        if (rc != DV_OK) return rc;
+        DV_HIP_CHECK(waited);
+        for (int64_t& off : res->row_off) off += n_prefix;
+      }
+    } else {
+      if (int rc = dv::bgzf_compress_on_device(who, static_cast<const uint8_t*>(prefix), false, n_prefix, stream, res.get())) {
+        return rc;
+      }
+      if (in->want_row_off) res->row_off.assign(1, n_prefix);
+    }
+    stats.pieces = pieces;
+    stats.rows = pieces + c.nv;
+    stats.text_bytes = text_bytes;
+    meta->n_rows = pieces + c.nv;
+    meta->n_pieces = pieces;
+    meta->text_bytes = text_bytes;
+    meta->row_off = in->want_row_off ? res->row_off.data() : nullptr;
+    *file = res.release();
     return DV_OK;
   });
 }

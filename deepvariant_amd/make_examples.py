@@ -724,6 +724,9 @@ def make_examples_runner(args, log=sys.stderr, hooks: Optional[RunnerHooks] = No
           stats['gvcf_rows'] = postprocess_variants.last_rows_stats() if on_device else {}
         else:
           stats['gvcf_merge'] = postprocess_variants.last_merge_stats() if on_device else {}
+        if postprocess_variants.bgzf_switch() and gvcf_outfile.endswith('.gz'):
+          # the device compresses only behind its own rows; every other route uses the host code
+          stats['gvcf_bgzf'] = postprocess_variants.last_bgzf_stats() if rows == 'native' and on_device else {}
       stats['n_vcf_records'] = len(records)
       stats['n_examples'] = proc.vcf.n_examples     # also when no CallVariantsOutput record was asked for
       stats['genotype_device'] = dict(proc.vcf.device_stats)

@@ -14,6 +14,9 @@ The gVCF: `merge_blocks_and_variants` (dv_gvcf_merge) and
 records -- both return the same arrays -- and `gvcf_text` / `write_gvcf` print the rows; with rows='native'
 (DV_GVCF_ROWS_NATIVE=1) `gvcf_body_native` merges and prints in one native call (section 23, csrc/gvcf_rows.hip).
 Blocks travel as `allelecounter.GVCF_BLOCK_DTYPE` arrays per contig from end to end; no object is made per block.
+With DV_BGZF=1 a name that ends in .gz is written as BGZF: `bgzf_compress` is the host code
+(dv_bgzf_compress) or, with `device`, the kernels of csrc/bgzf.hip; with the native rows as well `gvcf_file_native`
+takes the whole .g.vcf.gz from one call (dv_gvcf_rows_bgzf[_device]), deflated on the device where the rows were written.
 
   python -m deepvariant_amd.postprocess_variants --infile CVO --ref FASTA --outfile VCF
       [--nonvariant_site_tfrecord_path GVCF_TFRECORDS --gvcf_outfile GVCF]
@@ -357,6 +360,10 @@ def _write_text(path: str, text: str) -> None:
 
 
 def _write_bytes(path: str, *chunks: bytes) -> None:
+  """DV_BGZF=1: a .gz name gets BGZF members from the host code (bgzf_compress) instead of one gzip stream."""
+  if path.endswith('.gz') and bgzf_switch():
+    _write_finished(path, bgzf_compress(b''.join(chunks)))
+    return
   with open(path, 'wb') as f:
     if path.endswith('.gz'):
       with gzip.GzipFile(filename='', fileobj=f, mode='wb', mtime=0) as z:     # the same bytes on every run
@@ -365,6 +372,81 @@ def _write_bytes(path: str, *chunks: bytes) -> None:
     else:
       for data in chunks:
         f.write(data)
+
+
+def _write_finished(path: str, data: bytes) -> None:
+  """The bytes as they are, whatever the name ends in."""
+  with open(path, 'wb') as f:
+    f.write(data)
+
+
+# ------------------------------------------------------------------------------------------ BGZF (section 24)
+@dataclasses.dataclass
+class BgzfFile:
+  """One native call's result (dv_bgzf_view, copied)."""
+  data: bytes                       # the members and the end-of-file member
+  block_coff: np.ndarray            # int64 [n_blocks + 1]: every member's offset, the end-of-file member's last
+  stored_blocks: int
+
+
+def bgzf_switch() -> bool:
+  """DV_BGZF=1: names that end in .gz are written as BGZF."""
+  return _env_on('DV_BGZF')
+
+
+def bgzf_params() -> Dict[str, int]:
+  """The constants of csrc/bgzf_deflate.h: block, tile, seg, hash_bits."""
+  params = _lib.DvBgzfParameters()
+  _lib.check(_lib.lib().dv_bgzf_params(C.byref(params)))
+  return {name: int(getattr(params, name)) for name, _ in params._fields_}
+
+
+def _take_bgzf(handle) -> BgzfFile:
+  l = _lib.lib()
+  try:
+    view = _lib.DvBgzfView()
+    _lib.check(l.dv_bgzf_arrays(handle, C.byref(view)))
+    coff = np.ctypeslib.as_array(C.cast(view.block_coff, C.POINTER(C.c_int64)), (view.n_blocks + 1,)).copy()
+    return BgzfFile(data=C.string_at(view.data, view.n_bytes), block_coff=coff, stored_blocks=int(view.stored_blocks))
+  finally:
+    l.dv_bgzf_free(handle)
+
+
+def bgzf_file(data, device: bool = False, stream=None) -> BgzfFile:
+  """dv_bgzf_compress, or dv_bgzf_compress_device with `device` (csrc/bgzf.hip).  data: bytes, or with `device` a
+  contiguous uint8 torch tensor in device memory, which is read where it lies."""
+  l = _lib.lib()
+  handle = C.c_void_p()
+  if hasattr(data, 'data_ptr'):
+    if not device:
+      raise ValueError('a tensor is compressed on the device')
+    if not data.is_cuda or not data.is_contiguous() or data.element_size() != 1:
+      raise ValueError('a contiguous one-byte tensor in device memory is expected')
+    if stream is None:        # the library's own stream does not wait for the tensor's
+      import torch  # device memory + stream only
+      torch.cuda.current_stream(data.device).synchronize()
+    _lib.check(l.dv_bgzf_compress_device(C.c_void_p(data.data_ptr() or None), _lib.DV_MEM_DEVICE, data.numel(),
+                                         C.byref(handle), C.c_void_p(stream or None)))
+    return _take_bgzf(handle)
+  data = bytes(data)
+  text = C.cast(C.c_char_p(data), C.c_void_p)
+  if device:
+    _lib.check(l.dv_bgzf_compress_device(text, _lib.DV_MEM_HOST, len(data), C.byref(handle), C.c_void_p(stream or None)))
+  else:
+    _lib.check(l.dv_bgzf_compress(text, len(data), C.byref(handle)))
+  return _take_bgzf(handle)
+
+
+def bgzf_compress(data, device: bool = False, stream=None) -> bytes:
+  """data as a BGZF file: members of at most bgzf_params()['block'] input bytes and the end-of-file member."""
+  return bgzf_file(data, device, stream).data
+
+
+def last_bgzf_stats() -> Dict[str, int]:
+  """What the calling thread's last device compression did."""
+  stats = _lib.DvBgzfStats()
+  _lib.check(_lib.lib().dv_bgzf_last_stats(C.byref(stats)))
+  return {name: int(getattr(stats, name)) for name, _ in stats._fields_}
 
 
 def fasta_contigs(ref_reader) -> List[Tuple[str, int]]:
@@ -598,6 +680,10 @@ def write_gvcf(path: str, records: Sequence[VcfRecord], blocks_by_contig: Dict[s
                contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None,
                rows: str = 'python') -> None:
   """The .gz rule is write_vcf's.  rows as for gvcf_text; the native body goes to the file as the bytes it is."""
+  if rows == 'native' and path.endswith('.gz') and bgzf_switch():
+    _write_finished(path, gvcf_file_native(records, blocks_by_contig, ref_reader, contigs, sample_name, device,
+                                           stream).file.data)
+    return
   if rows == 'native':
     header, body = _native_gvcf(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream)
     _write_bytes(path, header.encode(), body)
@@ -622,6 +708,29 @@ def gvcf_rows_native(block_off, var_off, blocks, var_start, var_end, var_end_bas
   carried on to the text.  blocks: GVCF_BLOCK_DTYPE [B] over all groups; var_end_base: uint8 [V], the reference base at
   every variant's end; var_text_off [V + 1] into var_text, the variants' finished rows; name_off [G + 1] into names,
   the groups' contig names; med_dp: -1 = MED_DP when any block has one, else 0 or 1."""
+  arg, _alive = _rows_input(block_off, var_off, blocks, var_start, var_end, var_end_base, var_text_off, var_text, name_off,
+                            names, med_dp, want_row_off)
+  l = _lib.lib()
+  handle = C.c_void_p()
+  if device:
+    _lib.check(l.dv_gvcf_rows_device(C.byref(arg), C.byref(handle), C.c_void_p(stream or None)))
+  else:
+    _lib.check(l.dv_gvcf_rows(C.byref(arg), C.byref(handle)))
+  try:
+    view = _lib.DvGvcfTextView()
+    _lib.check(l.dv_gvcf_text_arrays(handle, C.byref(view)))
+    row_off = None
+    if want_row_off:
+      row_off = np.ctypeslib.as_array(C.cast(view.row_off, C.POINTER(C.c_int64)), (view.n_rows + 1,)).copy()
+    return GvcfBody(text=C.string_at(view.text, view.n_bytes), row_off=row_off, med_dp=bool(view.med_dp),
+                    n_pieces=int(view.n_pieces))
+  finally:
+    l.dv_gvcf_text_free(handle)
+
+
+def _rows_input(block_off, var_off, blocks, var_start, var_end, var_end_base, var_text_off, var_text: bytes, name_off,
+                names: bytes, med_dp: int, want_row_off: bool):
+  """-> (a dv_gvcf_rows_input, what its pointers point into)."""
   ints = [np.ascontiguousarray(a, np.int64).reshape(-1) for a in (block_off, var_off, var_start, var_end, var_text_off,
                                                                   name_off)]
   b_off, v_off, v_start, v_end, text_off, n_off = ints
@@ -641,22 +750,39 @@ def gvcf_rows_native(block_off, var_off, blocks, var_start, var_end, var_end_bas
       var_end_base=bases.ctypes.data, var_text_off=text_off.ctypes.data,
       var_text=C.cast(C.c_char_p(var_text), C.c_void_p), name_off=n_off.ctypes.data,
       names=C.cast(C.c_char_p(names), C.c_void_p))
+  return arg, (ints, blocks, bases, var_text, names)
+
+
+@dataclasses.dataclass
+class GvcfFile:
+  """One dv_gvcf_rows_bgzf[_device] call's result: the compressed gVCF and what its text was."""
+  file: BgzfFile
+  text_bytes: int                   # the prefix and the rows
+  n_rows: int
+  n_pieces: int
+  row_off: Optional[np.ndarray]     # int64 [rows + 1] into prefix + rows when asked for
+
+
+def gvcf_rows_bgzf_native(prefix: bytes, block_off, var_off, blocks, var_start, var_end, var_end_base, var_text_off,
+                          var_text: bytes, name_off, names: bytes, med_dp: int, want_row_off: bool = False,
+                          device: bool = False, stream=None) -> GvcfFile:
+  """gvcf_rows_native's rows behind `prefix`, compressed by the same call (section 24): on the device the text is
+  deflated where the rows were written and only the file comes back.  med_dp: 0 or 1, as the prefix says."""
+  arg, _alive = _rows_input(block_off, var_off, blocks, var_start, var_end, var_end_base, var_text_off, var_text, name_off,
+                            names, med_dp, want_row_off)
   l = _lib.lib()
-  handle = C.c_void_p()
+  handle, meta = C.c_void_p(), _lib.DvGvcfRowsMeta()
+  lead = C.cast(C.c_char_p(prefix), C.c_void_p)
   if device:
-    _lib.check(l.dv_gvcf_rows_device(C.byref(arg), C.byref(handle), C.c_void_p(stream or None)))
+    _lib.check(l.dv_gvcf_rows_bgzf_device(C.byref(arg), lead, len(prefix), C.byref(meta), C.byref(handle),
+                                          C.c_void_p(stream or None)))
   else:
-    _lib.check(l.dv_gvcf_rows(C.byref(arg), C.byref(handle)))
-  try:
-    view = _lib.DvGvcfTextView()
-    _lib.check(l.dv_gvcf_text_arrays(handle, C.byref(view)))
-    row_off = None
-    if want_row_off:
-      row_off = np.ctypeslib.as_array(C.cast(view.row_off, C.POINTER(C.c_int64)), (view.n_rows + 1,)).copy()
-    return GvcfBody(text=C.string_at(view.text, view.n_bytes), row_off=row_off, med_dp=bool(view.med_dp),
-                    n_pieces=int(view.n_pieces))
-  finally:
-    l.dv_gvcf_text_free(handle)
+    _lib.check(l.dv_gvcf_rows_bgzf(C.byref(arg), lead, len(prefix), C.byref(meta), C.byref(handle)))
+  row_off = None
+  if want_row_off:          # the handle owns it: copy before _take_bgzf frees the handle
+    row_off = np.ctypeslib.as_array(C.cast(meta.row_off, C.POINTER(C.c_int64)), (meta.n_rows + 1,)).copy()
+  return GvcfFile(file=_take_bgzf(handle), text_bytes=int(meta.text_bytes), n_rows=int(meta.n_rows),
+                  n_pieces=int(meta.n_pieces), row_off=row_off)
 
 
 def last_rows_stats() -> Dict[str, int]:
@@ -672,6 +798,12 @@ def gvcf_body_native(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, n
   """gvcf_rows with the block rows made by the native code, on the host or with `device` on the device: the records
   and blocks are sorted and grouped as there, the variants' rows are gvcf_variant_row's, and one native call merges
   and prints.  One get_bases per contig that has variants, over the variant ends below the contig's length."""
+  return gvcf_rows_native(**_native_arguments(records, blocks_by_contig, ref_reader, contigs), want_row_off=want_row_off,
+                          device=device, stream=stream)
+
+
+def _native_arguments(records, blocks_by_contig, ref_reader, contigs) -> dict:
+  """gvcf_rows_native's arrays for the records and blocks of a gVCF."""
   order = {name: k for k, (name, _) in enumerate(contigs)}
   for name in list(blocks_by_contig) + [r.reference_name for r in records]:
     if name not in order:
@@ -702,10 +834,21 @@ def gvcf_body_native(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, n
   texts = [gvcf_variant_row(r).encode() for r in records]
   var_text_off = np.zeros(len(texts) + 1, np.int64)
   np.cumsum([len(t) for t in texts], out=var_text_off[1:])
-  return gvcf_rows_native(block_off, var_off, np.concatenate(blocks) if blocks else np.zeros(0, dtype),
-                          np.array([r.start for r in records], np.int64), var_end, var_end_base, var_text_off,
-                          b''.join(texts), name_off, b''.join(names), want_row_off=want_row_off, device=device,
-                          stream=stream)
+  return dict(block_off=block_off, var_off=var_off, blocks=np.concatenate(blocks) if blocks else np.zeros(0, dtype),
+              var_start=np.array([r.start for r in records], np.int64), var_end=var_end, var_end_base=var_end_base,
+              var_text_off=var_text_off, var_text=b''.join(texts), name_off=name_off, names=b''.join(names))
+
+
+def gvcf_file_native(records: Sequence[VcfRecord], blocks_by_contig: Dict[str, np.ndarray], ref_reader,
+                     contigs: Sequence[Tuple[str, int]], sample_name: str, device: bool = False, stream=None,
+                     want_row_off: bool = False) -> GvcfFile:
+  """The whole .g.vcf.gz from one native call: the header goes in as the prefix, so whether it names MED_DP is
+  decided here, as gvcf_rows decides it."""
+  args = _native_arguments(records, blocks_by_contig, ref_reader, contigs)
+  med_dp = bool((args['blocks']['med_dp'] >= 0).any())
+  header = vcf_header(contigs, sample_name, _GVCF_HEADER + ((_GVCF_HEADER_MED_DP,) if med_dp else ()))
+  return gvcf_rows_bgzf_native(header.encode(), med_dp=int(med_dp), want_row_off=want_row_off, device=device,
+                               stream=stream, **args)
 
 
 def _native_gvcf(records, blocks_by_contig, ref_reader, contigs, sample_name, device, stream) -> Tuple[str, bytes]:

@@ -1896,6 +1896,64 @@ typedef struct dv_gvcf_rows_stats {
 /* What the calling thread's last dv_gvcf_rows_device did. */
 int dv_gvcf_rows_last_stats(dv_gvcf_rows_stats* out);
 
+/* ---- BGZF: a text deflated into members of at most 64 KiB (csrc/bgzf.hip) ----
+ * The text is cut every `block` bytes; every block becomes one BGZF member (one deflate block: fixed Huffman over the
+ * tokens of csrc/bgzf_deflate.h, or stored when that is shorter), and the 28-byte end-of-file member follows.  An
+ * empty text gives the end-of-file member alone.  The host code and the device write the same bytes.
+ * Null pointers, a negative n and an unknown `memory` are DV_ERR_INVALID_ARGUMENT; on any error *out is NULL. */
+typedef struct dv_bgzf_parameters {
+  int32_t block;                /* input bytes per member */
+  int32_t tile;                 /* positions that read their candidates before any of them is entered */
+  int32_t seg;                  /* bytes parsed greedily from their own start */
+  int32_t hash_bits;
+} dv_bgzf_parameters;
+int dv_bgzf_params(dv_bgzf_parameters* out);
+typedef struct dv_bgzf_file dv_bgzf_file;     /* owns one call's file */
+typedef struct dv_bgzf_view {                 /* views into the result; valid until dv_bgzf_free */
+  const uint8_t* data;          /* the members, then the end-of-file member */
+  int64_t n_bytes;
+  int64_t n_blocks;             /* the members with text */
+  const int64_t* block_coff;    /* [n_blocks + 1]: every member's offset in the file, the end-of-file member's last */
+  int64_t stored_blocks;        /* the members whose block is stored */
+} dv_bgzf_view;
+/* Host code; the blocks are spread over host threads. */
+int dv_bgzf_compress(const void* text, int64_t n, dv_bgzf_file** out);
+/* The same on the device; `text` is read where it lies (memory: dv_memory).  One staged upload (the text too when it
+ * is a host array), five launches queued on `stream` (NULL = a non-blocking stream the library owns), a wait for the
+ * 16-byte header, then a download of exactly n_bytes and block_coff and a second wait.  An empty text is DV_OK
+ * without a device and launches nothing; no device is DV_ERR_NO_DEVICE. */
+int dv_bgzf_compress_device(const void* text, int32_t memory, int64_t n, dv_bgzf_file** out, void* stream);
+int dv_bgzf_arrays(const dv_bgzf_file* f, dv_bgzf_view* out);
+void dv_bgzf_free(dv_bgzf_file* f);
+typedef struct dv_bgzf_stats {
+  int64_t text_bytes;
+  int64_t file_bytes;
+  int64_t blocks;
+  int64_t stored_blocks;
+  int64_t launches;
+  int64_t bytes_up;             /* the CRC tables, and the text when it was a host array */
+  int64_t bytes_down;           /* 16 + the file + block_coff */
+} dv_bgzf_stats;
+/* What the calling thread's last device compression did (dv_bgzf_compress_device, or the one inside
+ * dv_gvcf_rows_bgzf_device). */
+int dv_bgzf_last_stats(dv_bgzf_stats* out);
+
+/* dv_gvcf_rows[_device] with `prefix` (the header, n_prefix bytes) in front, compressed instead of returned: *file is
+ * the BGZF file of prefix + rows, *meta says what the text was.  in->med_dp must be 0 or 1 here, since the header that
+ * names MED_DP is written before the call.  Refused: everything dv_gvcf_rows refuses, a negative n_prefix, med_dp -1.
+ * On the device the text is never downloaded: the rows are written behind the prefix in device memory and deflated
+ * there; dv_gvcf_rows_last_stats then counts the rows' launches and bytes, dv_bgzf_last_stats the compressor's. */
+typedef struct dv_gvcf_rows_meta {
+  int64_t n_rows;
+  int64_t n_pieces;
+  int64_t text_bytes;           /* n_prefix + the rows */
+  const int64_t* row_off;       /* [n_rows + 1] into prefix + rows with want_row_off, else NULL; freed with *file */
+} dv_gvcf_rows_meta;
+int dv_gvcf_rows_bgzf(const dv_gvcf_rows_input* in, const void* prefix, int64_t n_prefix, dv_gvcf_rows_meta* meta,
+                      dv_bgzf_file** file);
+int dv_gvcf_rows_bgzf_device(const dv_gvcf_rows_input* in, const void* prefix, int64_t n_prefix, dv_gvcf_rows_meta* meta,
+                             dv_bgzf_file** file, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
