@@ -1635,7 +1635,10 @@ int dv_model_apply_corrections(dv_model* m, const float* corrections, int64_t n)
  * storing that tensor wider than fp16 would buy; NULL = the product's own rounding points.  flags bit 0: E multiplies
  * the float32 weights (isolates the activation roundings); bit 1: measure the corrections on these images under this
  * plan (the calibration proper; `corrections` must be NULL) and report them in `corrections_out` (optional, the
- * layout of dv_model_calibrate).  The model's state is not changed.  tools/r6_tensor_budget.py;
+ * layout of dv_model_calibrate).  The model's state is not changed.  dv_model_num_ops(NULL) is 0; dv_model_op_label
+ * writes "kind key=value ..." (at most capacity - 1 characters and a terminating NUL: a short buffer gets a truncated
+ * label) and refuses an index outside 0 .. dv_model_num_ops - 1, a NULL buffer or capacity < 1 with
+ * DV_ERR_INVALID_ARGUMENT, writing nothing.  tools/r6_tensor_budget.py, tests/test_hip_calib_pipelines.py;
  * no reference counterpart (deepvariant/call_variants.py:913-918 computes in float32 end to end). */
 int dv_model_num_ops(const dv_model* m);
 int dv_model_op_label(const dv_model* m, int op_index, char* buf, int capacity);

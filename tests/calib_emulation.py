@@ -1,7 +1,8 @@
 """torch restatement of the product's shift calibration (deepvariant_amd/csrc/calib.hip) -- test infrastructure.
 
-Two walks of the oracle's graph (oracle/inception_ref.py) with the product's rounding points: R in float32 as
-given; E with BN-folded weights rounded to fp16 and every stored fp16 activation rounded to fp16 (the pooled
+Two walks of the oracle's graph (oracle/inception_ref.py) with the product's rounding points: R in the oracle's
+own dtype as given (float32; a .double() copy of the oracle gives the float64 reference of
+tests/test_calib_reference_cpu.py and tests/test_hip_calib_pipelines.py); E with BN-folded weights rounded to fp16 and every stored fp16 activation rounded to fp16 (the pooled
 projections in the product's commuted order: raw 1x1 conv, float32 -> average pool -> + shift -> ReLU -> round; the
 last block's outputs stay float32 for the global pool -- round 6, BufferDesc::f32 in csrc/model_graph.h).
 corr[layer][c] = mean_E(pre-activation) - mean_R(pre-activation), applied in E before the next layer.
@@ -23,31 +24,32 @@ class _Walk:
     self.ref, self.e, self.ref_means = ref, mode_e, ref_means
     self.precise = precise        # precise mode (> 8 input channels): the 17x17 and 8x8 stages' tensors are hi + lo: not rounded
     self.wide = False
+    self.dtype = ref.classification.weight.dtype   # the oracle's: float32, or float64 for a .double() copy (mode R)
     self.index = {id(cb): i for i, cb in enumerate(ref.convs)}
     self.means = [None] * len(ref.convs)
     self.corr = [None] * len(ref.convs)
 
   def _r(self, x):
-    return x.half().float() if self.e else x
+    return x.half().to(x.dtype) if self.e else x
 
   def _act(self, i, z, keep_f32=False):
     self.means[i] = z.double().mean(dim=(0, 2, 3))
     if self.e:
-      self.corr[i] = (self.means[i] - self.ref_means[i]).float()
+      self.corr[i] = (self.means[i] - self.ref_means[i]).float().to(z.dtype)
       z = z - self.corr[i][None, :, None, None]
     return F.relu(z if keep_f32 or self.wide else self._r(z))
 
   def conv(self, cb, x, keep_f32=False):
     w, shift = _folded(cb)
     if self.e:
-      w = w.half().float()
+      w = w.half().to(x.dtype)
     z = F.conv2d(x, w, None, cb.conv.stride, cb.conv.padding) + shift[None, :, None, None]
     return self._act(self.index[id(cb)], z, keep_f32)
 
   def pooled_projection(self, cb, x, keep_f32=False):
     w, shift = _folded(cb)
     if self.e:
-      w = w.half().float()
+      w = w.half().to(x.dtype)
     raw = F.conv2d(x, w)            # float32 in LDS / in a float32 tensor: never rounded
     z = F.avg_pool2d(raw, 3, stride=1, padding=1, count_include_pad=False) + shift[None, :, None, None]
     return self._act(self.index[id(cb)], z, keep_f32)
@@ -59,7 +61,7 @@ class _Walk:
 
   def logits(self, images_u8):
     ref, c = self.ref, self.conv
-    x = ((images_u8.float() - 128.0) / 128.0).permute(0, 3, 1, 2).contiguous()
+    x = ((images_u8.to(self.dtype) - 128.0) / 128.0).permute(0, 3, 1, 2).contiguous()
     s = ref.stem
     x = c(s[2], c(s[1], c(s[0], x)))
     x = F.max_pool2d(x, 3, stride=2)
